@@ -6,6 +6,7 @@
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...          # bare: the parent spawns the N ranks itself (before it touches torch or the GPU)
     python bench.py --config c2|c4|c5|c5m16  # the other BASELINE.json workloads, same JSON schema (default c3 = the headline)
+    python bench.py ... --dump-outputs DIR   # also write the last timed step's loss and updated parameters as DIR/*.npy
 
 A step = one full ClassifierTrainer.train_step (forward, loss, backward, bucketed RCCL
 gradient all-reduce when N > 1, fused AdamW) on one synthetic batch already resident in HBM.
@@ -279,9 +280,32 @@ def make_step(args, trainer, batches):
     return one_step
 
 
-def run_leg(args, dtype, steps, warmup, ctx, world, rank):
+DUMP_SAMPLE = 1 << 23              # parameters written by --dump-outputs at most: 32 MB of float32
+
+
+def dump_outputs(out_dir, loss, trainer):
+    """--dump-outputs: what the last timed step handed its caller -- the loss it returned (`loss.npy`, float64) and the
+    f32 parameters it left after the update (`params.npy`, float32; `params<i>.npy` per arena when there are several).
+    An arena of more than DUMP_SAMPLE parameters is written at DUMP_SAMPLE distinct positions drawn from a seeded
+    generator, in ascending order (the same positions in every run of the same workload)."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.asarray([float(loss)], np.float64))
+    arenas = trainer._arenas()
+    for i, arena in enumerate(arenas):
+        n = arena.extent
+        flat = arena.params[:n]
+        if n > DUMP_SAMPLE:
+            idx = np.sort(np.random.Generator(np.random.PCG64(2024 + i)).choice(n, DUMP_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        name = "params.npy" if len(arenas) == 1 else f"params{i}.npy"
+        np.save(os.path.join(out_dir, name), flat.detach().float().cpu().numpy())
+
+
+def run_leg(args, dtype, steps, warmup, ctx, world, rank, dump_dir=None):
     """W untimed + K timed steps of the workload on the `dtype` engine, then one instrumented
-    step (HIP events around every GEMM launch).  Returns the numbers of the JSON line for that engine."""
+    step (HIP events around every GEMM launch).  Returns the numbers of the JSON line for that engine.
+    `dump_dir`: rank 0 writes the outputs of the last timed step there (dump_outputs) before the instrumented step."""
     import torch
     from polus_amd import comm, ops
     H, A, I, L = args.geom
@@ -340,6 +364,8 @@ def run_leg(args, dtype, steps, warmup, ctx, world, rank):
     last_loss = float(last)
     elapsed = comm.max_over_ranks(elapsed)
     trainer.measure_exposed = False
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, last, trainer)
 
     # ---- instrumented step: HIP events (recorded on the launch stream) around every GEMM launch.
     # Every rank takes the step -- it contains the gradient all-reduce -- only rank 0 records.  The dW
@@ -473,7 +499,11 @@ def main():
     ap.add_argument("--no-loss100", action="store_true", help="skip the 2 x 100-step loss@step100 runs")
     ap.add_argument("--graph", action="store_true", help="replay the step from a captured HIP graph (launch-bound shapes, one GPU)")
     ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 --pmc child passes behind roofline.traffic")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss and the updated parameters of the last timed step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N`: nothing has touched torch or the GPU in this process
@@ -514,7 +544,7 @@ def main():
         args.dropout = 0.0 if args.kind == "ir" else args.dropout
     plane = comm.data_plane_info() if world > 1 else None
 
-    head = run_leg(args, args.dtype, args.steps, args.warmup, ctx, world, rank)
+    head = run_leg(args, args.dtype, args.steps, args.warmup, ctx, world, rank, dump_dir=args.dump_outputs)
     # the reference computes in fp32 throughout (polus/models.py:197): the same workload on the f32 engine
     # (exact-f32 MFMA), timed in the same run on every rank; fewer steps, it is ~6x slower
     f32 = None

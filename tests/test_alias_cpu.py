@@ -1,5 +1,5 @@
 """CPU: the `polus` import path.  The import block of the reference's tutorial
-(/root/reference/tutorials/classifier_example.py:1-5, minus `import tensorflow`) and of its other user-facing
+(tutorials/classifier_example.py:1-5 of the reference, minus `import tensorflow`) and of its other user-facing
 modules resolves, unchanged, to the MI355X engine's classes."""
 
 

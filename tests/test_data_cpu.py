@@ -1,5 +1,5 @@
 """CPU: the host input pipeline (polus_amd/data.py) behaves as the reference's own data tests demand
-(/root/reference/tests/test_data.py:28-345 -- order preservation, get_n_samples, cache `.index` / `.part` /
+(tests/test_data.py:28-345 of the reference -- order preservation, get_n_samples, cache `.index` / `.part` /
 `.lookup` files on disk, pre_shuffle breaking the order at chunk level, merge counts 1000+500+721,
 from_cached_index), plus the tf.data-like chain the tutorials build (map / cache / shuffle / batch / prefetch)
 and the rank-sharding rule of polus/data.py:94-96."""

@@ -1,5 +1,5 @@
 import os, sys, numpy as np, torch
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from polus_amd import ops
 dt = torch.bfloat16
 g = torch.Generator(device="cuda").manual_seed(1)
