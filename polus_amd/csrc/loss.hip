@@ -7,7 +7,8 @@
 
 namespace {
 
-constexpr int CRF_MAXC = 16;
+constexpr int CRF_MAXC = 16;     // one thread per sequence up to here; crf.hip's workgroup-per-sequence kernels above
+constexpr int CRF_WG_MAXC = 128;
 
 // sum `partial[0..n)` in index order -> *out * mul
 __global__ void finalize_sum_kernel(const float* __restrict__ partial, int n, float mul, float* __restrict__ out) {
@@ -219,6 +220,14 @@ __global__ void crf_viterbi_kernel(const float* __restrict__ pot, const int32_t*
 
 }  // namespace
 
+// crf.hip: 17 <= C <= 128
+size_t polus_crf_wg_workspace_bytes(int B, int S, int C);
+int polus_crf_nll_wg(int dtype, const float* pot, const int32_t* tags, const int32_t* lengths, const float* trans,
+                     const float* sw, float* loss, void* dpot, float* dtrans, int accumulate, int B, int S, int C,
+                     void* workspace, hipStream_t st);
+int polus_crf_viterbi_wg(const float* pot, const int32_t* lengths, const float* trans, int32_t* out, int B, int S,
+                         int C, void* workspace, hipStream_t st);
+
 extern "C" size_t polus_loss_workspace_bytes(int rows) { return ((size_t)(rows + 255) / 256 + 1) * sizeof(float); }
 
 extern "C" int polus_softmax_xent(int dtype, const float* logits, long ldl, const int32_t* labels,
@@ -300,6 +309,7 @@ extern "C" int polus_argmax(const float* x, long ldx, int32_t* out, int rows, in
 }
 
 extern "C" size_t polus_crf_workspace_bytes(int B, int S, int C) {
+    if (C > CRF_MAXC) return polus_crf_wg_workspace_bytes(B, S, C);
     // alpha (or viterbi back-pointers) [B,S,C] + per-sequence nll [B] + per-sequence dtrans [B,C,C]
     return ((size_t)B * S * C + (size_t)B + (size_t)B * C * C) * sizeof(float) + 64;
 }
@@ -309,9 +319,11 @@ extern "C" int polus_crf_nll(int dtype, const float* potentials, const int32_t* 
                              float* dtrans, int accumulate, int B, int S, int C,
                              void* workspace, size_t workspace_bytes, void* stream) {
     POLUS_REQUIRE(potentials && tags && trans && loss && dpot && dtrans, "polus_crf_nll: null pointer");
-    POLUS_REQUIRE(B > 0 && S > 0 && C > 0 && C <= CRF_MAXC, "polus_crf_nll: need 0 < C <= %d (got %d)", CRF_MAXC, C);
+    POLUS_REQUIRE(B > 0 && S > 0 && C > 0 && C <= CRF_WG_MAXC, "polus_crf_nll: need 0 < C <= %d (got %d)", CRF_WG_MAXC, C);
     if (!workspace || workspace_bytes < polus_crf_workspace_bytes(B, S, C)) { polus_set_error("polus_crf_nll: workspace too small"); return POLUS_ERR_WORKSPACE; }
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (C > CRF_MAXC)
+        return polus_crf_nll_wg(dtype, potentials, tags, lengths, trans, sample_w, loss, dpot, dtrans, accumulate, B, S, C, workspace, st);
     float* alpha = static_cast<float*>(workspace);
     float* nll_b = alpha + (size_t)B * S * C;
     float* dtb = nll_b + B;
@@ -331,8 +343,10 @@ extern "C" int polus_crf_viterbi(const float* potentials, const int32_t* lengths
                                  int32_t* out_tags, int B, int S, int C,
                                  void* workspace, size_t workspace_bytes, void* stream) {
     POLUS_REQUIRE(potentials && trans && out_tags, "polus_crf_viterbi: null pointer");
-    POLUS_REQUIRE(B > 0 && S > 0 && C > 0 && C <= CRF_MAXC, "polus_crf_viterbi: need 0 < C <= %d", CRF_MAXC);
+    POLUS_REQUIRE(B > 0 && S > 0 && C > 0 && C <= CRF_WG_MAXC, "polus_crf_viterbi: need 0 < C <= %d (got %d)", CRF_WG_MAXC, C);
     if (!workspace || workspace_bytes < polus_crf_workspace_bytes(B, S, C)) { polus_set_error("polus_crf_viterbi: workspace too small"); return POLUS_ERR_WORKSPACE; }
+    if (C > CRF_MAXC)
+        return polus_crf_viterbi_wg(potentials, lengths, trans, out_tags, B, S, C, workspace, static_cast<hipStream_t>(stream));
     hipLaunchKernelGGL(crf_viterbi_kernel, dim3((B + 63) / 64), dim3(64), 0, static_cast<hipStream_t>(stream),
                        potentials, lengths, trans, out_tags, static_cast<int32_t*>(workspace), B, S, C);
     POLUS_CHECK_LAUNCH("polus_crf_viterbi");

@@ -254,7 +254,7 @@ class CRF(Layer):
 
     def get_transitions(self):
         """polus/layers.py:58-63 — T*M + (1-M)*-10000; a tiny [C,C] host-side parameter
-        transform re-uploaded per step (C <= 16)."""
+        transform re-uploaded per step (C <= 128)."""
         t = self.transitions.value
         if self.mask_impossible_transitions is None:
             return t
