@@ -1492,7 +1492,7 @@ extern "C" int polus_attention_bwd(int dtype, const void* qkv, const int32_t* ma
     a.qkv = qkv; a.mask = mask; a.ctx = const_cast<void*>(ctx); a.lse = const_cast<float*>(lse); a.dctx = dctx; a.dqkv = dqkv;
     a.delta = static_cast<const float*>(workspace);
     a.B = B; a.S = S; a.A = n_heads; a.H = n_heads * D; a.scale = 0.125f;
-    POLUS_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "polus_attention_bwd: bad drop_p");
+    POLUS_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (long)B * n_heads * S * S < (1LL << 32), "polus_attention_bwd: bad dropout arguments");
     a.drop_thresh = drop_p > 0.f ? polus_drop_thresh(drop_p) : 0u; a.drop_seed = seed; a.drop_inv = 1.0f / (1.0f - drop_p); a.dyn = polus_dyn();
     a.debug = polus_cfg().attn_debug;
     hipStream_t st = static_cast<hipStream_t>(stream);

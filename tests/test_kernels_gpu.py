@@ -139,6 +139,24 @@ def test_gemm_rejects_bad_arguments(ops):
         ops.gemm(a.cpu(), a.cpu(), a.cpu())
 
 
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_attention_rejects_dropout_index_overflow(ops, dtype):
+    """The attention dropout index ((b A + h) S + q) S + key is a uint32: both directions refuse B * A * S^2 >= 2^32
+    before launching anything."""
+    from polus_amd._lib import PolusHipError
+    B, S, A = 1, 65536, 1
+    qkv = torch.zeros((B * S, 192), dtype=dtype, device="cuda")
+    ctx = torch.zeros((B * S, 64), dtype=dtype, device="cuda")
+    lse = torch.zeros((B, A, S), device="cuda")
+    with pytest.raises(PolusHipError, match="dropout"):
+        ops.attention_fwd(qkv, None, ctx, lse, B, S, A, drop_p=0.1, seed=1)
+    dqkv = torch.full_like(qkv, 7.0)
+    with pytest.raises(PolusHipError, match="dropout"):
+        ops.attention_bwd(qkv, None, ctx, torch.zeros_like(ctx), lse, dqkv, B, S, A, drop_p=0.1, seed=1)
+    torch.cuda.synchronize()
+    assert bool((dqkv == 7.0).all())                    # nothing was launched
+
+
 # ------------------------------------------------------------------------------- attention
 def _attn_case(B, S, A, seed, full_mask=False):
     r = rng(seed)
