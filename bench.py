@@ -7,11 +7,14 @@
     python bench.py --gpus N ...          # bare: the parent spawns the N ranks itself (before it touches torch or the GPU)
     python bench.py --config c2|c4|c5|c5m16  # the other BASELINE.json workloads, same JSON schema (default c3 = the headline)
     python bench.py ... --dump-outputs DIR   # also write the last timed step's loss and updated parameters as DIR/*.npy
+    python bench.py ... --full               # also measure everything below the headline (roofline, f32 leg, loss@step100, ...)
 
 A step = one full ClassifierTrainer.train_step (forward, loss, backward, bucketed RCCL
 gradient all-reduce when N > 1, fused AdamW) on one synthetic batch already resident in HBM.
 Weak scaling: per-GPU batch fixed.  Rank 0 prints ONE JSON line.
 
+A plain run does only what the headline figure needs: it sets up, warms up, times the steps, writes --dump-outputs, and
+prints the line.  Everything else it can measure runs with `--full` only (the --no-* switches then drop parts of it):
 `roofline` describes the dominant kernel (the bf16 MFMA GEMM of the forward Dense layers):
 its launches are bracketed with HIP events during one extra instrumented step after the
 timed region; achieved = algorithmic FLOPs of those launches / their summed device time.
@@ -20,8 +23,9 @@ timed region; achieved = algorithmic FLOPs of those launches / their summed devi
 the same run; `loss_at_step100` is BASELINE.json's loss@step100 for both engines (dropout 0).
 `cpu_baseline` times a torch-CPU eager fp32 restatement of the identical step (fwd + bwd + AdamW,
 oracle/bert_torch.py) on the host cores of this box, on a bounded sample (B=8, 3 + 5 steps): a reported
-baseline, not the target.  `roofline.traffic` (full default run, one GPU): HBM bytes per launch of that kernel family from two
-counters-only `rocprofv3 --pmc` passes over a 2-step child run of this script, started before this process touches the GPU.
+baseline, not the target.  `roofline.traffic` (`--full` at the headline shape, one GPU): HBM bytes per launch of that kernel family
+from two counters-only `rocprofv3 --pmc` passes over a 2-step child run of this script, started before this process touches the GPU.
+At N > 1, `ms_per_step_nocomm` times the same steps with every rank training alone.
 """
 import argparse
 import json
@@ -106,7 +110,7 @@ def measure_hbm_traffic(extra_argv=()):
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         out = tempfile.mkdtemp(prefix="polus_pmc_", dir="/tmp")
         cmd = [prof, "--pmc", counter, "--output-format", "csv", "-d", out, "--", sys.executable, os.path.abspath(__file__),
-               "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-f32-leg", "--no-loss100", "--no-traffic"] + list(extra_argv)
+               "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-f32-leg", "--no-loss100", "--no-traffic"] + list(extra_argv)
         env = dict(os.environ, TMPDIR="/tmp", POLUS_BENCH_CHILD="1")
         try:
             p = subprocess.Popen(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
@@ -303,7 +307,7 @@ def dump_outputs(out_dir, loss, trainer):
 
 
 def run_leg(args, dtype, steps, warmup, ctx, world, rank, dump_dir=None):
-    """W untimed + K timed steps of the workload on the `dtype` engine, then one instrumented
+    """W untimed + K timed steps of the workload on the `dtype` engine, then with --full one instrumented
     step (HIP events around every GEMM launch).  Returns the numbers of the JSON line for that engine.
     `dump_dir`: rank 0 writes the outputs of the last timed step there (dump_outputs) before the instrumented step."""
     import torch
@@ -367,53 +371,55 @@ def run_leg(args, dtype, steps, warmup, ctx, world, rank, dump_dir=None):
     if dump_dir is not None and rank == 0:
         dump_outputs(dump_dir, last, trainer)
 
-    # ---- instrumented step: HIP events (recorded on the launch stream) around every GEMM launch.
+    peak = PEAK_TFLOPS[dtype]
+    roof = None
+    # ---- --full: an instrumented step, HIP events (recorded on the launch stream) around every GEMM launch.
     # Every rank takes the step -- it contains the gradient all-reduce -- only rank 0 records.  The dW
     # GEMMs normally run beside the dX GEMMs on a side stream; an event pair would then time two kernels
     # sharing the CUs, and the optimizer update normally starts inside backward on a third stream; this one
     # step keeps everything on one stream (as the rocprof summaries under profiles/ do with POLUS_OVERLAP_DW=0
     # POLUS_UPDATE_IN_BACKWARD=0).
-    roof, rec = None, []
-    if rank == 0:
-        ops.GEMM_PROFILE = rec
-    enc = getattr(model, "query_encoder", model)
-    overlap = getattr(enc, "overlap_dw", False)
-    enc.overlap_dw = False
-    trainer.update_in_backward = False
-    one_step(warmup + steps)
-    torch.cuda.synchronize()
-    enc.overlap_dw = overlap
-    trainer.update_in_backward = True
-    ops.GEMM_PROFILE = None
-    peak = PEAK_TFLOPS[dtype]
-    if rank == 0:
-        fwd = [(e0.elapsed_time(e1) * 1e-3, fl) for (key, fl, e0, e1) in rec if key == "fwd"]
-        if fwd:
-            tsum, fsum = sum(t for t, _ in fwd), sum(f for _, f in fwd)
-            ach = fsum / tsum / 1e12
-            kern = ("gemm_pp_kernel<256 x 256 | 256 x 192, epilogue mode 0-3> (ping-pong; the ring kernels gemm_ring_kernel<bf16> / "
-                    "gemm_ring128_kernel where a launch would leave CUs idle)" if dtype == "bf16" else "gemm_kernel<f32, K-contig, K-contig> (exact-f32 MFMA 16x16x4)")
-            roof = {"bound": "mfma", "achieved": round(ach, 2), "peak": peak, "unit": "TFLOP/s",
-                    "frac": round(ach / peak, 4), "traffic": None,
-                    "kernel": kern + " -- every K-contiguous Dense GEMM of the step: forward QKV, out-proj, FFN1, FFN2 and "
-                              "their input gradients dX = dY.W^T-shadow; the remaining GEMMs are the K-strided dW = dY^T.X",
-                    "launches": len(fwd), "avg_launch_us": round(tsum / len(fwd) * 1e6, 2),
-                    "flops_per_launch": fsum / len(fwd)}
-            live = getattr(args, "traffic", None) if dtype == "bf16" else None
-            if isinstance(live, dict):
-                roof["traffic"] = live["bytes_per_launch"]
-                roof["traffic_measurement"] = live
-            elif isinstance(live, str):
-                roof["traffic_note"] = "no live number: " + live
-            tf = os.path.join(ROOT, "profiles", TRAFFIC_PROFILE)
-            if dtype == "bf16" and os.path.exists(tf) and args.config == "c3" and (B, S, L, H) == (64, 256, 12, 768):
-                # NOT measured in this run: HBM bytes per launch of this kernel family from separate
-                # rocprofv3 --pmc passes (FETCH_SIZE x2 gfx950 correction, WRITE_SIZE), tools/hbm_traffic.py
-                roof["traffic_stored_profile"] = {"bytes_per_launch": json.load(open(tf))["bytes_per_launch"],
-                                                  "source": f"profiles/{TRAFFIC_PROFILE} (separate rocprofv3 --pmc passes; not measured in this run)"}
-            allg = [(e0.elapsed_time(e1) * 1e-3, fl) for (_, fl, e0, e1) in rec]
-            roof["all_gemm_tflops"] = round(sum(f for _, f in allg) / sum(t for t, _ in allg) / 1e12, 2)
-            roof["all_gemm_ms_per_step"] = round(sum(t for t, _ in allg) * 1e3, 3)
+    if args.full:
+        rec = []
+        if rank == 0:
+            ops.GEMM_PROFILE = rec
+        enc = getattr(model, "query_encoder", model)
+        overlap = getattr(enc, "overlap_dw", False)
+        enc.overlap_dw = False
+        trainer.update_in_backward = False
+        one_step(warmup + steps)
+        torch.cuda.synchronize()
+        enc.overlap_dw = overlap
+        trainer.update_in_backward = True
+        ops.GEMM_PROFILE = None
+        if rank == 0:
+            fwd = [(e0.elapsed_time(e1) * 1e-3, fl) for (key, fl, e0, e1) in rec if key == "fwd"]
+            if fwd:
+                tsum, fsum = sum(t for t, _ in fwd), sum(f for _, f in fwd)
+                ach = fsum / tsum / 1e12
+                kern = ("gemm_pp_kernel<256 x 256 | 256 x 192, epilogue mode 0-3> (ping-pong; the ring kernels gemm_ring_kernel<bf16> / "
+                        "gemm_ring128_kernel where a launch would leave CUs idle)" if dtype == "bf16" else "gemm_kernel<f32, K-contig, K-contig> (exact-f32 MFMA 16x16x4)")
+                roof = {"bound": "mfma", "achieved": round(ach, 2), "peak": peak, "unit": "TFLOP/s",
+                        "frac": round(ach / peak, 4), "traffic": None,
+                        "kernel": kern + " -- every K-contiguous Dense GEMM of the step: forward QKV, out-proj, FFN1, FFN2 and "
+                                  "their input gradients dX = dY.W^T-shadow; the remaining GEMMs are the K-strided dW = dY^T.X",
+                        "launches": len(fwd), "avg_launch_us": round(tsum / len(fwd) * 1e6, 2),
+                        "flops_per_launch": fsum / len(fwd)}
+                live = getattr(args, "traffic", None) if dtype == "bf16" else None
+                if isinstance(live, dict):
+                    roof["traffic"] = live["bytes_per_launch"]
+                    roof["traffic_measurement"] = live
+                elif isinstance(live, str):
+                    roof["traffic_note"] = "no live number: " + live
+                tf = os.path.join(ROOT, "profiles", TRAFFIC_PROFILE)
+                if dtype == "bf16" and os.path.exists(tf) and args.config == "c3" and (B, S, L, H) == (64, 256, 12, 768):
+                    # NOT measured in this run: HBM bytes per launch of this kernel family from separate
+                    # rocprofv3 --pmc passes (FETCH_SIZE x2 gfx950 correction, WRITE_SIZE), tools/hbm_traffic.py
+                    roof["traffic_stored_profile"] = {"bytes_per_launch": json.load(open(tf))["bytes_per_launch"],
+                                                      "source": f"profiles/{TRAFFIC_PROFILE} (separate rocprofv3 --pmc passes; not measured in this run)"}
+                allg = [(e0.elapsed_time(e1) * 1e-3, fl) for (_, fl, e0, e1) in rec]
+                roof["all_gemm_tflops"] = round(sum(f for _, f in allg) / sum(t for t, _ in allg) / 1e12, 2)
+                roof["all_gemm_ms_per_step"] = round(sum(t for t, _ in allg) * 1e3, 3)
     sps = world * B * steps / elapsed
     fstep = f_step_per_sample(L, S, H) * (2.0 / 3.0 if args.kind == "ir" else 1.0)   # ir: two encoder FORWARD passes per pair
     out = {"value": round(sps, 2), "ms_per_step": round(elapsed / steps * 1e3, 3), "steps": steps, "warmup": warmup,
@@ -426,21 +432,22 @@ def run_leg(args, dtype, steps, warmup, ctx, world, rank, dump_dir=None):
         out["dp_tuning"] = tuned
     if world > 1:
         # what the exchange costs: (a) the tail behind backward that nothing overlapped (HIP events, mean over the timed
-        # steps, max over ranks); (b) the same steps with every rank training alone -- no exchange at all (the replicas
-        # diverge from here on: this is the last thing this leg's trainer does)
+        # steps, max over ranks); (b) with --full, the same steps with every rank training alone -- no exchange at all (the
+        # replicas diverge from here on: this is the last thing this leg's trainer does)
         ex = [e0.elapsed_time(e1) for e0, e1 in exposed]
         out["exposed_comm_ms"] = round(comm.max_over_ranks(sum(ex) / max(len(ex), 1)), 3)
-        trainer.use_horovod = False
-        n_nc = max(3, min(steps, 10))
-        one_step(0)
-        torch.cuda.synchronize()
-        comm.barrier()
-        t0 = time.perf_counter()
-        for k in range(n_nc):
-            one_step(1 + k)
-        torch.cuda.synchronize()
-        out["ms_per_step_nocomm"] = round(comm.max_over_ranks(time.perf_counter() - t0) / n_nc * 1e3, 3)
-        comm.barrier()
+        if args.full:
+            trainer.use_horovod = False
+            n_nc = max(3, min(steps, 10))
+            one_step(0)
+            torch.cuda.synchronize()
+            comm.barrier()
+            t0 = time.perf_counter()
+            for k in range(n_nc):
+                one_step(1 + k)
+            torch.cuda.synchronize()
+            out["ms_per_step_nocomm"] = round(comm.max_over_ranks(time.perf_counter() - t0) / n_nc * 1e3, 3)
+            comm.barrier()
     del trainer, model, batches
     torch.cuda.empty_cache()
     return out
@@ -494,16 +501,21 @@ def main():
     ap.add_argument("--layers", type=int, default=12)
     ap.add_argument("--large", action="store_true", help="BERT-large instead of BERT-base")
     ap.add_argument("--dropout", type=float, default=0.1, help="hidden and attention dropout (HF BERT default 0.1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-f32-leg", action="store_true", help="skip the reference-precision (f32 engine) leg")
-    ap.add_argument("--no-loss100", action="store_true", help="skip the 2 x 100-step loss@step100 runs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline (one instrumented step, and the HBM-traffic passes), "
+                         "the f32 leg, loss@step100, the CPU baseline, and at N > 1 the steps without exchange")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-f32-leg", action="store_true", help="--full without the reference-precision (f32 engine) leg")
+    ap.add_argument("--no-loss100", action="store_true", help="--full without the 2 x 100-step loss@step100 runs")
     ap.add_argument("--graph", action="store_true", help="replay the step from a captured HIP graph (launch-bound shapes, one GPU)")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 --pmc child passes behind roofline.traffic")
+    ap.add_argument("--no-traffic", action="store_true", help="--full without the two rocprofv3 --pmc child passes behind roofline.traffic")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the loss and the updated parameters of the last timed step as DIR/<name>.npy")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        args.no_cpu_baseline = args.no_f32_leg = args.no_loss100 = args.no_traffic = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N`: nothing has touched torch or the GPU in this process
@@ -512,7 +524,7 @@ def main():
     if (args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_traffic and "POLUS_BENCH_CHILD" not in os.environ and
             args.config == "c3" and args.dtype == "bf16" and args.batch is None and args.seq is None and args.layers == 12 and not args.large and
             not (args.no_cpu_baseline or args.no_f32_leg or args.no_loss100) and "rocprof" not in os.environ.get("LD_PRELOAD", "")):
-        # (only the full default run -- what the driver executes -- pays for the two passes; the A/B and profile scripts shorten the run)
+        # (only a --full run of the headline with nothing switched off pays for the two passes)
         args.traffic = measure_hbm_traffic()          # before torch is imported: the children are the first to touch the GPU
 
     import torch
@@ -575,8 +587,9 @@ def main():
                        "grad_allreduce": (f"bucketed RCCL {'reduce-scatter (f32, 64 MB buckets) overlapped with backward -> AdamW on the owned slices -> all-gather of the parameters' if os.environ.get('POLUS_DP_MODE', 'allreduce') == 'rs' else 'all-reduce (f32, 64 MB buckets) fired inside backward, the fused AdamW of each bucket queued behind it'}; data plane: {comm._STATE['backend']}") if world > 1 else "none"},
             "step_mfma_frac": head["step_mfma_frac"], "step_tflops_per_gpu": head["step_tflops_per_gpu"],
             "loss_first": head["loss_first"], "loss_last": head["loss_last"],
-            "tf_reference": tf_reference_probe(),
         }
+        if args.full:
+            out["tf_reference"] = tf_reference_probe()
         if world > 1:
             out.update(rccl_ranks=plane["ranks_seen"], data_plane=plane["data_plane"],
                        exposed_comm_ms=head.get("exposed_comm_ms"), ms_per_step_nocomm=head.get("ms_per_step_nocomm"),
@@ -595,7 +608,7 @@ def main():
             out["loss_at_step100"] = l100
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(S, L, H, A, I)
-        elif world > 1:
+        elif world > 1 and args.full:
             # timed on rank 0 at N = 1 only (a host-core measurement beside N busy ranks would be noise); same schema key
             out["cpu_baseline"] = {"value": None, "note": "timed at N=1 only: see the cpu_baseline of the n_gpus=1 line of the same build"}
         print(json.dumps(out), flush=True)

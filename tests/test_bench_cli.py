@@ -1,5 +1,6 @@
-"""bench.py's command line: `--steps` is the number of timed steps, and `--dump-outputs DIR` writes what the last timed
-step computed (its loss and the updated parameters) as float .npy files within the 64 MB budget."""
+"""bench.py's command line: `--steps` is the number of timed steps, `--dump-outputs DIR` writes what the last timed
+step computed (its loss and the updated parameters) as float .npy files within the 64 MB budget, and a run without
+`--full` prints the headline figure alone."""
 import json
 import os
 import subprocess
@@ -9,7 +10,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--layers", "2", "--batch", "8", "--seq", "64", "--no-f32-leg", "--no-loss100", "--no-cpu-baseline", "--no-traffic"]
+SMALL = ["--layers", "2", "--batch", "8", "--seq", "64"]
 
 
 def test_bench_refuses_zero_timed_steps():
@@ -31,6 +32,10 @@ def test_bench_dump_outputs_holds_the_last_timed_step(tmp_path):
     assert len(lines) == 1, r.stdout
     line = json.loads(lines[0])
     assert line["steps"] == 3 and line["ms_per_step"] > 0
+    assert line["metric"] == "train samples/sec BioBERT-base NER seq256" and line["unit"] == "samples/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "bf16" and line["value"] > 0
+    # no --full: nothing beyond the headline was measured
+    assert not {"roofline", "f32", "loss_at_step100", "cpu_baseline", "tf_reference"} & set(line)
     assert sorted(os.listdir(out_dir)) == ["loss.npy", "params.npy"]
     arrays = {n: np.load(out_dir / n, allow_pickle=False) for n in os.listdir(out_dir)}
     assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())

@@ -122,15 +122,15 @@ def test_native_rccl_plane_world_1():
 
 
 def test_bench_bare_multi_gpu_launch_line(tmp_path):
-    """`python bench.py --gpus 2` with NO launcher around it: the parent spawns both ranks (before it touches torch or
-    the GPU), rank 0 prints the one JSON line, and the N > 1 line describes its own exchange: how many ranks the data
+    """`python bench.py --gpus 2 --full` with NO launcher around it: the parent spawns both ranks (before it touches torch
+    or the GPU), rank 0 prints the one JSON line, and the N > 1 line describes its own exchange: how many ranks the data
     plane really spanned, which plane, the exposed tail behind backward and the step time with no exchange at all.
     Two ranks share the box's one GPU, so the wire is gloo (RCCL refuses duplicate devices)."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(POLUS_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
-                        "--layers", "2", "--batch", "8", "--seq", "64", "--no-f32-leg", "--no-loss100", "--no-cpu-baseline"],
+                        "--layers", "2", "--batch", "8", "--seq", "64", "--full", "--no-f32-leg", "--no-loss100", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

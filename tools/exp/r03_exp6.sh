@@ -32,5 +32,5 @@ python3 tools/pp_bench.py --ab POLUS_GEMM_PERSIST=0,1,2 --rounds 5 --iters 10 > 
 python3 tools/pp_bench.py --ab POLUS_GEMM_PERSIST=0,1,2 --rounds 3 --iters 6 --cold > gpurun_out/r03_persist_cold.txt 2>&1
 cat gpurun_out/r03_persist_warm.txt gpurun_out/r03_persist_cold.txt
 for pv in 0 1 0 1; do
-  POLUS_GEMM_PERSIST=$pv python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-f32-leg --no-loss100 2>/dev/null | python3 -c "import json,sys;d=json.loads(sys.stdin.read());print('persist $pv', d['ms_per_step'], d['roofline']['avg_launch_us'], d['roofline']['frac'])"
+  POLUS_GEMM_PERSIST=$pv python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-f32-leg --no-loss100 2>/dev/null | python3 -c "import json,sys;d=json.loads(sys.stdin.read());print('persist $pv', d['ms_per_step'], d['roofline']['avg_launch_us'], d['roofline']['frac'])"
 done

@@ -10,6 +10,6 @@ for rep in 1 2 3; do for v in "1 0" "0 0" "1 1:232" "1 1:240" "0 1:240"; do set 
 done; done > $O/ab.txt
 cat $O/ab.txt
 unset POLUS_DW_STREAMK POLUS_DW_SK_CUS; export POLUS_UPDATE_AFTER_LN=1
-rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-f32-leg --no-loss100 > $O/trace.log 2>&1 || { tail -20 $O/trace.log; exit 1; }
+rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python3 bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-f32-leg --no-loss100 > $O/trace.log 2>&1 || { tail -20 $O/trace.log; exit 1; }
 python3 tools/timeline.py $O/trace > $O/timeline.txt
 rm -rf $O/trace

@@ -1,8 +1,8 @@
 """HBM bytes per launch of the K-contiguous bf16 Dense GEMM kernels from two rocprofv3 --pmc passes.
 
-    rocprofv3 --pmc FETCH_SIZE  --output-format csv -d gpurun_out/pmc_fetch -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline
-    rocprofv3 --pmc WRITE_SIZE  --output-format csv -d gpurun_out/pmc_write -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline
-    python tools/hbm_traffic.py gpurun_out/pmc_fetch gpurun_out/pmc_write profiles/r01_gemm_hbm_traffic.json
+    rocprofv3 --pmc FETCH_SIZE  --output-format csv -d pmc_fetch -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+    rocprofv3 --pmc WRITE_SIZE  --output-format csv -d pmc_write -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+    python tools/hbm_traffic.py pmc_fetch pmc_write profiles/r01_gemm_hbm_traffic.json
 
 Units and corrections as in /opt/skills/guides/MI355X_MICROARCH.md: both counters are in KiB;
 on gfx950 FETCH_SIZE reports half of the bytes of wide coalesced reads (doubled here), WRITE_SIZE is exact.

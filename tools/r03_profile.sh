@@ -4,9 +4,9 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r03
 rm -rf $O && mkdir -p $O
-B="bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-f32-leg --no-loss100"
-P="bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-f32-leg --no-loss100"
-python3 bench.py > $O/bench_line.json 2> $O/bench.err || exit 1
+B="bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-f32-leg --no-loss100"
+P="bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-f32-leg --no-loss100"
+python3 bench.py --full > $O/bench_line.json 2> $O/bench.err || exit 1
 export POLUS_OVERLAP_DW=0 POLUS_UPDATE_IN_BACKWARD=0
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $B > $O/stats.log 2>&1 || exit 1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python3 $P > $O/pmc_fetch.log 2>&1 || exit 1
@@ -25,8 +25,8 @@ python3 tools/hbm_traffic.py $O/pmc_fetch $O/pmc_write $O/gemm_hbm_traffic.json
 python3 tools/hbm_traffic.py $O/pmc_fetch_o0 $O/pmc_write $O/gemm_hbm_traffic_order0.json
 for f in $O/pmc_attn/*/*counter_collection.csv; do python3 tools/pmc_summary.py $f attn > $O/attention_pmc.txt; done
 for c in c2 c5 c5m16 c4; do
-  python3 bench.py --config $c > $O/bench_$c.json 2> $O/bench_$c.err || exit 1
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$c -- python3 bench.py --config $c --steps 5 --warmup 2 > $O/stats_$c.log 2>&1 || exit 1
+  python3 bench.py --full --config $c > $O/bench_$c.json 2> $O/bench_$c.err || exit 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$c -- python3 bench.py --full --config $c --steps 5 --warmup 2 > $O/stats_$c.log 2>&1 || exit 1
   python3 tools/kstats.py $O/stats_$c/*/*kernel_stats.csv 8 > $O/${c}_kernel_stats_summary.txt
 done
 cp $O/stats/*/*kernel_stats.csv $O/step_kernel_stats.csv
