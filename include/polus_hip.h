@@ -242,6 +242,32 @@ int polus_crf_viterbi(const float* potentials, const int32_t* lengths, const flo
                       int32_t* out_tags, int B, int S, int C,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- token-level late interaction (ColBERT MaxSim) for dense retrieval.  The reference types the document
+ * representation `# B, E or B, L, E` (polus/ir/training.py:51,63,98) and leaves the scoring of token vectors
+ * to the user's `compute_scores`; these are its forward and backward (maxsim.hip).
+ * Q [B,Lq,E] and D [N,Ld,E] in `dtype`, contiguous, 16-byte aligned; qmask int32 [B,Lq] and dmask int32 [N,Ld],
+ * NULL = all ones; a token is valid where its mask is non-zero.
+ *   score[b*lds + c]  = sum over valid i of max over valid j of <Q[b,i], D[c,j]>   (f32, lds >= N)
+ *   argmax[b][c][i]   = the winning j (int32 [B,N,Lq]); ties go to the lowest j as computed; -1 for an invalid
+ *                       query token or a document without a valid token (such a term adds 0).
+ * bf16: v_mfma_f32_16x16x32_bf16 with f32 accumulation; f32: exact-f32 v_mfma_f32_16x16x4_f32 in a fixed k order.
+ * Backward, from dscore f32 (row stride lds) and the forward's argmax, f32 sums rounded once to `dtype`:
+ *   dQ[b,i] = sum over c ascending of dscore[b,c] * D[c, argmax[b,c,i]]
+ *   dD[c,j] = sum over (b,i) ascending with argmax[b,c,i] == j of dscore[b,c] * Q[b,i]
+ * Every element of dQ and dD is written (0 where nothing lands); no atomics, bitwise reproducible; no workspace.
+ * Limits (refused before any launch): E a multiple of 32 in [32, 256]; 1 <= Lq, Ld <= 512; B, N <= 65535;
+ * B*N*Lq < 2^31. */
+int polus_maxsim_fwd(int dtype, const void* Q, const void* D, const int32_t* qmask, const int32_t* dmask,
+                     float* score, long lds, int32_t* argmax, int B, int N, int Lq, int Ld, int E, void* stream);
+int polus_maxsim_bwd(int dtype, const void* Q, const void* D, const float* dscore, long lds,
+                     const int32_t* argmax, void* dQ, void* dD, int B, int N, int Lq, int Ld, int E, void* stream);
+/* Row L2 normalisation, torch.nn.functional.normalize(x, dim=-1, eps) (ColBERT's cosine): x, y [rows,E] in
+ * `dtype` (E <= 256), rnorm f32 [rows].  Forward (f32 arithmetic): y = x / max(|x|, eps), rnorm = 1 / max(|x|, eps).
+ * Backward: dx = (dy - y <y, dy>) * rnorm where |x| > eps, dy / eps otherwise.  One wave per row. */
+int polus_l2norm_fwd(int dtype, const void* x, void* y, float* rnorm, int rows, int E, float eps, void* stream);
+int polus_l2norm_bwd(int dtype, const void* y, const float* rnorm, const void* dy, void* dx, int rows, int E,
+                     float eps, void* stream);
+
 /* ---- argmax over the last axis (PolusClassifier.inference, polus/models.py:148-150) */
 int polus_argmax(const float* x, long ldx, int32_t* out, int rows, int C, void* stream);
 

@@ -1,8 +1,12 @@
-"""Dual-encoder model for polus/ir/training.py: frozen BERT encoders (forward only, run in
+"""Dual-encoder models for polus/ir/training.py: frozen BERT encoders (forward only, run in
 `forward_without_grads`, :69-75) + trainable query/document projections (:82-83).
 
-`encode_*` return the [CLS] hidden state (TFBertSplited's pooler_output convention,
-polus/models.py:215-216).  One encoder may be shared by both towers."""
+`DualEncoder.encode_*` return the [CLS] hidden state (TFBertSplited's pooler_output convention,
+polus/models.py:215-216); `LateInteractionDualEncoder.encode_*` return every token's state with its mask
+(`TokenReps`, the `B, L, E` document representation of polus/ir/training.py:51,63,98).  One encoder may be
+shared by both towers."""
+from collections import namedtuple
+
 import torch
 
 from ..layers import Dense
@@ -44,3 +48,38 @@ class DualEncoder(PolusModel):
         self.qp.backward(dq, accumulate, need_dx=False)
         self.dp.backward(dd, accumulate, need_dx=False)
         self._notify(self.dp.variables() + self.qp.variables())
+
+
+class TokenReps(namedtuple("TokenReps", ["values", "mask"])):
+    """Token representations [n, L, E] paired with their int32 mask [n, L] (non-zero = a valid token)."""
+    __slots__ = ()
+
+
+class LateInteractionDualEncoder(DualEncoder):
+    """ColBERT-style dual encoder: `encode_*` return `TokenReps` of last_hidden_state with the input attention_mask,
+    and the two Dense(projection_dim) projections apply to every token row.  Score it with
+    polus_amd.ir.training.MaxSimScores."""
+
+    def __init__(self, query_encoder, document_encoder=None, projection_dim=128, compute_dtype="bf16",
+                 name="late_interaction_dual_encoder"):
+        super().__init__(query_encoder, document_encoder, projection_dim, compute_dtype, name)
+
+    def _tokens(self, encoder, x, training):
+        out = encoder(**x, training=False) if isinstance(x, dict) else encoder(x, training=False)
+        h = out.last_hidden_state.contiguous().clone()        # a fresh buffer (the encoder reuses its own)
+        mask = x.get("attention_mask") if isinstance(x, dict) else None
+        if mask is None:
+            mask = torch.ones(h.shape[:2], dtype=torch.int32, device=h.device)
+        return TokenReps(h, to_device(mask, torch.int32, h.device).reshape(h.shape[:2]).clone())
+
+    def encode_query(self, x, training=False):
+        return self._tokens(self.query_encoder, x, training)
+
+    def encode_document(self, x, training=False):
+        return self._tokens(self.document_encoder, x, training)
+
+    def query_projection(self, rep, training=False):
+        return TokenReps(self.qp.forward(to_device(rep.values, self.compute_dtype, self.arena.device), training), rep.mask)
+
+    def document_projection(self, rep, training=False):
+        return TokenReps(self.dp.forward(to_device(rep.values, self.compute_dtype, self.arena.device), training), rep.mask)

@@ -6,12 +6,16 @@ Because there is no tape, `compute_scores` and the loss must be objects that can
 backward: `InBatchDotScores` + `ContrastiveLoss` below are the stock pair.  With explicit negatives
 (:59-67, :94-107) the positive and the k negative documents of a batch go through
 `document_projection` as ONE [(k+1)B, H] call -- one stashed input, one backward -- and
-`compute_scores.backward` returns (dq, dd, dnegs)."""
+`compute_scores.backward` returns (dq, dd, dnegs).
+
+Token-level representations (`TokenReps`, from LateInteractionDualEncoder) take the same path: the documents
+are [(k+1)B, Ld, H] in one buffer, and `MaxSimScores` scores them ColBERT-style."""
 import torch
 
 from .. import ops
 from ..tensor import DeviceScalar, to_device
 from ..training import BaseTrainer
+from .models import TokenReps
 
 
 def _adjacent_rows(first, rest):
@@ -39,6 +43,8 @@ class EfficientDenseRetrievalTrainer(BaseTrainer):
         ids, am = negative_doc["input_ids"], negative_doc["attention_mask"]
         self.k_negatives = k = ids.shape[1]
         d = self.model.encode_document(positive_doc, training=True)
+        if isinstance(d, TokenReps):
+            return (q,) + self._token_documents(d, ids, am, k)
         B, H = d.shape
         reps = torch.empty((1 + k, B, H), dtype=d.dtype, device=d.device)
         reps[0].copy_(d)
@@ -46,8 +52,55 @@ class EfficientDenseRetrievalTrainer(BaseTrainer):
             reps[1 + i].copy_(self.model.encode_document({"input_ids": ids[:, i, :], "attention_mask": am[:, i, :]}, training=True))
         return q, reps[0], reps[1:]
 
+    def _token_documents(self, d, ids, am, k):
+        """Positive and negative token representations in one [(1+k), B, Ld, H] buffer (and one mask buffer)."""
+        B, Ld, H = d.values.shape
+        if ids.shape[-1] != Ld:
+            raise ValueError(f"negative documents are padded to {ids.shape[-1]} tokens, the positives to {Ld}: "
+                             "token-level scoring needs one padded length")
+        reps = torch.empty((1 + k, B, Ld, H), dtype=d.values.dtype, device=d.values.device)
+        masks = torch.empty((1 + k, B, Ld), dtype=torch.int32, device=d.values.device)
+        reps[0].copy_(d.values)
+        masks[0].copy_(d.mask)
+        for i in range(k):
+            n = self.model.encode_document({"input_ids": ids[:, i, :], "attention_mask": am[:, i, :]}, training=True)
+            reps[1 + i].copy_(n.values)
+            masks[1 + i].copy_(n.mask)
+        return TokenReps(reps[0], masks[0]), TokenReps(reps[1:], masks[1:])
+
+    def _token_forward_with_grads(self, question, positive_doc, negative_doc):
+        if self.post_process_logits is not None:
+            raise ValueError("post_process_logits does not apply to token representations: normalisation belongs "
+                             "to the scorer (MaxSimScores(normalize=True))")
+        q = self.model.query_projection(question, training=True)
+        if negative_doc is None:
+            self._n_neg = 0
+            return self.compute_scores(q, self.model.document_projection(positive_doc, training=True))
+        pv, nv = positive_doc.values, negative_doc.values
+        k, B, Ld = nv.shape[0], pv.shape[0], pv.shape[1]
+        if nv.shape[2] != Ld:
+            raise ValueError(f"negative documents are padded to {nv.shape[2]} tokens, the positives to {Ld}: "
+                             "token-level scoring needs one padded length")
+        self.k_negatives = self._n_neg = k
+        H = pv.shape[-1]
+        if _adjacent_rows(pv.reshape(-1, H), nv.reshape(-1, H)):
+            docs = torch.as_strided(pv, ((k + 1) * B, Ld, H), (Ld * H, H, 1))
+        else:
+            docs = torch.cat([pv, nv.reshape(k * B, Ld, H)], 0)
+        pm, nm = positive_doc.mask, negative_doc.mask
+        if _adjacent_rows(pm.reshape(-1, Ld), nm.reshape(-1, Ld)):
+            dmask = torch.as_strided(pm, ((k + 1) * B, Ld), (Ld, 1))
+        else:
+            dmask = torch.cat([pm, nm.reshape(k * B, Ld)], 0)
+        dall = self.model.document_projection(TokenReps(docs, dmask), training=True).values   # one stash, one backward
+        d = TokenReps(dall[:B], dmask[:B])
+        negs = [TokenReps(dall[B * (i + 1):B * (i + 2)], dmask[B * (i + 1):B * (i + 2)]) for i in range(k)]
+        return self.compute_scores(q, d, *negs)
+
     def forward_with_grads(self, question, positive_doc, negative_doc=None):
         """polus/ir/training.py:77-117."""
+        if isinstance(question, TokenReps):
+            return self._token_forward_with_grads(question, positive_doc, negative_doc)
         q = self.model.query_projection(question, training=True)
         if negative_doc is None:
             d = self.model.document_projection(positive_doc, training=True)
@@ -75,6 +128,11 @@ class EfficientDenseRetrievalTrainer(BaseTrainer):
         dpos, dneg = self.loss.backward(accumulate)
         out = self.compute_scores.backward(dpos, dneg)
         k = getattr(self, "_n_neg", 0)
+        if out[0].dim() == 3:                                       # token representations: [n, L, E] -> rows
+            E = out[0].shape[-1]
+            out = (out[0].reshape(-1, E), out[1].reshape(-1, E)) + tuple(
+                None if o is None else (o if torch.is_tensor(o) else torch.stack(list(o), 0)).reshape(-1, E)
+                for o in out[2:])
         if k == 0:
             dq, dd = out[0], out[1]
         else:
@@ -122,6 +180,69 @@ class InBatchDotScores:
         if self.k == 0:
             return dq, ddocs
         return dq, ddocs[:B], ddocs[B:].view(self.k, B, E)
+
+
+class MaxSimScores:
+    """Token-level late interaction (ColBERT MaxSim): score[b, c] = sum over the valid tokens i of query b of the
+    max over the valid tokens j of document c of <q_i, d_j>, with q and d rows L2-normalised first when
+    `normalize` (cosine, torch.nn.functional.normalize).  Same contract as InBatchDotScores: called with
+    TokenReps q [B, Lq, E], d [B, Ld, E] and negatives [B, Ld, E] each, it returns the column blocks (pos [B, B],
+    neg [B, kB] or None) of one f32 [B, (k+1)B] matrix; `backward` returns (dq, dd) or (dq, dd, dnegs [k, B, Ld, E]).
+    `argmax` (int32 [B, (k+1)B, Lq]) holds the winning document token of the last call, -1 where none."""
+
+    def __init__(self, normalize=True, eps=1e-12):
+        self.normalize = normalize
+        self.eps = eps
+
+    def _norm(self, x):
+        y = torch.empty_like(x)
+        r = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
+        ops.l2norm_fwd(x, y, r, self.eps)
+        return y, r
+
+    def __call__(self, q, d, *negs):
+        qv, qm = q.values.contiguous(), q.mask.contiguous()
+        B, Lq, E = qv.shape
+        k = len(negs)
+        Ld = d.values.shape[1]
+        if any(n.values.shape[1] != Ld for n in negs):
+            raise ValueError("token-level scoring needs the positives and negatives padded to one length")
+        if k:
+            parts = (d,) + negs
+            if all(_adjacent_rows(a.values.reshape(-1, E), b.values.reshape(-1, E)) for a, b in zip(parts[:-1], parts[1:])):
+                dv = torch.as_strided(d.values, ((k + 1) * B, Ld, E), (Ld * E, E, 1))
+            else:
+                dv = torch.cat([p.values.reshape(-1, Ld, E) for p in parts], 0)
+            if all(_adjacent_rows(a.mask.reshape(-1, Ld), b.mask.reshape(-1, Ld)) for a, b in zip(parts[:-1], parts[1:])):
+                dm = torch.as_strided(d.mask, ((k + 1) * B, Ld), (Ld, 1))
+            else:
+                dm = torch.cat([p.mask.reshape(-1, Ld) for p in parts], 0)
+        else:
+            dv, dm = d.values.contiguous(), d.mask.contiguous()
+        self.k, self.B = k, B
+        if self.normalize:
+            (self.q, self._rq), (self.docs, self._rd) = self._norm(qv), self._norm(dv)
+        else:
+            self.q, self.docs = qv, dv
+        N = dv.shape[0]
+        self.scores = torch.empty((B, N), dtype=torch.float32, device=qv.device)
+        self.argmax = torch.empty((B, N, Lq), dtype=torch.int32, device=qv.device)
+        ops.maxsim_fwd(self.q, self.docs, qm, dm, self.scores, self.argmax)
+        return (self.scores[:, :B], self.scores[:, B:]) if k else (self.scores, None)
+
+    def backward(self, dpos, dneg):
+        B, k = self.B, self.k
+        ds = dpos if k == 0 else _whole(dpos, dneg)
+        dq, dd = torch.empty_like(self.q), torch.empty_like(self.docs)
+        ops.maxsim_bwd(self.q, self.docs, ds, self.argmax, dq, dd)
+        if self.normalize:
+            gq, gd = torch.empty_like(dq), torch.empty_like(dd)
+            ops.l2norm_bwd(self.q, self._rq, dq, gq, self.eps)
+            ops.l2norm_bwd(self.docs, self._rd, dd, gd, self.eps)
+            dq, dd = gq, gd
+        if k == 0:
+            return dq, dd
+        return dq, dd[:B], dd[B:].view(k, B, *dd.shape[1:])
 
 
 def _whole(pos, neg):

@@ -302,6 +302,65 @@ def crf_viterbi(potentials, lengths, trans, out_tags):
           "polus_crf_viterbi")
 
 
+def _maxsim_mask(m, rows, L, name):
+    if m is None:
+        return None
+    assert m.dtype == torch.int32 and m.is_contiguous() and m.numel() == rows * L, f"{name}: int32 [{rows}, {L}] expected"
+    return m
+
+
+def maxsim_fwd(q, d, qmask, dmask, score, argmax):
+    """score[b, c] (f32, any row stride >= N) = sum over valid i of max over valid j of <q[b, i], d[c, j]>, and
+    argmax[b, c, i] (int32 [B, N, Lq]) the winning j; q [B, Lq, E], d [N, Ld, E] (include/polus_hip.h)."""
+    _req_cuda(q, d, qmask, dmask, score, argmax)
+    B, Lq, E = q.shape
+    N, Ld = d.shape[0], d.shape[1]
+    assert d.dim() == 3 and d.shape[2] == E and d.dtype == q.dtype and q.is_contiguous() and d.is_contiguous()
+    assert score.dtype == torch.float32 and score.dim() == 2 and score.shape[0] >= B and score.shape[1] >= N and score.stride(1) == 1
+    assert argmax.dtype == torch.int32 and argmax.is_contiguous() and argmax.numel() == B * N * Lq
+    check(_lib.load().polus_maxsim_fwd(dtype_code(q.dtype), ptr(q), ptr(d), ptr(_maxsim_mask(qmask, B, Lq, "qmask")),
+                                       ptr(_maxsim_mask(dmask, N, Ld, "dmask")), ptr(score), score.stride(0), ptr(argmax),
+                                       B, N, Lq, Ld, E, _st()), "polus_maxsim_fwd")
+
+
+def maxsim_bwd(q, d, dscore, argmax, dq, dd):
+    """dq [B, Lq, E] and dd [N, Ld, E] from dscore (f32 [B, N], row stride free) and the forward's argmax; every
+    element is written."""
+    _req_cuda(q, d, dscore, argmax, dq, dd)
+    B, Lq, E = q.shape
+    N, Ld = d.shape[0], d.shape[1]
+    assert d.dim() == 3 and d.shape[2] == E and d.dtype == q.dtype and q.is_contiguous() and d.is_contiguous()
+    assert dscore.dtype == torch.float32 and dscore.shape[0] >= B and dscore.shape[1] >= N and dscore.stride(1) == 1
+    assert argmax.dtype == torch.int32 and argmax.is_contiguous() and argmax.numel() == B * N * Lq
+    assert dq.shape == q.shape and dd.shape == d.shape and dq.dtype == q.dtype and dd.dtype == d.dtype
+    assert dq.is_contiguous() and dd.is_contiguous()
+    check(_lib.load().polus_maxsim_bwd(dtype_code(q.dtype), ptr(q), ptr(d), ptr(dscore), dscore.stride(0), ptr(argmax),
+                                       ptr(dq), ptr(dd), B, N, Lq, Ld, E, _st()), "polus_maxsim_bwd")
+
+
+def l2norm_fwd(x, y, rnorm, eps=1e-12):
+    """y = x / max(|x|, eps) over the last axis, rnorm (f32, one per row) = 1 / max(|x|, eps)."""
+    _req_cuda(x, y, rnorm)
+    E = x.shape[-1]
+    rows = x.numel() // E
+    assert x.is_contiguous() and y.is_contiguous() and y.shape == x.shape and y.dtype == x.dtype
+    assert rnorm.dtype == torch.float32 and rnorm.numel() == rows and rnorm.is_contiguous()
+    check(_lib.load().polus_l2norm_fwd(dtype_code(x.dtype), ptr(x), ptr(y), ptr(rnorm), rows, E, float(eps), _st()),
+          "polus_l2norm_fwd")
+
+
+def l2norm_bwd(y, rnorm, dy, dx, eps=1e-12):
+    """dx = (dy - y <y, dy>) * rnorm where |x| > eps, dy / eps otherwise (y, rnorm: the forward's outputs)."""
+    _req_cuda(y, rnorm, dy, dx)
+    E = y.shape[-1]
+    rows = y.numel() // E
+    assert y.is_contiguous() and dy.is_contiguous() and dx.is_contiguous()
+    assert dy.shape == y.shape and dx.shape == y.shape and dy.dtype == y.dtype and dx.dtype == y.dtype
+    assert rnorm.dtype == torch.float32 and rnorm.numel() == rows
+    check(_lib.load().polus_l2norm_bwd(dtype_code(y.dtype), ptr(y), ptr(rnorm), ptr(dy), ptr(dx), rows, E, float(eps), _st()),
+          "polus_l2norm_bwd")
+
+
 def argmax(x, out, rows=None, C=None):
     lib = _lib.load()
     _req_cuda(x, out)
