@@ -1,6 +1,10 @@
-// MFMA GEMM for the Dense layers of the BERT step and their gradients (gfx950).
+// GEMM for the Dense layers of the BERT step and their gradients (gfx950).  This file holds
+//   - the general MFMA kernel (128 x 128 tile, f32 / bf16, any layout and alignment) and the split-K reduce kernels;
+//   - the host side of every Dense GEMM: polus_gemm / polus_gemm_dropout, whose choice among this kernel and the ones of
+//     gemm_ring.hip / gemm_pp.hip is gemm_route(), and polus_dense_bwd_params(_grouped), whose workspace layout is
+//     grouped_dw_plan() (kernels in gemm_ring.hip / gemm_ppks.hip).
 //
-// One 256-thread workgroup (4 waves, 2x2) computes a 128x128 tile of C; each wave owns
+// The general kernel: one 256-thread workgroup (4 waves, 2x2) computes a 128x128 tile of C; each wave owns
 // 64x64 = 4x4 MFMA 16x16 tiles (64 accumulator registers).  A K-step is 128 bytes of K per
 // row (64 bf16 / 32 f32).  Operands are staged HBM -> registers -> LDS (double-buffered,
 // one barrier per K-step, the next tile's global loads in flight under the MFMAs).
@@ -285,12 +289,14 @@ extern "C" size_t polus_gemm_workspace_bytes(int M, int N, int split_k) {
     return (size_t)split_k * (size_t)M * (size_t)N * sizeof(float);
 }
 
-// Epilogue class of a bf16-C launch for the kernels with compile-time epilogues (gemm_pp.hip, the 128 x 128 ring tile):
+// ---- Which kernel a polus_gemm call runs: gemm_route below is the whole decision; the three heuristics it consults come first.
+
+// Epilogue class of an unsplit launch for the kernels with compile-time epilogues (gemm_pp.hip, the ring tiles):
 // 0 = alpha / bias, 1 = activation forward (+ pre-activation to aux), 2 = residual (+ dropout), 3 = activation backward
-// (aux read); -1 = a combination they are not built for (the caller stays on the run-time epilogue of the ring kernel).
-int polus_gemm_epi_mode(const GemmArgs& a, int c_is_f32, int drop) {
-    if (c_is_f32 || (a.flags & POLUS_GEMM_ACCUM_C) || a.partial) return -1;
-    const bool fwd = a.flags & POLUS_GEMM_ACT_FWD, bwd = a.flags & POLUS_GEMM_ACT_BWD;
+// (aux read); -1 = a combination they are not built for (the launch stays on the run-time epilogue of the ring kernel).
+static int epi_mode(const GemmArgs& a, bool c_is_f32) {
+    if (c_is_f32 || (a.flags & POLUS_GEMM_ACCUM_C)) return -1;
+    const bool fwd = a.flags & POLUS_GEMM_ACT_FWD, bwd = a.flags & POLUS_GEMM_ACT_BWD, drop = a.flags & POLUS_GEMM_DROPOUT;
     if (fwd && (bwd || a.resid || drop)) return -1;
     if (bwd && (a.resid || drop || !a.aux)) return -1;
     if (drop && !a.resid) return -1;
@@ -299,6 +305,11 @@ int polus_gemm_epi_mode(const GemmArgs& a, int c_is_f32, int drop) {
     if (a.resid) return 2;
     return 0;
 }
+
+// CUs a ping-pong launch can count on: all of them, minus what a concurrent gradient exchange holds (POLUS_GEMM_RESERVE_CUS: a
+// ping-pong workgroup fills a CU's registers and LDS, so a CU running an RCCL channel kernel takes no tile, and a
+// 256-tile launch that finds 240 free CUs runs two rounds)
+static int pp_cus() { return max(32, polus_num_cus() - polus_reserved_cus()); }
 
 // The ping-pong kernel (gemm_pp.hip, one 8-wave workgroup per CU, 256 x 256 or 256 x 192 tile): more
 // FLOP per byte filled into LDS than the ring kernel's 256 x 128, which is what bounds these GEMMs.
@@ -309,10 +320,7 @@ static int pp_tile(int M, int N, int K, int mode, bool vec16) {
     const int sel = polus_cfg().gemm_pp;
     if (sel < 0 || mode < 0 || K % 64 != 0 || M < 256 || N < 192 || !vec16) return 0;
     if (sel == 256 || sel == 192) return sel;
-    // CUs a launch can count on: all of them, minus what a concurrent gradient exchange holds (POLUS_GEMM_RESERVE_CUS: a
-    // ping-pong workgroup fills a CU's registers and LDS, so a CU running an RCCL channel kernel takes no tile, and a
-    // 256-tile launch that finds 240 free CUs runs two rounds)
-    const int ncu = max(32, polus_num_cus() - polus_reserved_cus());
+    const int ncu = pp_cus();
     const long tm = (M + 255) / 256;
     double best = 0.0; int best_tn = 0;
     for (int tn : {256, 192}) {
@@ -323,6 +331,20 @@ static int pp_tile(int M, int N, int K, int mode, bool vec16) {
         if (score > best) { best = score; best_tn = tn; }
     }
     return best >= 0.70 ? best_tn : 0;
+}
+
+// Persistent form of a ping-pong launch with several rounds of tiles: one workgroup per CU walks them, the next tile's operand
+// prologue under the epilogue.  Returns the number of workgroups, 0 = one workgroup per tile.
+// measured (tools/pp_bench.py --ab POLUS_GEMM_PERSIST=0,1,2; bench.py --config c3 | c4 | c5): wins on the 256-wide launches --
+// the GELU ones of BERT-base (FFN1 forward, dU: -8 % from cold caches) and every multi-round launch of BERT-large (+0.5 %
+// on the c4 step) -- and is neutral to slightly negative on the 192-wide bias-only QKV launch of BERT-base (three exact
+// rounds, an epilogue too short to hide anything; c5, 512 tiles of 256 x 192: 34.4 -> 34.8 ms/step); POLUS_GEMM_PERSIST=2
+// forces it on every multi-round launch
+static int pp_persist_cus(int M, int N, int tn) {
+    const int sel = polus_cfg().gemm_persist;
+    if (!sel || (tn != 256 && sel < 2)) return 0;
+    const int tiles = ((M + 255) / 256) * ((N + tn - 1) / tn);
+    return tiles > pp_cus() ? pp_cus() : 0;
 }
 
 // 128 x 128 ring tile instead of 256 x 128 (bf16 C, both operands K-contiguous, a compile-time epilogue mode).
@@ -362,12 +384,188 @@ extern "C" int polus_gemm_auto_split(int M, int N, int K) {
     return s < 2 ? 1 : (int)s;
 }
 
+enum GemmKernel {
+    GEMM_V1,         // gemm.hip, 128 x 128, any dtype / layout / alignment
+    GEMM_RING,       // gemm_ring.hip, 256 x 128 (compile-time epilogue when mode >= 0)
+    GEMM_RING128,    // gemm_ring.hip, 128 x 128
+    GEMM_RING_DROP,  // gemm_ring.hip, 256 x 128 with the dropout epilogue
+    GEMM_PP,         // gemm_pp.hip, 256 x tn, one workgroup per tile
+    GEMM_PP_PERSIST  // gemm_pp.hip, 256 x tn, persist_cus workgroups walk the tiles
+};
+enum GemmReduce { REDUCE_NONE, REDUCE_PLAIN /* splitk_reduce_kernel */, REDUCE_EPI /* splitk_reduce_epi_kernel */ };
+struct GemmRoute {
+    GemmKernel kernel;
+    int tn;           // tile width
+    int mode;         // compile-time epilogue class (epi_mode), -1 = run-time epilogue
+    int drop;
+    int splits;       // K slices launched; > 1: the kernel writes f32 slabs and `reduce` follows
+    GemmReduce reduce;
+    int persist_cus;  // GEMM_PP_PERSIST: workgroups
+};
+
+// Everything polus_gemm / polus_gemm_dropout decide about a validated call.  `a` is filled but for k_per_split and partial,
+// which follow from the route; splits is the number of non-empty K slices the caller's split_k gives.
+static GemmRoute gemm_route(const GemmArgs& a, int dtype, bool c_is_f32, bool a_ks, bool b_ks, int splits) {
+    const bool both_kc = !a_ks && !b_ks;
+    const int drop = (a.flags & POLUS_GEMM_DROPOUT) != 0;
+    const bool epi = a.resid || a.aux || (a.flags & (POLUS_GEMM_ACT_FWD | POLUS_GEMM_ACT_BWD | POLUS_GEMM_DROPOUT));
+    // the direct-to-LDS kernels: bf16, whole 16-byte chunks, at least one 256 x 128 tile
+    const bool fast = dtype == POLUS_BF16 && a.a_vec && a.b_vec && a.M >= 256 && a.N >= 128 && !polus_cfg().gemm_v1;
+    GemmRoute r = {fast ? GEMM_RING : GEMM_V1, 128, -1, drop, splits, REDUCE_NONE, 0};
+    if (splits > 1) {
+        if (!epi) r.reduce = REDUCE_PLAIN;
+        else if (fast && both_kc && !c_is_f32) r.reduce = REDUCE_EPI;
+        else r.splits = 1;           // small or unaligned problem: one slice, in-kernel epilogue
+    }
+    if (!fast || r.splits > 1) return r;
+    r.mode = both_kc ? epi_mode(a, c_is_f32) : -1;     // with dropout: 2 or -1
+    if (const int tn = pp_tile(a.M, a.N, a.K, r.mode, a.epi_vec16)) {
+        r.tn = tn;
+        r.persist_cus = pp_persist_cus(a.M, a.N, tn);
+        r.kernel = r.persist_cus ? GEMM_PP_PERSIST : GEMM_PP;
+    } else if (use_ring128(a.M, a.N, a.K, r.mode)) {
+        r.kernel = GEMM_RING128;
+    } else if (drop) {
+        r.kernel = GEMM_RING_DROP;
+    }
+    return r;
+}
+
+// The slab launch of a split ring GEMM: plain f32 stores of every K slice, the epilogue is left to the reduce kernel.
+static GemmArgs slab_args(const GemmArgs& a) {
+    GemmArgs s = a;
+    s.C = a.partial; s.ldc = a.N; s.c_split_stride = (long)a.M * a.N; s.partial = nullptr;
+    s.alpha = 1.0f; s.bias = nullptr; s.flags = 0; s.resid = nullptr; s.aux = nullptr;
+    s.epi_vec = (a.N % 4 == 0); s.epi_vec16 = (a.N % 4 == 0) && polus_aligned16(a.partial);
+    return s;
+}
+
+static int launch_splitk_reduce_epi(const GemmArgs& a, int splits, hipStream_t st) {
+    GemmArgs e = a;
+    e.partial = nullptr;
+    const long quads = (long)a.M * ((a.N + 3) / 4);
+    const int blocks = (int)((quads + 255) / 256);
+    if (a.flags & POLUS_GEMM_DROPOUT)
+        hipLaunchKernelGGL(splitk_reduce_epi_kernel<true>, dim3(blocks), dim3(256), 0, st, e, a.partial, splits);
+    else
+        hipLaunchKernelGGL(splitk_reduce_epi_kernel<false>, dim3(blocks), dim3(256), 0, st, e, a.partial, splits);
+    POLUS_CHECK_LAUNCH("polus_gemm(splitk_reduce_epi)");
+    return POLUS_OK;
+}
+
+static int launch_v1(int dtype, int c_dtype, int a_layout, int b_layout, const GemmArgs& a, int drop, int splits, hipStream_t st) {
+    const dim3 grid(((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN), 1, splits);
+    if (drop) {                       // forward Dense only: K-contiguous operands, C in the compute dtype
+        const bool v = a.a_vec && a.b_vec;
+        if (dtype == POLUS_BF16) return v ? launch_v<bf16_t, false, false, bf16_t, true, true>(a, grid, st) : launch_v<bf16_t, false, false, bf16_t, false, true>(a, grid, st);
+        return v ? launch_v<float, false, false, float, true, true>(a, grid, st) : launch_v<float, false, false, float, false, true>(a, grid, st);
+    }
+    if (dtype == POLUS_BF16)
+        return c_dtype == POLUS_F32 ? dispatch_layout<bf16_t, float>(a_layout, b_layout, a, grid, st)
+                                    : dispatch_layout<bf16_t, bf16_t>(a_layout, b_layout, a, grid, st);
+    return dispatch_layout<float, float>(a_layout, b_layout, a, grid, st);
+}
+
+// C (+)= alpha * sum of the f32 slabs (+ bias), in slice order
+static int launch_splitk_reduce(int c_dtype, const float* slabs, int splits, int M, int N, void* C, long ldc, float alpha,
+                                const float* bias, int accumulate, const char* what, hipStream_t st) {
+    const int blocks = (int)(((long)M * N + 255) / 256);
+    if (c_dtype == POLUS_F32)
+        hipLaunchKernelGGL(splitk_reduce_kernel<float>, dim3(blocks), dim3(256), 0, st, slabs, splits, M, N, static_cast<float*>(C), ldc, alpha, bias, accumulate);
+    else
+        hipLaunchKernelGGL(splitk_reduce_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, slabs, splits, M, N, static_cast<bf16_t*>(C), ldc, alpha, bias, accumulate);
+    POLUS_CHECK_LAUNCH(what);
+    return POLUS_OK;
+}
+
 static int gemm_impl(int dtype, int a_layout, int b_layout, int c_dtype,
                      const void* A, long lda, const void* B, long ldb, void* C, long ldc,
                      int M, int N, int K, float alpha,
                      const float* bias, const void* resid, long ldr, void* aux, long ldaux,
                      int act, int flags, int split_k, void* workspace, size_t workspace_bytes,
-                     float drop_p, uint32_t seed, void* stream);
+                     float drop_p, uint32_t seed, void* stream) {
+    POLUS_REQUIRE(dtype == POLUS_F32 || dtype == POLUS_BF16, "polus_gemm: bad dtype %d", dtype);
+    POLUS_REQUIRE(c_dtype == POLUS_F32 || c_dtype == dtype, "polus_gemm: c_dtype must be f32 or dtype");
+    POLUS_REQUIRE(M > 0 && N > 0 && K > 0, "polus_gemm: empty problem M=%d N=%d K=%d", M, N, K);
+    POLUS_REQUIRE(A && B && C, "polus_gemm: null operand");
+    POLUS_REQUIRE((a_layout | 1) == 1 && (b_layout | 1) == 1, "polus_gemm: bad layout");
+    POLUS_REQUIRE(lda >= (a_layout == POLUS_K_CONTIG ? K : M), "polus_gemm: lda %ld too small", lda);
+    POLUS_REQUIRE(ldb >= (b_layout == POLUS_K_CONTIG ? K : N), "polus_gemm: ldb %ld too small", ldb);
+    POLUS_REQUIRE(ldc >= N, "polus_gemm: ldc %ld < N %d", ldc, N);
+    POLUS_REQUIRE(!resid || ldr >= N, "polus_gemm: ldr too small");
+    POLUS_REQUIRE(!((flags & POLUS_GEMM_ACT_BWD) && !aux), "polus_gemm: ACT_BWD needs aux");
+    POLUS_REQUIRE(!aux || ldaux >= N, "polus_gemm: ldaux too small");
+    if (split_k < 1) split_k = 1;
+    const size_t es = polus_dtype_size(dtype), ecs = polus_dtype_size(c_dtype);
+    const int bk = dtype == POLUS_BF16 ? 64 : 32;
+    const int nkt = (K + bk - 1) / bk;
+    if (split_k > nkt) split_k = nkt;
+    const bool both_kc = a_layout == POLUS_K_CONTIG && b_layout == POLUS_K_CONTIG;
+    if (split_k > 1) {
+        const bool epi = resid || aux || (flags & (POLUS_GEMM_ACT_FWD | POLUS_GEMM_ACT_BWD | POLUS_GEMM_DROPOUT));
+        POLUS_REQUIRE(!epi || (dtype == POLUS_BF16 && c_dtype == POLUS_BF16 && both_kc && !(flags & POLUS_GEMM_ACCUM_C)),
+                      "polus_gemm: split_k with a residual / activation / dropout epilogue needs bf16 K-contiguous operands and a bf16 C");
+        if (!workspace || workspace_bytes < polus_gemm_workspace_bytes(M, N, split_k)) {
+            polus_set_error("polus_gemm: workspace %zu < %zu", workspace_bytes, polus_gemm_workspace_bytes(M, N, split_k));
+            return POLUS_ERR_WORKSPACE;
+        }
+    }
+    // forward Dense only: K-contiguous operands, C in the compute dtype
+    POLUS_REQUIRE(!(flags & POLUS_GEMM_DROPOUT) || (both_kc && c_dtype == dtype), "polus_gemm_dropout: needs K-contiguous operands and c_dtype == dtype");
+    GemmArgs a = {};
+    a.A = A; a.B = B; a.C = C; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
+    a.M = M; a.N = N; a.K = K; a.alpha = alpha;
+    a.bias = bias; a.resid = resid; a.ldr = ldr; a.aux = aux; a.ldaux = ldaux;
+    a.act = act; a.flags = flags;
+    a.drop_inv = 1.0f / (1.0f - drop_p); a.drop_thresh = polus_drop_thresh(drop_p); a.drop_seed = seed;
+    a.dyn = polus_dyn();
+    const int epc = (int)(16 / es);
+    // whole-chunk validity: the contiguous extent of each operand must be a multiple of a chunk
+    a.a_vec = polus_aligned16(A) && ((lda * es) % 16 == 0) && ((a_layout == POLUS_K_CONTIG ? K : M) % epc == 0);
+    a.b_vec = polus_aligned16(B) && ((ldb * es) % 16 == 0) && ((b_layout == POLUS_K_CONTIG ? K : N) % epc == 0);
+    // 4-wide epilogue accesses: every touched row start must be 4-element aligned
+    bool ev = (((uintptr_t)C) % (4 * ecs) == 0) && (ldc % 4 == 0);
+    if (bias) ev = ev && (((uintptr_t)bias) % 16 == 0);
+    if (resid) ev = ev && (((uintptr_t)resid) % (4 * es) == 0) && (ldr % 4 == 0);
+    if (aux) ev = ev && (((uintptr_t)aux) % (4 * es) == 0) && (ldaux % 4 == 0);
+    a.epi_vec = ev;
+    bool ev16 = (((uintptr_t)C) % 16 == 0) && ((ldc * ecs) % 16 == 0);
+    if (bias) ev16 = ev16 && (((uintptr_t)bias) % 16 == 0);
+    if (resid) ev16 = ev16 && (((uintptr_t)resid) % 16 == 0) && ((ldr * es) % 16 == 0);
+    if (aux) ev16 = ev16 && (((uintptr_t)aux) % 16 == 0) && ((ldaux * es) % 16 == 0);
+    a.epi_vec16 = ev16 && dtype == POLUS_BF16;
+    a.order = polus_cfg().gemm_order;
+
+    const int kt_per_split = (nkt + split_k - 1) / split_k;
+    const bool c_is_f32 = c_dtype == POLUS_F32;
+    const int a_ks = a_layout == POLUS_K_STRIDED, b_ks = b_layout == POLUS_K_STRIDED;
+    const GemmRoute r = gemm_route(a, dtype, c_is_f32, a_ks, b_ks, (nkt + kt_per_split - 1) / kt_per_split);
+    if (r.splits > 1) { a.k_per_split = kt_per_split * bk; a.partial = static_cast<float*>(workspace); }
+    else a.k_per_split = r.kernel == GEMM_V1 ? nkt * bk : ((K + 31) / 32) * 32;
+
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int rc = POLUS_ERR_INVALID;
+    switch (r.kernel) {
+        case GEMM_V1: rc = launch_v1(dtype, c_dtype, a_layout, b_layout, a, r.drop, r.splits, st); break;
+        case GEMM_RING:
+            rc = r.splits > 1 ? polus_launch_gemm_ring(slab_args(a), 1, a_ks, b_ks, r.splits, -1, st)
+                              : polus_launch_gemm_ring(a, c_is_f32, a_ks, b_ks, 1, r.mode, st);
+            break;
+        case GEMM_RING128: rc = polus_launch_gemm_ring128(a, r.mode, r.drop, st); break;
+        case GEMM_RING_DROP: rc = polus_launch_gemm_ring_dropout(a, r.mode, st); break;
+        case GEMM_PP:
+        case GEMM_PP_PERSIST: rc = polus_launch_gemm_pp(a, r.mode, r.drop, r.tn, r.persist_cus, st); break;
+    }
+    if (rc != POLUS_OK) return rc;
+    switch (r.reduce) {
+        case REDUCE_NONE: break;
+        case REDUCE_EPI: return launch_splitk_reduce_epi(a, r.splits, st);
+        case REDUCE_PLAIN:
+            return launch_splitk_reduce(c_dtype, a.partial, r.splits, M, N, C, ldc, alpha, bias, (flags & POLUS_GEMM_ACCUM_C) ? 1 : 0,
+                                        "polus_gemm(splitk_reduce)", st);
+    }
+    return POLUS_OK;
+}
 
 extern "C" int polus_gemm(int dtype, int a_layout, int b_layout, int c_dtype,
                           const void* A, long lda, const void* B, long ldb, void* C, long ldc,
@@ -393,157 +591,6 @@ extern "C" int polus_gemm_dropout(int dtype, int a_layout, int b_layout, int c_d
                      aux, ldaux, act, flags, split_k, workspace, workspace_bytes, drop_p, seed, stream);
 }
 
-static int gemm_impl(int dtype, int a_layout, int b_layout, int c_dtype,
-                     const void* A, long lda, const void* B, long ldb, void* C, long ldc,
-                     int M, int N, int K, float alpha,
-                     const float* bias, const void* resid, long ldr, void* aux, long ldaux,
-                     int act, int flags, int split_k, void* workspace, size_t workspace_bytes,
-                     float drop_p, uint32_t seed, void* stream) {
-    POLUS_REQUIRE(dtype == POLUS_F32 || dtype == POLUS_BF16, "polus_gemm: bad dtype %d", dtype);
-    POLUS_REQUIRE(c_dtype == POLUS_F32 || c_dtype == dtype, "polus_gemm: c_dtype must be f32 or dtype");
-    POLUS_REQUIRE(M > 0 && N > 0 && K > 0, "polus_gemm: empty problem M=%d N=%d K=%d", M, N, K);
-    POLUS_REQUIRE(A && B && C, "polus_gemm: null operand");
-    POLUS_REQUIRE((a_layout | 1) == 1 && (b_layout | 1) == 1, "polus_gemm: bad layout");
-    POLUS_REQUIRE(lda >= (a_layout == POLUS_K_CONTIG ? K : M), "polus_gemm: lda %ld too small", lda);
-    POLUS_REQUIRE(ldb >= (b_layout == POLUS_K_CONTIG ? K : N), "polus_gemm: ldb %ld too small", ldb);
-    POLUS_REQUIRE(ldc >= N, "polus_gemm: ldc %ld < N %d", ldc, N);
-    POLUS_REQUIRE(!resid || ldr >= N, "polus_gemm: ldr too small");
-    POLUS_REQUIRE(!((flags & POLUS_GEMM_ACT_BWD) && !aux), "polus_gemm: ACT_BWD needs aux");
-    POLUS_REQUIRE(!aux || ldaux >= N, "polus_gemm: ldaux too small");
-    if (split_k < 1) split_k = 1;
-    const size_t es = polus_dtype_size(dtype), ecs = polus_dtype_size(c_dtype);
-    const int bk = dtype == POLUS_BF16 ? 64 : 32;
-    int nkt = (K + bk - 1) / bk;
-    if (split_k > nkt) split_k = nkt;
-    if (split_k > 1) {
-        const bool epi = resid || aux || (flags & (POLUS_GEMM_ACT_FWD | POLUS_GEMM_ACT_BWD | POLUS_GEMM_DROPOUT));
-        POLUS_REQUIRE(!epi || (dtype == POLUS_BF16 && c_dtype == POLUS_BF16 && a_layout == POLUS_K_CONTIG && b_layout == POLUS_K_CONTIG &&
-                               !(flags & POLUS_GEMM_ACCUM_C)),
-                      "polus_gemm: split_k with a residual / activation / dropout epilogue needs bf16 K-contiguous operands and a bf16 C");
-        if (!workspace || workspace_bytes < polus_gemm_workspace_bytes(M, N, split_k)) {
-            polus_set_error("polus_gemm: workspace %zu < %zu", workspace_bytes, polus_gemm_workspace_bytes(M, N, split_k));
-            return POLUS_ERR_WORKSPACE;
-        }
-    }
-    GemmArgs a;
-    a.A = A; a.B = B; a.C = C; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
-    a.M = M; a.N = N; a.K = K; a.alpha = alpha;
-    a.k_per_split = ((nkt + split_k - 1) / split_k) * bk;
-    a.bias = bias; a.resid = resid; a.ldr = ldr; a.aux = aux; a.ldaux = ldaux;
-    a.act = act; a.flags = flags;
-    a.drop_inv = 1.0f / (1.0f - drop_p); a.drop_thresh = polus_drop_thresh(drop_p); a.drop_seed = seed;
-    a.dyn = polus_dyn();
-    a.partial = split_k > 1 ? static_cast<float*>(workspace) : nullptr;
-    const int epc = (int)(16 / es);
-    // whole-chunk validity: the contiguous extent of each operand must be a multiple of a chunk
-    a.a_vec = polus_aligned16(A) && ((lda * es) % 16 == 0) && ((a_layout == POLUS_K_CONTIG ? K : M) % epc == 0);
-    a.b_vec = polus_aligned16(B) && ((ldb * es) % 16 == 0) && ((b_layout == POLUS_K_CONTIG ? K : N) % epc == 0);
-    // 4-wide epilogue accesses: every touched row start must be 4-element aligned
-    bool ev = (((uintptr_t)C) % (4 * ecs) == 0) && (ldc % 4 == 0);
-    if (bias) ev = ev && (((uintptr_t)bias) % 16 == 0);
-    if (resid) ev = ev && (((uintptr_t)resid) % (4 * es) == 0) && (ldr % 4 == 0);
-    if (aux) ev = ev && (((uintptr_t)aux) % (4 * es) == 0) && (ldaux % 4 == 0);
-    a.epi_vec = ev;
-    bool ev16 = (((uintptr_t)C) % 16 == 0) && ((ldc * ecs) % 16 == 0);
-    if (bias) ev16 = ev16 && (((uintptr_t)bias) % 16 == 0);
-    if (resid) ev16 = ev16 && (((uintptr_t)resid) % 16 == 0) && ((ldr * es) % 16 == 0);
-    if (aux) ev16 = ev16 && (((uintptr_t)aux) % 16 == 0) && ((ldaux * es) % 16 == 0);
-    a.epi_vec16 = ev16 && dtype == POLUS_BF16;
-    a.order = polus_cfg().gemm_order;
-    a.persist = polus_cfg().gemm_persist ? max(32, polus_num_cus() - polus_reserved_cus()) : 0;
-    a.persist_all = polus_cfg().gemm_persist >= 2;
-    const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    int splits_eff = (nkt + (a.k_per_split / bk) - 1) / (a.k_per_split / bk);
-    dim3 grid(tiles, 1, split_k > 1 ? splits_eff : 1);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    int rc = POLUS_OK;
-    a.c_split_stride = 0;
-    a.colsum_a = nullptr;
-    const bool both_kc = a_layout == POLUS_K_CONTIG && b_layout == POLUS_K_CONTIG;
-    const bool fast_bf16 = dtype == POLUS_BF16 && a.a_vec && a.b_vec && M >= 256 && N >= 128 && !polus_cfg().gemm_v1;
-    const bool epi_split = split_k > 1 && (resid || aux || (flags & (POLUS_GEMM_ACT_FWD | POLUS_GEMM_ACT_BWD | POLUS_GEMM_DROPOUT)));
-    if (epi_split && fast_bf16 && both_kc && c_dtype == POLUS_BF16) {
-        GemmArgs s = a;              // slabs: plain f32 stores of every K slice ...
-        s.C = a.partial; s.ldc = N; s.c_split_stride = (long)M * N; s.partial = nullptr;
-        s.alpha = 1.0f; s.bias = nullptr; s.flags = 0; s.resid = nullptr; s.aux = nullptr;
-        s.epi_vec = (N % 4 == 0); s.epi_vec16 = (N % 4 == 0) && polus_aligned16(a.partial);
-        rc = polus_launch_gemm_ring(s, 1, 0, 0, splits_eff, st);
-        if (rc != POLUS_OK) return rc;
-        GemmArgs e = a;              // ... then the whole epilogue on their sum
-        e.partial = nullptr;
-        const long quads = (long)M * ((N + 3) / 4);
-        const int blocks = (int)((quads + 255) / 256);
-        if (flags & POLUS_GEMM_DROPOUT)
-            hipLaunchKernelGGL(splitk_reduce_epi_kernel<true>, dim3(blocks), dim3(256), 0, st, e, a.partial, splits_eff);
-        else
-            hipLaunchKernelGGL(splitk_reduce_epi_kernel<false>, dim3(blocks), dim3(256), 0, st, e, a.partial, splits_eff);
-        POLUS_CHECK_LAUNCH("polus_gemm(splitk_reduce_epi)");
-        return POLUS_OK;
-    }
-    if (epi_split) {                 // not on the fast path (small or unaligned problem): one slice, in-kernel epilogue
-        split_k = 1; a.partial = nullptr;
-        a.k_per_split = nkt * bk;
-        grid = dim3(tiles, 1, 1);
-        splits_eff = 1;
-    }
-    if (flags & POLUS_GEMM_DROPOUT) {
-        // forward Dense only: K-contiguous operands, C in the compute dtype
-        POLUS_REQUIRE(both_kc && c_dtype == dtype, "polus_gemm_dropout: needs K-contiguous operands and c_dtype == dtype");
-        if (dtype == POLUS_BF16 && a.a_vec && a.b_vec && M >= 256 && N >= 128 && !polus_cfg().gemm_v1) {
-            a.k_per_split = ((K + 31) / 32) * 32;
-            if (const int tn = pp_tile(M, N, K, polus_gemm_epi_mode(a, 0, 1), a.epi_vec16))
-                return polus_launch_gemm_pp(a, polus_gemm_epi_mode(a, 0, 1), 1, tn, st);
-            if (use_ring128(M, N, K, polus_gemm_epi_mode(a, 0, 1))) return polus_launch_gemm_ring128(a, polus_gemm_epi_mode(a, 0, 1), 1, st);
-            return polus_launch_gemm_ring_dropout(a, st);
-        }
-        const bool v = a.a_vec && a.b_vec;
-        if (dtype == POLUS_BF16) return v ? launch_v<bf16_t, false, false, bf16_t, true, true>(a, grid, st) : launch_v<bf16_t, false, false, bf16_t, false, true>(a, grid, st);
-        return v ? launch_v<float, false, false, float, true, true>(a, grid, st) : launch_v<float, false, false, float, false, true>(a, grid, st);
-    }
-    const int a_ks = a_layout == POLUS_K_STRIDED, b_ks = b_layout == POLUS_K_STRIDED;
-    if (dtype == POLUS_BF16 && a.a_vec && a.b_vec && M >= 256 && N >= 128 && !polus_cfg().gemm_v1) {
-        if (split_k <= 1) {
-            a.k_per_split = ((K + 31) / 32) * 32;
-            if (both_kc) {
-                if (const int tn = pp_tile(M, N, K, polus_gemm_epi_mode(a, c_dtype == POLUS_F32, 0), a.epi_vec16))
-                    return polus_launch_gemm_pp(a, polus_gemm_epi_mode(a, c_dtype == POLUS_F32, 0), 0, tn, st);
-            }
-            if (both_kc && c_dtype == POLUS_BF16 && use_ring128(M, N, K, polus_gemm_epi_mode(a, 0, 0)))
-                return polus_launch_gemm_ring128(a, polus_gemm_epi_mode(a, 0, 0), 0, st);
-            return polus_launch_gemm_ring(a, c_dtype == POLUS_F32, a_ks, b_ks, 1, st);
-        }
-        GemmArgs s = a;              // slabs: plain f32 stores, epilogue applied by the reduce kernel
-        s.C = a.partial; s.ldc = N; s.c_split_stride = (long)M * N; s.partial = nullptr;
-        s.alpha = 1.0f; s.bias = nullptr; s.flags = 0; s.resid = nullptr; s.aux = nullptr;
-        s.epi_vec = (N % 4 == 0); s.epi_vec16 = (N % 4 == 0) && polus_aligned16(a.partial);
-        rc = polus_launch_gemm_ring(s, 1, a_ks, b_ks, splits_eff, st);
-        if (rc != POLUS_OK) return rc;
-        goto reduce;
-    }
-    if (dtype == POLUS_BF16) {
-        rc = (c_dtype == POLUS_F32) ? dispatch_layout<bf16_t, float>(a_layout, b_layout, a, grid, st)
-                                    : dispatch_layout<bf16_t, bf16_t>(a_layout, b_layout, a, grid, st);
-    } else {
-        rc = dispatch_layout<float, float>(a_layout, b_layout, a, grid, st);
-    }
-    if (rc != POLUS_OK) return rc;
-reduce:
-    if (split_k > 1) {
-        long total = (long)M * N;
-        int blocks = (int)((total + 255) / 256);
-        if (c_dtype == POLUS_F32)
-            hipLaunchKernelGGL(splitk_reduce_kernel<float>, dim3(blocks), dim3(256), 0, st,
-                               a.partial, splits_eff, M, N, static_cast<float*>(C), ldc, alpha, bias,
-                               (flags & POLUS_GEMM_ACCUM_C) ? 1 : 0);
-        else
-            hipLaunchKernelGGL(splitk_reduce_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st,
-                               a.partial, splits_eff, M, N, static_cast<bf16_t*>(C), ldc, alpha, bias,
-                               (flags & POLUS_GEMM_ACCUM_C) ? 1 : 0);
-        POLUS_CHECK_LAUNCH("polus_gemm(splitk_reduce)");
-    }
-    return POLUS_OK;
-}
-
 // ---- Dense backward for the parameters: dW = dY^T X (+)= and db = column sums of dY, one pass
 // over dY.  On the ring kernel the bias gradient rides on the matrix pipe (ones-fragment MFMA).
 extern "C" size_t polus_dense_bwd_params_workspace_bytes(int T, int n_out, int n_in, int split_k) {
@@ -563,6 +610,34 @@ __global__ void colsum_splits_kernel(const float* __restrict__ partial, int spli
     out[c] = accumulate ? out[c] + s : s;
 }
 }  // namespace
+
+static int launch_colsum_splits(const float* partial, int splits, int n, float* out, int accumulate, const char* what, hipStream_t st) {
+    hipLaunchKernelGGL(colsum_splits_kernel, dim3((n + 255) / 256), dim3(256), 0, st, partial, splits, n, out, accumulate);
+    POLUS_CHECK_LAUNCH(what);
+    return POLUS_OK;
+}
+
+// GemmArgs of one dW problem for the ring / ping-pong kernels: A = dY, B = X, both K-strided and whole 16-byte chunks,
+// K slices of kps rows, their column sums of dY (the bias gradient) to colsum.
+static GemmArgs dw_args(const polus_dw_problem& q, int T, int kps, float* colsum) {
+    GemmArgs a = {};
+    a.A = q.dY; a.B = q.X; a.lda = q.lddy; a.ldb = q.ldx;
+    a.M = q.n_out; a.N = q.n_in; a.K = T; a.alpha = 1.0f;
+    a.k_per_split = kps;
+    a.a_vec = a.b_vec = 1;
+    a.colsum_a = colsum;
+    return a;
+}
+// ... and where the product goes: several slices write f32 slabs [splits][n_out][n_in], a single one writes (or adds to) dW.
+static void dw_dest(GemmArgs& a, const polus_dw_problem& q, void* slabs, int accumulate) {
+    if (slabs) {
+        a.C = slabs; a.ldc = q.n_in; a.c_split_stride = (long)q.n_out * q.n_in;
+        a.epi_vec = a.epi_vec16 = (q.n_in % 4 == 0);
+    } else {
+        a.C = q.dW; a.ldc = q.lddw; a.flags = accumulate ? POLUS_GEMM_ACCUM_C : 0;
+        a.epi_vec = a.epi_vec16 = polus_aligned16(q.dW) && (q.lddw % 4 == 0);
+    }
+}
 
 extern "C" int polus_dense_bwd_params(int dtype, const void* dY, long lddy, const void* X, long ldx,
                                       float* dW, long lddw, float* db, int T, int n_out, int n_in,
@@ -591,37 +666,19 @@ extern "C" int polus_dense_bwd_params(int dtype, const void* dY, long lddy, cons
         if (rc != POLUS_OK || !db) return rc;
         return polus_colsum(dtype, dY, lddy, T, n_out, db, accumulate, cs_ws, workspace_bytes - slab_bytes, stream);
     }
-    GemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A = dY; a.B = X; a.lda = lddy; a.ldb = ldx;
-    a.M = n_out; a.N = n_in; a.K = T; a.alpha = 1.0f;
-    a.k_per_split = ((nkt + split_k - 1) / split_k) * bk;
-    const int splits_eff = (nkt + (a.k_per_split / bk) - 1) / (a.k_per_split / bk);
-    a.a_vec = a.b_vec = 1;
-    a.colsum_a = cs_ws;
-    a.order = polus_cfg().gemm_order;
-    a.persist = polus_cfg().gemm_persist ? max(32, polus_num_cus() - polus_reserved_cus()) : 0;
-    a.persist_all = polus_cfg().gemm_persist >= 2;
-    int rc;
-    if (splits_eff > 1) {
-        a.C = ws; a.ldc = n_in; a.c_split_stride = (long)n_out * n_in;
-        a.epi_vec = (n_in % 4 == 0); a.epi_vec16 = (n_in % 4 == 0);
-        rc = polus_launch_gemm_ring(a, 1, 1, 1, splits_eff, st);
-        if (rc != POLUS_OK) return rc;
-        long total = (long)n_out * n_in;
-        hipLaunchKernelGGL(splitk_reduce_kernel<float>, dim3((int)((total + 255) / 256)), dim3(256), 0, st,
-                           reinterpret_cast<const float*>(ws), splits_eff, n_out, n_in, dW, lddw, 1.0f,
-                           (const float*)nullptr, accumulate ? 1 : 0);
-        POLUS_CHECK_LAUNCH("polus_dense_bwd_params(reduce)");
-    } else {
-        a.C = dW; a.ldc = lddw; a.flags = accumulate ? POLUS_GEMM_ACCUM_C : 0;
-        a.epi_vec = polus_aligned16(dW) && (lddw % 4 == 0); a.epi_vec16 = a.epi_vec;
-        rc = polus_launch_gemm_ring(a, 1, 1, 1, 1, st);
+    const polus_dw_problem q = {dY, lddy, X, ldx, dW, lddw, db, n_out, n_in};
+    const int kt_per_split = (nkt + split_k - 1) / split_k;
+    const int splits = (nkt + kt_per_split - 1) / kt_per_split;
+    GemmArgs a = dw_args(q, T, kt_per_split * bk, cs_ws);
+    dw_dest(a, q, splits > 1 ? ws : nullptr, accumulate);
+    int rc = polus_launch_gemm_ring(a, 1, 1, 1, splits, -1, st);
+    if (rc != POLUS_OK) return rc;
+    if (splits > 1) {
+        rc = launch_splitk_reduce(POLUS_F32, reinterpret_cast<const float*>(ws), splits, n_out, n_in, dW, lddw, 1.0f, nullptr,
+                                  accumulate ? 1 : 0, "polus_dense_bwd_params(reduce)", st);
         if (rc != POLUS_OK) return rc;
     }
-    hipLaunchKernelGGL(colsum_splits_kernel, dim3((n_out + 255) / 256), dim3(256), 0, st, cs_ws, splits_eff, n_out, db, accumulate ? 1 : 0);
-    POLUS_CHECK_LAUNCH("polus_dense_bwd_params(colsum)");
-    return POLUS_OK;
+    return launch_colsum_splits(cs_ws, splits, n_out, db, accumulate ? 1 : 0, "polus_dense_bwd_params(colsum)", st);
 }
 
 // ---- The same for several Dense layers at once (all four of an encoder layer): one ring launch
@@ -641,21 +698,13 @@ static bool grouped_use_pp(int n, const polus_dw_problem* pr, int T) {
 
 // The stream-K hybrid replaces the even split when the library chooses the slices itself (split_k <= 0), the ping-pong
 // kernel applies and the even split would leave at least 1/16 of the CUs without a workgroup.
-static bool grouped_sk_plan(int n, const polus_dw_problem* pr, int T, int split_k, PPKSSKPlan* pl) {
-    if (!polus_cfg().dw_streamk || split_k > 0 || !grouped_use_pp(n, pr, T)) return false;
+static bool grouped_sk_plan(int n, const polus_dw_problem* pr, int T, int split_k, bool pp, PPKSSKPlan* pl) {
+    if (!polus_cfg().dw_streamk || split_k > 0 || !pp) return false;
     int no[POLUS_MAX_GROUP], ni[POLUS_MAX_GROUP];
     for (int k = 0; k < n; ++k) { no[k] = pr[k].n_out; ni[k] = pr[k].n_in; }
     int ncu = polus_num_cus() - polus_reserved_cus();
     if (polus_cfg().dw_sk_cus > 0 && polus_cfg().dw_sk_cus < ncu) ncu = polus_cfg().dw_sk_cus;
     return polus_ppks_sk_plan(no, ni, n, T, ncu, polus_cfg().dw_sk_delta, pl) != 0;
-}
-static size_t grouped_sk_need(int n, const polus_dw_problem* pr, const PPKSSKPlan& pl, size_t* cs_off) {
-    size_t off = (size_t)pl.ttot * pl.slots * 256 * 256 * sizeof(float);
-    for (int k = 0; k < n; ++k) {
-        cs_off[k] = off;
-        off += (((size_t)pl.slots * pr[k].n_out * sizeof(float) + 255) / 256) * 256;
-    }
-    return off + 256;
 }
 
 static void grouped_splits(int n, const polus_dw_problem* pr, int T, int split_k, int* splits, bool pp) {
@@ -693,35 +742,78 @@ static void grouped_splits(int n, const polus_dw_problem* pr, int T, int split_k
     }
 }
 
-static size_t grouped_need(int n, const polus_dw_problem* pr, const int* splits, size_t* slab_off, size_t* cs_off) {
-    size_t off = 0;
+// Everything the workspace query and the launcher of a grouped dW must agree on, computed in one place from what the query
+// knows: (n, problems' shapes, T, split_k) and the switches.
+// `pp` is grouped_use_pp, decided from shapes alone: the query cannot see the dtype and the pointers that can send the launcher
+// to its one-by-one fallback.  That is safe.  Where the grouped kernel runs, the launcher's conditions imply those of the
+// ring kernel, so pp (and sk, which needs pp) are exactly the kernel it takes and the layout here is the one it writes.
+// Where it does not, no grouped kernel writes anything: each problem runs alone with splits[k] slices -- a count sized for
+// ping-pong tiles is as valid a split_k as any -- in a workspace of at least `single` bytes, which is sized for those counts.
+struct GroupedDwPlan {
+    bool pp, sk;
+    int splits[POLUS_MAX_GROUP];                             // K slices asked for, per problem
+    int kps[POLUS_MAX_GROUP], eff[POLUS_MAX_GROUP];          // even split: contraction rows per slice, non-empty slices
+    size_t slab_off[POLUS_MAX_GROUP], cs_off[POLUS_MAX_GROUP];   // even split: slabs [splits][n_out][n_in], column sums [splits][n_out]
+    PPKSSKPlan skp;                                          // sk: the stream-K launch, its slabs at offset 0 ...
+    size_t sk_cs_off[POLUS_MAX_GROUP];                       // ... and its column sums [slots][n_out]
+    size_t bytes;                                            // the largest of the even, stream-K and one-by-one layouts
+};
+
+static void grouped_dw_plan(int n, const polus_dw_problem* pr, int T, int split_k, GroupedDwPlan* pl) {
+    pl->pp = grouped_use_pp(n, pr, T);
+    grouped_splits(n, pr, T, split_k, pl->splits, pl->pp);
+    const int nkt = (T + 63) / 64;
+    size_t off = 0, single = 0;
     for (int k = 0; k < n; ++k) {
-        slab_off[k] = off;
-        if (splits[k] > 1) off += (((size_t)splits[k] * pr[k].n_out * pr[k].n_in * sizeof(float) + 255) / 256) * 256;
-        cs_off[k] = off;
-        off += (((size_t)splits[k] * pr[k].n_out * sizeof(float) + 255) / 256) * 256;
+        const int sk = pl->splits[k] > nkt ? nkt : pl->splits[k];
+        pl->kps[k] = ((nkt + sk - 1) / sk) * 64;
+        pl->eff[k] = (nkt + (pl->kps[k] / 64) - 1) / (pl->kps[k] / 64);
+        pl->slab_off[k] = off;
+        if (pl->splits[k] > 1) off += (((size_t)pl->splits[k] * pr[k].n_out * pr[k].n_in * sizeof(float) + 255) / 256) * 256;
+        pl->cs_off[k] = off;
+        off += (((size_t)pl->splits[k] * pr[k].n_out * sizeof(float) + 255) / 256) * 256;
+        const size_t b = polus_dense_bwd_params_workspace_bytes(T, pr[k].n_out, pr[k].n_in, pl->splits[k]);   // the fallback runs them one by one
+        if (b > single) single = b;
     }
-    return off + 256;
+    pl->bytes = off + 256;
+    pl->sk = grouped_sk_plan(n, pr, T, split_k, pl->pp, &pl->skp);
+    if (pl->sk) {
+        off = (size_t)pl->skp.ttot * pl->skp.slots * 256 * 256 * sizeof(float);
+        for (int k = 0; k < n; ++k) {
+            pl->sk_cs_off[k] = off;
+            off += (((size_t)pl->skp.slots * pr[k].n_out * sizeof(float) + 255) / 256) * 256;
+        }
+        if (off + 256 > pl->bytes) pl->bytes = off + 256;
+    }
+    if (single > pl->bytes) pl->bytes = single;
 }
 
 extern "C" size_t polus_dense_bwd_params_grouped_workspace_bytes(int n, const polus_dw_problem* problems, int T, int split_k) {
     if (n < 1 || n > POLUS_MAX_GROUP || !problems || T < 1) return 0;
-    int splits[POLUS_MAX_GROUP];
-    grouped_splits(n, problems, T, split_k, splits, grouped_use_pp(n, problems, T));
-    size_t so[POLUS_MAX_GROUP], co[POLUS_MAX_GROUP];
-    size_t grouped = grouped_need(n, problems, splits, so, co);
-    size_t single = 0;   // fallback path runs them one by one
+    GroupedDwPlan pl;
+    grouped_dw_plan(n, problems, T, split_k, &pl);
+    return pl.bytes;
+}
+
+// Per-problem arrays for the one-launch reductions of a group (polus_launch_dw_group_reduce / _sk).
+struct DwGroupOut {
+    const float* slabs[POLUS_MAX_GROUP]; float* cs[POLUS_MAX_GROUP];
+    float* dW[POLUS_MAX_GROUP]; float* db[POLUS_MAX_GROUP];
+    long lddw[POLUS_MAX_GROUP]; int n_out[POLUS_MAX_GROUP], n_in[POLUS_MAX_GROUP];
+    bool aligned;     // every dW allows the reductions' 16-byte accesses
+};
+// slab_off: null where the slabs are not per problem (stream-K) -- else problem k has slabs iff eff[k] > 1
+static DwGroupOut dw_group_out(int n, const polus_dw_problem* pr, unsigned char* ws, const size_t* cs_off, const size_t* slab_off, const int* eff) {
+    DwGroupOut o;
+    o.aligned = true;
     for (int k = 0; k < n; ++k) {
-        size_t b = polus_dense_bwd_params_workspace_bytes(T, problems[k].n_out, problems[k].n_in, splits[k]);
-        if (b > single) single = b;
+        const polus_dw_problem& q = pr[k];
+        o.slabs[k] = slab_off && eff[k] > 1 ? reinterpret_cast<const float*>(ws + slab_off[k]) : nullptr;
+        o.cs[k] = q.db ? reinterpret_cast<float*>(ws + cs_off[k]) : nullptr;
+        o.dW[k] = q.dW; o.db[k] = q.db; o.lddw[k] = q.lddw; o.n_out[k] = q.n_out; o.n_in[k] = q.n_in;
+        o.aligned = o.aligned && (q.n_in % 4 == 0) && (q.lddw % 4 == 0) && polus_aligned16(q.dW);
     }
-    PPKSSKPlan pl;
-    if (grouped_sk_plan(n, problems, T, split_k, &pl)) {
-        size_t co2[POLUS_MAX_GROUP];
-        const size_t sk = grouped_sk_need(n, problems, pl, co2);
-        if (sk > grouped) grouped = sk;
-    }
-    return grouped > single ? grouped : single;
+    return o;
 }
 
 extern "C" int polus_dense_bwd_params_grouped(int dtype, int n, const polus_dw_problem* problems, int T, int accumulate,
@@ -735,113 +827,57 @@ extern "C" int polus_dense_bwd_params_grouped(int dtype, int n, const polus_dw_p
         ring = ring && polus_aligned16(q.dY) && polus_aligned16(q.X) && ((q.lddy * es) % 16 == 0) && ((q.ldx * es) % 16 == 0) &&
                (q.n_out % 8 == 0) && (q.n_in % 8 == 0) && q.n_out >= 256 && q.n_in >= 128;
     }
-    const bool pp = ring && grouped_use_pp(n, problems, T);
-    int splits[POLUS_MAX_GROUP];
-    grouped_splits(n, problems, T, split_k, splits, grouped_use_pp(n, problems, T));
-    size_t need = polus_dense_bwd_params_grouped_workspace_bytes(n, problems, T, split_k);
-    if (!workspace || workspace_bytes < need) { polus_set_error("polus_dense_bwd_params_grouped: workspace %zu < %zu", workspace_bytes, need); return POLUS_ERR_WORKSPACE; }
+    GroupedDwPlan pl;
+    grouped_dw_plan(n, problems, T, split_k, &pl);
+    if (!workspace || workspace_bytes < pl.bytes) { polus_set_error("polus_dense_bwd_params_grouped: workspace %zu < %zu", workspace_bytes, pl.bytes); return POLUS_ERR_WORKSPACE; }
     if (!ring) {
         for (int k = 0; k < n; ++k) {
             const polus_dw_problem& q = problems[k];
             int rc;
             if (q.db) rc = polus_dense_bwd_params(dtype, q.dY, q.lddy, q.X, q.ldx, q.dW, q.lddw, q.db, T, q.n_out, q.n_in,
-                                                  accumulate, splits[k], workspace, workspace_bytes, stream);
+                                                  accumulate, pl.splits[k], workspace, workspace_bytes, stream);
             else rc = polus_gemm(dtype, POLUS_K_STRIDED, POLUS_K_STRIDED, POLUS_F32, q.dY, q.lddy, q.X, q.ldx, q.dW, q.lddw,
                                  q.n_out, q.n_in, T, 1.0f, nullptr, nullptr, 0, nullptr, 0, 0, accumulate ? POLUS_GEMM_ACCUM_C : 0,
-                                 splits[k], workspace, workspace_bytes, stream);
+                                 pl.splits[k], workspace, workspace_bytes, stream);
             if (rc != POLUS_OK) return rc;
         }
         return POLUS_OK;
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    PPKSSKPlan skp;
-    if (pp && grouped_sk_plan(n, problems, T, split_k, &skp)) {
-        size_t co2[POLUS_MAX_GROUP];
-        grouped_sk_need(n, problems, skp, co2);
-        unsigned char* ws2 = static_cast<unsigned char*>(workspace);
-        GemmArgs ga2[POLUS_MAX_GROUP];
-        float* cs2[POLUS_MAX_GROUP]; float* dWs[POLUS_MAX_GROUP]; float* dbs[POLUS_MAX_GROUP];
-        long ldw[POLUS_MAX_GROUP]; int no[POLUS_MAX_GROUP], ni[POLUS_MAX_GROUP];
-        bool aligned = true;
-        for (int k = 0; k < n; ++k) {
-            const polus_dw_problem& q = problems[k];
-            GemmArgs& a = ga2[k];
-            memset(&a, 0, sizeof(a));
-            a.A = q.dY; a.B = q.X; a.lda = q.lddy; a.ldb = q.ldx;
-            a.M = q.n_out; a.N = q.n_in; a.K = T; a.alpha = 1.0f;
-            a.a_vec = a.b_vec = 1; a.epi_vec = a.epi_vec16 = 1;
-            cs2[k] = q.db ? reinterpret_cast<float*>(ws2 + co2[k]) : nullptr;
-            dWs[k] = q.dW; dbs[k] = q.db; ldw[k] = q.lddw; no[k] = q.n_out; ni[k] = q.n_in;
-            aligned = aligned && (q.n_in % 4 == 0) && (q.lddw % 4 == 0) && polus_aligned16(q.dW);
-        }
-        if (aligned) {
-            int rc2 = polus_launch_gemm_ppks_sk(ga2, skp, reinterpret_cast<float*>(ws2), cs2, st);
-            if (rc2 != POLUS_OK) return rc2;
-            return polus_launch_dw_group_reduce_sk(skp, reinterpret_cast<const float*>(ws2), cs2, dWs, dbs, ldw, no, ni, accumulate ? 1 : 0, st);
-        }
-    }
-    const int bk = 64;
-    const int nkt = (T + bk - 1) / bk;
-    int eff[POLUS_MAX_GROUP], kps[POLUS_MAX_GROUP];
-    for (int k = 0; k < n; ++k) {
-        int sk = splits[k] > nkt ? nkt : splits[k];
-        kps[k] = ((nkt + sk - 1) / sk) * bk;
-        eff[k] = (nkt + (kps[k] / bk) - 1) / (kps[k] / bk);
-    }
-    size_t so[POLUS_MAX_GROUP], co[POLUS_MAX_GROUP];
-    grouped_need(n, problems, splits, so, co);
     unsigned char* ws = static_cast<unsigned char*>(workspace);
     GemmArgs ga[POLUS_MAX_GROUP];
-    for (int k = 0; k < n; ++k) {
-        const polus_dw_problem& q = problems[k];
-        GemmArgs& a = ga[k];
-        memset(&a, 0, sizeof(a));
-        a.A = q.dY; a.B = q.X; a.lda = q.lddy; a.ldb = q.ldx;
-        a.M = q.n_out; a.N = q.n_in; a.K = T; a.alpha = 1.0f;
-        a.k_per_split = kps[k];
-        a.a_vec = a.b_vec = 1;
-        a.colsum_a = q.db ? reinterpret_cast<float*>(ws + co[k]) : nullptr;
-        a.order = 0;
-        a.persist = 0;
-        a.persist_all = 0;
-        if (eff[k] > 1) {
-            a.C = ws + so[k]; a.ldc = q.n_in; a.c_split_stride = (long)q.n_out * q.n_in;
-            a.epi_vec = a.epi_vec16 = (q.n_in % 4 == 0);
-        } else {
-            a.C = q.dW; a.ldc = q.lddw; a.flags = accumulate ? POLUS_GEMM_ACCUM_C : 0;
-            a.epi_vec = polus_aligned16(q.dW) && (q.lddw % 4 == 0); a.epi_vec16 = a.epi_vec;
+    if (pl.sk) {
+        const DwGroupOut o = dw_group_out(n, problems, ws, pl.sk_cs_off, nullptr, nullptr);
+        if (o.aligned) {             // else: the even split below
+            for (int k = 0; k < n; ++k) {
+                ga[k] = dw_args(problems[k], T, 0, nullptr);     // the stream-K kernel addresses slabs and column sums itself
+                ga[k].epi_vec = ga[k].epi_vec16 = 1;
+            }
+            int rc = polus_launch_gemm_ppks_sk(ga, pl.skp, reinterpret_cast<float*>(ws), o.cs, st);
+            if (rc != POLUS_OK) return rc;
+            return polus_launch_dw_group_reduce_sk(pl.skp, reinterpret_cast<const float*>(ws), o.cs, o.dW, o.db, o.lddw, o.n_out, o.n_in, accumulate ? 1 : 0, st);
         }
     }
-    int rc = pp ? polus_launch_gemm_ppks_grouped_dw(ga, n, eff, st) : polus_launch_gemm_ring_grouped_dw(ga, n, eff, st);
+    const DwGroupOut o = dw_group_out(n, problems, ws, pl.cs_off, pl.slab_off, pl.eff);
+    for (int k = 0; k < n; ++k) {
+        ga[k] = dw_args(problems[k], T, pl.kps[k], o.cs[k]);
+        dw_dest(ga[k], problems[k], pl.eff[k] > 1 ? ws + pl.slab_off[k] : nullptr, accumulate);
+    }
+    int rc = pl.pp ? polus_launch_gemm_ppks_grouped_dw(ga, n, pl.eff, st) : polus_launch_gemm_ring_grouped_dw(ga, n, pl.eff, st);
     if (rc != POLUS_OK) return rc;
-    if (polus_cfg().dw_fused_reduce) {
-        // every slab reduction and every bias-gradient finalisation of the group in ONE launch
-        const float* slabs[POLUS_MAX_GROUP]; const float* cs[POLUS_MAX_GROUP];
-        float* dWs[POLUS_MAX_GROUP]; float* dbs[POLUS_MAX_GROUP];
-        long ldw[POLUS_MAX_GROUP]; int no[POLUS_MAX_GROUP], ni[POLUS_MAX_GROUP];
-        bool fusable = true;
-        for (int k = 0; k < n; ++k) {
-            const polus_dw_problem& q = problems[k];
-            slabs[k] = eff[k] > 1 ? reinterpret_cast<const float*>(ws + so[k]) : nullptr;
-            cs[k] = q.db ? reinterpret_cast<const float*>(ws + co[k]) : nullptr;
-            dWs[k] = q.dW; dbs[k] = q.db; ldw[k] = q.lddw; no[k] = q.n_out; ni[k] = q.n_in;
-            fusable = fusable && (q.n_in % 4 == 0) && (q.lddw % 4 == 0) && polus_aligned16(q.dW);
-        }
-        if (fusable) return polus_launch_dw_group_reduce(n, slabs, cs, dWs, dbs, ldw, no, ni, eff, accumulate ? 1 : 0, st);
-    }
+    // every slab reduction and every bias-gradient finalisation of the group in ONE launch
+    if (polus_cfg().dw_fused_reduce && o.aligned)
+        return polus_launch_dw_group_reduce(n, o.slabs, o.cs, o.dW, o.db, o.lddw, o.n_out, o.n_in, pl.eff, accumulate ? 1 : 0, st);
     for (int k = 0; k < n; ++k) {
         const polus_dw_problem& q = problems[k];
-        if (eff[k] > 1) {
-            long total = (long)q.n_out * q.n_in;
-            hipLaunchKernelGGL(splitk_reduce_kernel<float>, dim3((int)((total + 255) / 256)), dim3(256), 0, st,
-                               reinterpret_cast<const float*>(ws + so[k]), eff[k], q.n_out, q.n_in, q.dW, q.lddw, 1.0f,
-                               (const float*)nullptr, accumulate ? 1 : 0);
-            POLUS_CHECK_LAUNCH("polus_dense_bwd_params_grouped(reduce)");
+        if (pl.eff[k] > 1) {
+            rc = launch_splitk_reduce(POLUS_F32, o.slabs[k], pl.eff[k], q.n_out, q.n_in, q.dW, q.lddw, 1.0f, nullptr, accumulate ? 1 : 0,
+                                      "polus_dense_bwd_params_grouped(reduce)", st);
+            if (rc != POLUS_OK) return rc;
         }
         if (q.db) {
-            hipLaunchKernelGGL(colsum_splits_kernel, dim3((q.n_out + 255) / 256), dim3(256), 0, st,
-                               reinterpret_cast<const float*>(ws + co[k]), eff[k], q.n_out, q.db, accumulate ? 1 : 0);
-            POLUS_CHECK_LAUNCH("polus_dense_bwd_params_grouped(colsum)");
+            rc = launch_colsum_splits(o.cs[k], pl.eff[k], q.n_out, q.db, accumulate ? 1 : 0, "polus_dense_bwd_params_grouped(colsum)", st);
+            if (rc != POLUS_OK) return rc;
         }
     }
     return POLUS_OK;

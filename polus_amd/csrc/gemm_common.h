@@ -23,8 +23,7 @@ struct GemmArgs {
     unsigned drop_thresh, drop_seed;
     float* colsum_a;      // ring kernel, A K-strided: per-split column sums of A, [splits][M] (bias gradient)
     long c_split_stride;  // elements between the C slabs of consecutive K-splits (ring kernel)
-    int persist_all;  // POLUS_GEMM_PERSIST=2: the persistent form for every multi-round ping-pong launch (A/B)
-    int persist; // gemm_pp.hip: > 0 = number of CUs for the persistent form of multi-round launches (POLUS_GEMM_PERSIST), 0 = one workgroup per tile
+    int unused0, unused1; // no kernel reads them: placeholders that keep the kernel-argument offsets of the fields behind them
     int order;   // gemm_pp.hip: column tiles the concurrent tiles of one XCD span (0 = its run in row-major order)
     const PolusDyn* dyn;  // per-step scalars in device memory (graph replay) or null: kernels with a dropout epilogue
                           // replace drop_seed by polus_eff_seed(drop_seed, dyn) on entry
@@ -522,22 +521,36 @@ __device__ __forceinline__ void tile_of(int bid, int nwg, int tiles_n, int order
 
 }  // namespace pgemm
 
-// gemm_ring.hip: same contract, 256x128 tile, two workgroups per CU.
+// The launchers below run what gemm.hip decided (gemm_route and the grouped dW plan); they check their arguments and decide nothing.
+// mode: compile-time epilogue class of a bf16-C launch (0 = alpha / bias, 1 = activation forward + pre-activation to aux, 2 = residual
+// (+ dropout when drop), 3 = activation backward with aux read), -1 = the run-time epilogue.  polus_dispatch_epi calls
+// f(bool_constant<DROP>, integral_constant<int, MODE>) for a mode >= 0; dropout exists for mode 2 only.
+template <typename F> int polus_dispatch_epi(int mode, int drop, F&& f) {
+    typedef std::false_type no_drop;
+    switch (mode) {
+        case 0: return f(no_drop(), std::integral_constant<int, 0>());
+        case 1: return f(no_drop(), std::integral_constant<int, 1>());
+        case 2: return drop ? f(std::true_type(), std::integral_constant<int, 2>()) : f(no_drop(), std::integral_constant<int, 2>());
+        case 3: return f(no_drop(), std::integral_constant<int, 3>());
+    }
+    return POLUS_ERR_INVALID;
+}
+// gemm_ring.hip: same contract as gemm.hip's kernel, 256x128 tile, two workgroups per CU.
 // a_ks / b_ks: operand stored [K][rows]; splits > 1: blockIdx.y selects [y*k_per_split, ..) and C + y*c_split_stride.
-int polus_launch_gemm_ring(const pgemm::GemmArgs& a, int c_is_f32, int a_ks, int b_ks, int splits, hipStream_t st);
-// gemm_ring.hip: 128 x 128 tile, three workgroups per CU, both operands K-contiguous, bf16 C, mode from polus_gemm_epi_mode:
+// mode >= 0 needs bf16 C, both operands K-contiguous and splits == 1.
+int polus_launch_gemm_ring(const pgemm::GemmArgs& a, int c_is_f32, int a_ks, int b_ks, int splits, int mode, hipStream_t st);
+// gemm_ring.hip: 128 x 128 tile, three workgroups per CU, both operands K-contiguous, bf16 C, mode >= 0:
 // for launches whose 256-row tiles would leave most of the chip idle (a few thousand tokens).
 int polus_launch_gemm_ring128(const pgemm::GemmArgs& a, int mode, int drop, hipStream_t st);
 // several dW problems (both operands K-strided, f32 C / slabs, same K and k_per_split) in one launch
 #define POLUS_MAX_GROUP 8
 int polus_launch_gemm_ring_grouped_dw(const pgemm::GemmArgs* probs, int n, const int* splits, hipStream_t st);
-// dropout epilogue (POLUS_GEMM_DROPOUT): bf16 C, both operands K-contiguous only.
-int polus_launch_gemm_ring_dropout(const pgemm::GemmArgs& a, hipStream_t st);
-// gemm.hip: compile-time epilogue class of a launch (0 bias, 1 act fwd, 2 residual (+ dropout), 3 act bwd; -1: none fits)
-int polus_gemm_epi_mode(const pgemm::GemmArgs& a, int c_is_f32, int drop);
+// dropout epilogue (POLUS_GEMM_DROPOUT): bf16 C, both operands K-contiguous only; mode 2 or -1.
+int polus_launch_gemm_ring_dropout(const pgemm::GemmArgs& a, int mode, hipStream_t st);
 // gemm_pp.hip: 256 x tn tile (tn = 256 or 192), 8 waves in two half-phase-staggered groups, one workgroup per
-// CU, both operands K-contiguous, K % 64 == 0, bf16 C, mode from polus_gemm_epi_mode.
-int polus_launch_gemm_pp(const pgemm::GemmArgs& a, int mode, int drop, int tn, hipStream_t st);
+// CU, both operands K-contiguous, K % 64 == 0, bf16 C, mode >= 0.  persist_cus > 0: the persistent form, that many
+// workgroups walk the tiles; 0: one workgroup per tile.
+int polus_launch_gemm_pp(const pgemm::GemmArgs& a, int mode, int drop, int tn, int persist_cus, hipStream_t st);
 // gemm_ppks.hip: the grouped dW launch on 256 x 256 tiles (both operands K-strided, f32 C / slabs, K % 64 == 0),
 // and the one-launch reduction of a group's slabs and bias-gradient partials.
 int polus_ppks_tiles(int n_out, int n_in);

@@ -387,13 +387,7 @@ int launch_ppp(const GemmArgs& a, int ncu, hipStream_t st) {
 }
 template <int NT>
 int launch_ppp_mode(const GemmArgs& a, int mode, int drop, int ncu, hipStream_t st) {
-    switch (mode) {
-        case 0: return launch_ppp<NT, false, 0>(a, ncu, st);
-        case 1: return launch_ppp<NT, false, 1>(a, ncu, st);
-        case 2: return drop ? launch_ppp<NT, true, 2>(a, ncu, st) : launch_ppp<NT, false, 2>(a, ncu, st);
-        case 3: return launch_ppp<NT, false, 3>(a, ncu, st);
-    }
-    return POLUS_ERR_INVALID;
+    return polus_dispatch_epi(mode, drop, [&](auto d, auto m) { return launch_ppp<NT, decltype(d)::value, decltype(m)::value>(a, ncu, st); });
 }
 
 template <int NT, bool DROP, int MODE>
@@ -414,32 +408,18 @@ int launch_pp(const GemmArgs& a, hipStream_t st) {
 
 template <int NT>
 int launch_pp_mode(const GemmArgs& a, int mode, int drop, hipStream_t st) {
-    switch (mode) {
-        case 0: return launch_pp<NT, false, 0>(a, st);
-        case 1: return launch_pp<NT, false, 1>(a, st);
-        case 2: return drop ? launch_pp<NT, true, 2>(a, st) : launch_pp<NT, false, 2>(a, st);
-        case 3: return launch_pp<NT, false, 3>(a, st);
-    }
-    return POLUS_ERR_INVALID;
+    return polus_dispatch_epi(mode, drop, [&](auto d, auto m) { return launch_pp<NT, decltype(d)::value, decltype(m)::value>(a, st); });
 }
 
 }  // namespace
 
-// tn = 256 or 192; mode from polus_gemm_epi_mode (>= 0); K % 64 == 0; bf16 C; 16-byte aligned rows.
-int polus_launch_gemm_pp(const GemmArgs& a, int mode, int drop, int tn, hipStream_t st) {
+// tn = 256 or 192; mode >= 0; K % 64 == 0; bf16 C; 16-byte aligned rows.  persist_cus > 0: that many workgroups walk several
+// rounds of tiles, the next tile's operand prologue under the epilogue (gemm.hip: pp_persist_cus says when); 0: one per tile.
+int polus_launch_gemm_pp(const GemmArgs& a, int mode, int drop, int tn, int persist_cus, hipStream_t st) {
     if (mode < 0 || a.K % TK != 0 || a.K < TK) return POLUS_ERR_INVALID;
-    if (a.persist > 0) {
-        // several rounds of tiles: one workgroup per CU walks them, the next tile's operand prologue under the epilogue
-        const int tiles = ((a.M + TM - 1) / TM) * ((a.N + tn - 1) / tn);
-        // measured (tools/pp_bench.py --ab POLUS_GEMM_PERSIST=0,1,2; bench.py --config c3 | c4 | c5): wins on the 256-wide launches --
-        // the GELU ones of BERT-base (FFN1 forward, dU: -8 % from cold caches) and every multi-round launch of BERT-large (+0.5 %
-        // on the c4 step) -- and is neutral to slightly negative on the 192-wide bias-only QKV launch of BERT-base (three exact
-        // rounds, an epilogue too short to hide anything); POLUS_GEMM_PERSIST=2 forces it everywhere
-        const bool wins = tn == 256 || a.persist_all;     // 192-wide launches lose with it (c5, 512 tiles of 256 x 192: 34.4 -> 34.8 ms/step)
-        if (tiles > a.persist && wins) {
-            if (tn == 256) return launch_ppp_mode<4>(a, mode, drop, a.persist, st);
-            if (tn == 192) return launch_ppp_mode<3>(a, mode, drop, a.persist, st);
-        }
+    if (persist_cus > 0) {
+        if (tn == 256) return launch_ppp_mode<4>(a, mode, drop, persist_cus, st);
+        if (tn == 192) return launch_ppp_mode<3>(a, mode, drop, persist_cus, st);
     }
     if (tn == 256) return launch_pp_mode<4>(a, mode, drop, st);
     if (tn == 192) return launch_pp_mode<3>(a, mode, drop, st);

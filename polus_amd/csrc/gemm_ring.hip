@@ -419,29 +419,18 @@ int launch_ring128(const GemmArgs& a, hipStream_t st) {
 }
 
 int polus_launch_gemm_ring128(const GemmArgs& a, int mode, int drop, hipStream_t st) {
-    switch (mode) {
-        case 0: return launch_ring128<false, 0>(a, st);
-        case 1: return launch_ring128<false, 1>(a, st);
-        case 2: return drop ? launch_ring128<true, 2>(a, st) : launch_ring128<false, 2>(a, st);
-        case 3: return launch_ring128<false, 3>(a, st);
-    }
-    return POLUS_ERR_INVALID;
+    return polus_dispatch_epi(mode, drop, [&](auto d, auto m) { return launch_ring128<decltype(d)::value, decltype(m)::value>(a, st); });
 }
 
-int polus_launch_gemm_ring_dropout(const GemmArgs& a, hipStream_t st) {
-    if (polus_gemm_epi_mode(a, 0, 1) == 2) return launch_ring<bf16_t, false, false, true, 2>(a, 1, st);
+int polus_launch_gemm_ring_dropout(const GemmArgs& a, int mode, hipStream_t st) {
+    if (mode == 2) return launch_ring<bf16_t, false, false, true, 2>(a, 1, st);
     return launch_ring<bf16_t, false, false, true>(a, 1, st);
 }
 
-int polus_launch_gemm_ring(const GemmArgs& a, int c_is_f32, int a_ks, int b_ks, int splits, hipStream_t st) {
-    if (!c_is_f32 && !a_ks && !b_ks && splits == 1) {
-        switch (polus_gemm_epi_mode(a, 0, 0)) {      // same epilogue classes as the persistent kernel
-            case 0: return launch_ring<bf16_t, false, false, false, 0>(a, 1, st);
-            case 1: return launch_ring<bf16_t, false, false, false, 1>(a, 1, st);
-            case 2: return launch_ring<bf16_t, false, false, false, 2>(a, 1, st);
-            case 3: return launch_ring<bf16_t, false, false, false, 3>(a, 1, st);
-            default: break;
-        }
+int polus_launch_gemm_ring(const GemmArgs& a, int c_is_f32, int a_ks, int b_ks, int splits, int mode, hipStream_t st) {
+    if (mode >= 0) {
+        if (c_is_f32 || a_ks || b_ks || splits != 1) return POLUS_ERR_INVALID;
+        return polus_dispatch_epi(mode, 0, [&](auto d, auto m) { return launch_ring<bf16_t, false, false, decltype(d)::value, decltype(m)::value>(a, 1, st); });
     }
     return c_is_f32 ? launch_layout<float>(a, a_ks, b_ks, splits, st) : launch_layout<bf16_t>(a, a_ks, b_ks, splits, st);
 }

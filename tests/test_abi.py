@@ -43,6 +43,19 @@ def test_workspace_queries_are_host_only(lib):
     assert lib.polus_layernorm_bwd_workspace_bytes(16384, 768) == (512 + 4) * 3 * 768 * 4
     assert lib.polus_crf_workspace_bytes(4, 16, 3) >= (4 * 16 * 3 + 4 + 4 * 9) * 4
     assert lib.polus_sqnorm_workspace_bytes(10 ** 8) == 1024 * 4
+    # without a device the CU count falls back to the MI355X's 256
+    f = lib.polus_gemm_auto_split
+    assert (f(16384, 768, 3072), f(2048, 768, 3072), f(1024, 1024, 4096)) == (1, 4, 5)
+    # the grouped dW plan: the four weight gradients of a BERT-base layer at 16384 tokens, slices chosen by the library
+    from polus_amd import _lib, ops
+    shapes = [(768, 3072), (3072, 768), (768, 768), (2304, 768)]
+    arr = (_lib.DwProblem * 4)(*[_lib.DwProblem(None, no, None, ni, None, ni, None, no, ni) for no, ni in shapes])
+    assert lib.polus_dense_bwd_params_grouped_workspace_bytes(4, arr, 16384, 0) == 56678656
+    try:
+        ops.set_env("POLUS_DW_STREAMK", 1)
+        assert lib.polus_dense_bwd_params_grouped_workspace_bytes(4, arr, 16384, 0) == 113357056
+    finally:
+        ops.set_env("POLUS_DW_STREAMK")
 
 
 def test_argument_validation_happens_on_the_host(lib):
