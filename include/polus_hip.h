@@ -259,6 +259,11 @@ int polus_crf_viterbi(const float* potentials, const int32_t* lengths, const flo
  * B*N*Lq < 2^31. */
 int polus_maxsim_fwd(int dtype, const void* Q, const void* D, const int32_t* qmask, const int32_t* dmask,
                      float* score, long lds, int32_t* argmax, int B, int N, int Lq, int Ld, int E, void* stream);
+/* The forward without the argmax, for scoring a corpus (polus_amd/ir/search.py): the same kernel body with the
+ * argmax stores compiled out, so score is bit for bit what polus_maxsim_fwd writes for the same inputs, and 4*B*N*Lq
+ * bytes less leave the chip.  Limits: those of polus_maxsim_fwd without B*N*Lq < 2^31 (that one is the argmax's). */
+int polus_maxsim_scores(int dtype, const void* Q, const void* D, const int32_t* qmask, const int32_t* dmask,
+                        float* score, long lds, int B, int N, int Lq, int Ld, int E, void* stream);
 int polus_maxsim_bwd(int dtype, const void* Q, const void* D, const float* dscore, long lds,
                      const int32_t* argmax, void* dQ, void* dD, int B, int N, int Lq, int Ld, int E, void* stream);
 /* Row L2 normalisation, torch.nn.functional.normalize(x, dim=-1, eps) (ColBERT's cosine): x, y [rows,E] in
@@ -267,6 +272,25 @@ int polus_maxsim_bwd(int dtype, const void* Q, const void* D, const float* dscor
 int polus_l2norm_fwd(int dtype, const void* x, void* y, float* rnorm, int rows, int E, float eps, void* stream);
 int polus_l2norm_bwd(int dtype, const void* y, const float* rnorm, const void* dy, void* dx, int rows, int E,
                      float eps, void* stream);
+
+/* ---- exact running top-k of score rows, for corpus search (topk.hip).  scores f32 [rows, n], row stride lds >= n;
+ * column c is the document with id id0 + c.  top_val f32 and top_id int32, contiguous [rows, k], hold the running
+ * state and are rewritten.  Per row:
+ *   candidates = the entries of the incoming state with id >= 0, plus (scores[r][c], id0 + c) for c < n; with
+ *                init != 0 the incoming state is ignored and never read;
+ *   dropped    = candidates whose score is NaN or -inf (-inf is how a caller masks a document out);
+ *   order      = score descending by IEEE comparison (-0.0 equals +0.0 and either may come back as +0.0), ties to the
+ *                lower id;
+ *   output     = the best k candidates in that order; when fewer than k remain the tail is (-inf, -1).
+ * With init == 0 the state must come from an earlier call and its ids must be disjoint from the chunk's: duplicates
+ * are not detected.  The result is exact: a corpus merged in any chunking gives bit for bit the result of one call
+ * over the whole row.  One workgroup per row keeps the top k and a candidate buffer as 64-bit keys (orderable score
+ * bits, then the complemented id: a total order) in LDS and bitonic-sorts them when the buffer fills; no float
+ * atomics, bitwise reproducible, no workspace.  Memory-bound: one read of 4*rows*n bytes.
+ * Limits (refused before any launch): 1 <= k <= 1024; rows >= 1; n >= 1; id0 >= 0; id0 + n <= 2^31 - 1; lds >= n;
+ * non-null pointers. */
+int polus_topk_merge(const float* scores, long lds, int rows, int n, int32_t id0,
+                     float* top_val, int32_t* top_id, int k, int init, void* stream);
 
 /* ---- argmax over the last axis (PolusClassifier.inference, polus/models.py:148-150) */
 int polus_argmax(const float* x, long ldx, int32_t* out, int rows, int C, void* stream);

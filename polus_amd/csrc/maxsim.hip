@@ -8,7 +8,7 @@
 // global loads in flight while the current one is multiplied) and every wave reads its 16-token tiles from there
 // as A fragments, so an accumulator holds S[doc 16t + 4g + r][query token 16u + i] and the max over j is a
 // per-lane running compare, closed by two cross-group shuffles.  The document mask sits in LDS too.  Only B*N
-// scores and the argmax leave the chip.
+// scores and the argmax leave the chip; polus_maxsim_scores (corpus search) runs the same body without the argmax.
 // Backward (no atomics, fixed summation orders):
 //   dQ: one wave per query token, ascending c;
 //   dD: one workgroup per (document, 64- or 32-wide column chunk), f32 accumulators in LDS; wave w of 16 owns
@@ -68,13 +68,13 @@ __device__ __forceinline__ void ms_sstore(const u32x4* stg, unsigned char* buf) 
     }
 }
 
-template <typename T, int KS>
-__global__ __launch_bounds__(256) void maxsim_fwd_kernel(const T* __restrict__ Q, const T* __restrict__ D,
-                                                         const int32_t* __restrict__ qmask,
-                                                         const int32_t* __restrict__ dmask,
-                                                         float* __restrict__ score, long lds,
-                                                         int32_t* __restrict__ argmax, int B, int N, int Lq,
-                                                         int Ld, int qpb) {
+// The forward of both entry points.  ARGMAX = false (polus_maxsim_scores) compiles the argmax stores out and nothing
+// else: the winning j is still tracked, because "no valid j" is how an empty document is told, so the scores are
+// the same bits.
+template <typename T, int KS, bool ARGMAX>
+__device__ __forceinline__ void maxsim_fwd_body(const T* Q, const T* D, const int32_t* qmask, const int32_t* dmask,
+                                                float* score, long lds, int32_t* argmax, int B, int N, int Lq, int Ld,
+                                                int qpb) {
     using S = MsStage<T, KS>;
     constexpr int UT = MsTiles<T, KS>::UT;
     constexpr int E = 32 * KS;
@@ -180,7 +180,8 @@ __global__ __launch_bounds__(256) void maxsim_fwd_kernel(const T* __restrict__ Q
                 const int tok = ((uu % nut) << 4) + i;
                 const bool qv = tok < Lq && (!qmask || qmask[(size_t)bq * Lq + tok] != 0);
                 const bool hit = qv && ju != MS_NOJ;
-                if (g == 0 && tok < Lq) argmax[((size_t)bq * N + c) * Lq + tok] = hit ? ju : -1;
+                if constexpr (ARGMAX)
+                    if (g == 0 && tok < Lq) argmax[((size_t)bq * N + c) * Lq + tok] = hit ? ju : -1;
                 contrib = hit ? mu : 0.f;
             }
             // sum of the tile's 16 maxima (lanes 0..15; every group holds the same values)
@@ -195,6 +196,25 @@ __global__ __launch_bounds__(256) void maxsim_fwd_kernel(const T* __restrict__ Q
         for (int t = 0; t < nut; ++t) s += tsum[threadIdx.x * nut + t];
         score[(size_t)(b0 + threadIdx.x) * lds + c] = s;
     }
+}
+
+template <typename T, int KS>
+__global__ __launch_bounds__(256) void maxsim_fwd_kernel(const T* __restrict__ Q, const T* __restrict__ D,
+                                                         const int32_t* __restrict__ qmask,
+                                                         const int32_t* __restrict__ dmask,
+                                                         float* __restrict__ score, long lds,
+                                                         int32_t* __restrict__ argmax, int B, int N, int Lq,
+                                                         int Ld, int qpb) {
+    maxsim_fwd_body<T, KS, true>(Q, D, qmask, dmask, score, lds, argmax, B, N, Lq, Ld, qpb);
+}
+
+template <typename T, int KS>
+__global__ __launch_bounds__(256) void maxsim_scores_kernel(const T* __restrict__ Q, const T* __restrict__ D,
+                                                            const int32_t* __restrict__ qmask,
+                                                            const int32_t* __restrict__ dmask,
+                                                            float* __restrict__ score, long lds, int B, int N, int Lq,
+                                                            int Ld, int qpb) {
+    maxsim_fwd_body<T, KS, false>(Q, D, qmask, dmask, score, lds, nullptr, B, N, Lq, Ld, qpb);
 }
 
 // dQ[b, i, :] = sum over c ascending of dscore[b, c] * D[c, argmax[b, c, i], :]; one wave per query token
@@ -356,7 +376,7 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const T* __restrict__ y
     }
 }
 
-int ms_check(const char* what, int dtype, int B, int N, int Lq, int Ld, int E, long lds) {
+int ms_check(const char* what, int dtype, int B, int N, int Lq, int Ld, int E, long lds, bool with_argmax = true) {
     POLUS_REQUIRE(dtype == POLUS_F32 || dtype == POLUS_BF16, "%s: unknown dtype %d", what, dtype);
     POLUS_REQUIRE(E >= 32 && E <= MS_EMAX && E % 32 == 0, "%s: E must be a multiple of 32 in [32, %d] (got %d)", what,
                   MS_EMAX, E);
@@ -364,7 +384,7 @@ int ms_check(const char* what, int dtype, int B, int N, int Lq, int Ld, int E, l
     POLUS_REQUIRE(Ld >= 1 && Ld <= MS_LMAX, "%s: need 1 <= Ld <= %d (got %d)", what, MS_LMAX, Ld);
     POLUS_REQUIRE(B >= 1 && B <= 65535, "%s: need 1 <= B <= 65535 (got %d)", what, B);
     POLUS_REQUIRE(N >= 1 && N <= 65535, "%s: need 1 <= N <= 65535 (got %d)", what, N);
-    POLUS_REQUIRE((long long)B * N * Lq < (1LL << 31), "%s: B*N*Lq must be < 2^31 (got %lld)", what,
+    POLUS_REQUIRE(!with_argmax || (long long)B * N * Lq < (1LL << 31), "%s: B*N*Lq must be < 2^31 (got %lld)", what,
                   (long long)B * N * Lq);
     POLUS_REQUIRE(lds >= N, "%s: score row stride lds must be >= N (got %ld < %d)", what, lds, N);
     return POLUS_OK;
@@ -380,8 +400,12 @@ void fwd_launch(const void* Q, const void* D, const int32_t* qm, const int32_t* 
     int qpb = nut >= per ? 1 : min(16, per / nut);
     while (qpb > 1 && (long)N * ((B + qpb - 1) / qpb) < 512) qpb >>= 1;
     dim3 grid(N, (B + qpb - 1) / qpb);
-    hipLaunchKernelGGL((maxsim_fwd_kernel<T, KS>), grid, dim3(256), 0, st, static_cast<const T*>(Q),
-                       static_cast<const T*>(D), qm, dm, score, lds, am, B, N, Lq, Ld, qpb);
+    if (am)
+        hipLaunchKernelGGL((maxsim_fwd_kernel<T, KS>), grid, dim3(256), 0, st, static_cast<const T*>(Q),
+                           static_cast<const T*>(D), qm, dm, score, lds, am, B, N, Lq, Ld, qpb);
+    else                                              // polus_maxsim_scores (polus_maxsim_fwd refuses a null argmax)
+        hipLaunchKernelGGL((maxsim_scores_kernel<T, KS>), grid, dim3(256), 0, st, static_cast<const T*>(Q),
+                           static_cast<const T*>(D), qm, dm, score, lds, B, N, Lq, Ld, qpb);
 }
 
 template <typename T>
@@ -425,6 +449,21 @@ extern "C" int polus_maxsim_fwd(int dtype, const void* Q, const void* D, const i
     else
         fwd_dispatch<float>(E, Q, D, qmask, dmask, score, lds, argmax, B, N, Lq, Ld, st);
     POLUS_CHECK_LAUNCH("polus_maxsim_fwd");
+    return POLUS_OK;
+}
+
+extern "C" int polus_maxsim_scores(int dtype, const void* Q, const void* D, const int32_t* qmask, const int32_t* dmask,
+                                   float* score, long lds, int B, int N, int Lq, int Ld, int E, void* stream) {
+    int rc = ms_check("polus_maxsim_scores", dtype, B, N, Lq, Ld, E, lds, false);
+    if (rc != POLUS_OK) return rc;
+    POLUS_REQUIRE(Q && D && score, "polus_maxsim_scores: null pointer");
+    POLUS_REQUIRE(polus_aligned16(Q) && polus_aligned16(D), "polus_maxsim_scores: Q and D must be 16-byte aligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == POLUS_BF16)
+        fwd_dispatch<bf16_t>(E, Q, D, qmask, dmask, score, lds, nullptr, B, N, Lq, Ld, st);
+    else
+        fwd_dispatch<float>(E, Q, D, qmask, dmask, score, lds, nullptr, B, N, Lq, Ld, st);
+    POLUS_CHECK_LAUNCH("polus_maxsim_scores");
     return POLUS_OK;
 }
 

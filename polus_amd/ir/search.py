@@ -1,0 +1,180 @@
+"""Corpus search for the dual encoders of polus_amd/ir: encode and store a corpus, score queries against it in chunks
+with the kernels the trainer uses, keep an exact running top-k on the device, and drive a validation loop with it.
+
+    index = CorpusIndex(model, compute_scores)          # the trainer's model and scorer
+    for docs in corpus_batches: index.add(docs)         # {"input_ids", "attention_mask"}
+    scores, ids = index.search(queries, k=100)          # f32 / int32 [Q, k] on the device
+
+As in ir/training.py, arithmetic is hand-written HIP (ops.gemm / ops.maxsim_scores, ops.l2norm_fwd, ops.topk_merge);
+torch allocates, views and copies.  Data parallelism: every rank holds the whole index and searches its own shard of
+the queries; ValidationDataCallback gathers the predictions."""
+import torch
+
+from .. import ops
+from ..callbacks import ValidationDataCallback
+from .models import TokenReps
+
+MAX_CHUNK = 65535             # documents per launch: the MaxSim grid's limit, kept on the dot path too
+
+
+class CorpusIndex:
+    """Projected document representations in one contiguous device buffer, [N, E] ([CLS], DualEncoder) or [N, Ld, E]
+    with an int32 mask [N, Ld] (tokens, LateInteractionDualEncoder), in the model's compute dtype.
+
+    `compute_scores` is the trainer's InBatchDotScores or MaxSimScores; `normalize` and `eps` are taken from it.
+    `post_process_logits` is the trainer's hook for [CLS] vectors, applied to queries and documents as the trainer
+    applies it; token representations refuse it, as the trainer does.  `scratch_bytes` bounds the [Q, n] f32 score
+    buffer of one chunk."""
+
+    def __init__(self, model, compute_scores, post_process_logits=None, scratch_bytes=256 << 20):
+        self.model, self.compute_scores = model, compute_scores
+        self.post_process_logits = post_process_logits
+        self.scratch_bytes = int(scratch_bytes)
+        self.normalize = bool(getattr(compute_scores, "normalize", False))
+        self.eps = float(getattr(compute_scores, "eps", 1e-12))
+        self.clear()
+
+    def clear(self):
+        """Empty the index (the storage is released; the next `add` fixes the document length again)."""
+        self._reps = self._mask = None
+        self._n = 0
+        self.tokens = None            # True: token representations; fixed by the first add
+
+    def __len__(self):
+        return self._n
+
+    @property
+    def representations(self):
+        """[N, E] or [N, Ld, E]: a view of the stored documents."""
+        return None if self._reps is None else self._reps[:self._n]
+
+    @property
+    def mask(self):
+        return None if self._mask is None else self._mask[:self._n]
+
+    def _l2norm(self, x):
+        y = torch.empty_like(x)
+        r = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
+        ops.l2norm_fwd(x, y, r, self.eps)
+        return y
+
+    def _check_kind(self, rep):
+        tokens = isinstance(rep, TokenReps)
+        if tokens and self.post_process_logits is not None:
+            raise ValueError("post_process_logits does not apply to token representations: normalisation belongs "
+                             "to the scorer (MaxSimScores(normalize=True))")
+        if self.tokens is not None and tokens != self.tokens:
+            raise ValueError("the index holds " + ("token" if self.tokens else "[CLS]") + " representations")
+        return tokens
+
+    def _grow(self, need, like, tail):
+        """Room for `need` documents in one buffer: capacity doubles, the stored rows are copied over."""
+        cap = 0 if self._reps is None else self._reps.shape[0]
+        if need <= cap:
+            return
+        cap = max(need, 2 * cap)
+        # zeros: the padding of documents shorter than the index's length is never written
+        reps = torch.zeros((cap,) + tail, dtype=like.dtype, device=like.device)
+        mask = torch.zeros((cap, tail[0]), dtype=torch.int32, device=like.device) if self.tokens else None
+        if self._n:
+            reps[:self._n].copy_(self._reps[:self._n])
+            if mask is not None:
+                mask[:self._n].copy_(self._mask[:self._n])
+        self._reps, self._mask = reps, mask
+
+    def add(self, documents):
+        """Encode, project (and normalise) a batch of documents and append it; returns its ids, the consecutive int32
+        positions in the index.  Token documents are padded with masked tokens to the length of the first batch;
+        a longer batch raises ValueError."""
+        model = self.model
+        rep = model.document_projection(model.encode_document(documents, training=False), training=False)
+        tokens = self._check_kind(rep)
+        if tokens:
+            v, m = rep.values, rep.mask
+            if self.normalize:
+                v = self._l2norm(v.contiguous())
+            n, L, E = v.shape
+            if self.tokens is None:
+                self.tokens, self._ld = True, L
+            if L > self._ld:
+                raise ValueError(f"a document batch of {L} tokens does not fit the index's document length {self._ld} "
+                                 "(fixed by the first add)")
+            self._grow(self._n + n, v, (self._ld, E))
+            self._reps[self._n:self._n + n, :L].copy_(v)
+            self._mask[self._n:self._n + n, :L].copy_(m)
+        else:
+            v = rep if self.post_process_logits is None else self.post_process_logits(rep)
+            n, E = v.shape
+            self.tokens = False
+            self._grow(self._n + n, v, (E,))
+            self._reps[self._n:self._n + n].copy_(v)
+        ids = torch.arange(self._n, self._n + n, dtype=torch.int32, device=v.device)
+        self._n += n
+        return ids
+
+    def chunks(self, Q):
+        """[(start, stop), ...]: the document ranges a search with Q queries scores, one launch each: at most 65535
+        documents, and at most as many as keep the [Q, n] f32 scores within scratch_bytes."""
+        per = min(MAX_CHUNK, self.scratch_bytes // (4 * int(Q)))
+        if per < 1:
+            raise ValueError(f"scratch_bytes = {self.scratch_bytes} does not hold the scores of one document for "
+                             f"{Q} queries ({4 * int(Q)} bytes)")
+        return [(s, min(s + per, self._n)) for s in range(0, self._n, per)]
+
+    def encode_queries(self, queries):
+        """The query side of the trainer: encode_query, query_projection, then the normalisation (tokens) or
+        post_process_logits ([CLS])."""
+        q = self.model.query_projection(self.model.encode_query(queries, training=False), training=False)
+        if self._check_kind(q):
+            v = q.values.contiguous()
+            return TokenReps(self._l2norm(v) if self.normalize else v, q.mask.contiguous())
+        return (q if self.post_process_logits is None else self.post_process_logits(q)).contiguous()
+
+    def search(self, queries, k):
+        """(scores f32 [Q, k], ids int32 [Q, k]) on the device: per query the k best documents, score descending, ties
+        to the lower id; when the corpus holds fewer than k, the tail is (-inf, -1)."""
+        if self._n == 0:
+            raise ValueError("the index is empty: add documents before searching")
+        q = self.encode_queries(queries)
+        qv = q.values if self.tokens else q
+        Q = qv.shape[0]
+        spans = self.chunks(Q)
+        scratch = torch.empty((Q, max(b - a for a, b in spans)), dtype=torch.float32, device=qv.device)
+        top_val = torch.empty((Q, int(k)), dtype=torch.float32, device=qv.device)
+        top_id = torch.empty((Q, int(k)), dtype=torch.int32, device=qv.device)
+        for a, b in spans:
+            s = scratch[:, :b - a]
+            if self.tokens:
+                ops.maxsim_scores(qv, self._reps[a:b], q.mask, self._mask[a:b], s)
+            else:
+                ops.gemm(qv, self._reps[a:b], s)
+            ops.topk_merge(s, top_val, top_id, id0=a, init=(a == 0))
+        return top_val, top_id
+
+
+class RetrievalValidationCallback(ValidationDataCallback):
+    """Validation of a retrieval run: on each validated epoch the corpus (an iterable of document batches) is encoded
+    again with the trainer's current model, compute_scores and post_process_logits, every validation sample
+    `(queries, relevant)` becomes `(ids [Q, k], relevant)`, and the trainer's metrics (polus_amd/ir/metrics.py) land in
+    shared_dict["validation"][name], where SaveModelCallback(strategy="best") reads them."""
+
+    def __init__(self, corpus, tf_validation, k, name=None, validation_interval=1, show_progress=False,
+                 scratch_bytes=256 << 20):
+        super().__init__(tf_validation, custom_inference_f=self._rank, name=name, show_progress=show_progress,
+                         validation_interval=validation_interval)
+        self.corpus, self.k, self.scratch_bytes = corpus, int(k), scratch_bytes
+        self.index = None
+
+    def _rank(self, model, sample):
+        queries, relevant = sample
+        return self.index.search(queries, self.k)[1], relevant
+
+    def on_epoch_end(self, epoch):
+        if epoch % self.validation_interval:
+            return
+        trainer = self.coordinator.trainer
+        self.index = CorpusIndex(trainer.model, trainer.compute_scores, trainer.post_process_logits, self.scratch_bytes)
+        for documents in self.corpus:
+            self.index.add(documents)
+        super().on_epoch_end(epoch)
+        self.index.clear()

@@ -323,6 +323,34 @@ def maxsim_fwd(q, d, qmask, dmask, score, argmax):
                                        B, N, Lq, Ld, E, _st()), "polus_maxsim_fwd")
 
 
+def maxsim_scores(q, d, qmask, dmask, score):
+    """maxsim_fwd without the argmax (the same kernel body, bitwise the same scores): for scoring a corpus, where
+    nothing runs backward.  No B*N*Lq limit."""
+    _req_cuda(q, d, qmask, dmask, score)
+    B, Lq, E = q.shape
+    N, Ld = d.shape[0], d.shape[1]
+    assert d.dim() == 3 and d.shape[2] == E and d.dtype == q.dtype and q.is_contiguous() and d.is_contiguous()
+    assert score.dtype == torch.float32 and score.dim() == 2 and score.shape[0] >= B and score.shape[1] >= N and score.stride(1) == 1
+    check(_lib.load().polus_maxsim_scores(dtype_code(q.dtype), ptr(q), ptr(d), ptr(_maxsim_mask(qmask, B, Lq, "qmask")),
+                                          ptr(_maxsim_mask(dmask, N, Ld, "dmask")), ptr(score), score.stride(0),
+                                          B, N, Lq, Ld, E, _st()), "polus_maxsim_scores")
+
+
+def topk_merge(scores, top_val, top_id, id0=0, init=False):
+    """Merge scores (f32 [rows, n], any row stride; column c is document id0 + c) into the running top-k state
+    top_val f32 / top_id int32 [rows, k]: score descending, ties to the lower id, NaN and -inf dropped, (-inf, -1)
+    padding.  init=True starts a new state (the old contents are not read).  Exact and bitwise reproducible
+    (include/polus_hip.h polus_topk_merge)."""
+    _req_cuda(scores, top_val, top_id)
+    rows, n = scores.shape
+    k = top_val.shape[1]
+    assert scores.dtype == torch.float32 and scores.dim() == 2 and (scores.stride(1) == 1 or n == 1)
+    assert top_val.dtype == torch.float32 and top_id.dtype == torch.int32 and top_val.is_contiguous() and top_id.is_contiguous()
+    assert tuple(top_val.shape) == (rows, k) and tuple(top_id.shape) == (rows, k)
+    check(_lib.load().polus_topk_merge(ptr(scores), scores.stride(0), rows, n, int(id0), ptr(top_val), ptr(top_id), k,
+                                       1 if init else 0, _st()), "polus_topk_merge")
+
+
 def maxsim_bwd(q, d, dscore, argmax, dq, dd):
     """dq [B, Lq, E] and dd [N, Ld, E] from dscore (f32 [B, N], row stride free) and the forward's argmax; every
     element is written."""
