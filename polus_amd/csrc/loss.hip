@@ -47,13 +47,15 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restri
         for (int c = 0; c < C; ++c) mx = fmaxf(mx, x[c]);
         float se = 0.f;
         for (int c = 0; c < C; ++c) se += expf(x[c] - mx);
-        const float lse = mx + logf(se);
+        const float lz = logf(se);
+        const float lse = mx + lz;
         const float w = cw ? cw[lab] : 1.0f;
         loss = (lse - x[lab]) * w;
         const float inv = w / (float)rows;
         T* d = dlogits + (long)row * lddl;
         for (int c = 0; c < C; ++c) {
-            float pr = expf(x[c] - lse);
+            // (x - mx) - log(se), not x - lse: adding mx into lse would round p near 1 to ulp(lse)
+            float pr = expf((x[c] - mx) - lz);
             d[c] = from_f<T>((pr - (c == lab ? 1.0f : 0.0f)) * inv);
         }
     }
