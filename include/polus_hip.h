@@ -266,6 +266,25 @@ int polus_maxsim_scores(int dtype, const void* Q, const void* D, const int32_t* 
                         float* score, long lds, int B, int N, int Lq, int Ld, int E, void* stream);
 int polus_maxsim_bwd(int dtype, const void* Q, const void* D, const float* dscore, long lds,
                      const int32_t* argmax, void* dQ, void* dD, int B, int N, int Lq, int Ld, int E, void* stream);
+/* Re-ranking (rerank.hip): every query scores its own list of candidate documents, the second stage of a two-stage
+ * search.  Q [B,Lq,E], qmask [B,Lq] as above; D [N,Ld,E] and dmask int32 [N,Ld] (NULL = all ones) hold the whole
+ * stored corpus; cand int32 [B,C], row stride ldc >= C, names documents of D; score f32 [B,C], row stride lds >= C.
+ *   score[b*lds + c] = the MaxSim score of query b and document cand[b*ldc + c], bit for bit what polus_maxsim_scores
+ *                      writes for that pair (the same fragments and MFMAs in ascending k, the same summation tree and
+ *                      tile order): a document without a valid token and a query without one score 0.0;
+ *                    = -inf where cand[b*ldc + c] < 0 or >= N: the entry is absent and nothing of it is dereferenced
+ *                      (-inf is what polus_topk_merge and polus_topk_merge_ids drop).
+ * Columns of score past C are not written.  One workgroup per (query, block of candidates); a wave keeps the query's
+ * tiles in registers and streams its own documents from global memory, skipping the 16-token tiles behind a
+ * document's last valid token (masked tokens never win, so the bits do not change); queries of more tiles than a
+ * wave holds take rounds over the document.  Document addresses are 64-bit.  No LDS, no atomics, no workspace;
+ * bitwise reproducible.  Memory-bound: each candidate's valid tiles are read once per query.
+ * Limits (refused before any launch): dtype f32 or bf16; E a multiple of 32 in [32, 256]; 1 <= Lq, Ld <= 512;
+ * 1 <= B <= 65535; 1 <= C <= 65535; 1 <= N <= 2^31 - 1; ldc >= C; lds >= C; Q, D, cand, score non-null; Q and D
+ * 16-byte aligned. */
+int polus_maxsim_rerank(int dtype, const void* Q, const void* D, const int32_t* qmask, const int32_t* dmask,
+                        const int32_t* cand, long ldc, float* score, long lds,
+                        int B, int C, int N, int Lq, int Ld, int E, void* stream);
 /* Row L2 normalisation, torch.nn.functional.normalize(x, dim=-1, eps) (ColBERT's cosine): x, y [rows,E] in
  * `dtype` (E <= 256), rnorm f32 [rows].  Forward (f32 arithmetic): y = x / max(|x|, eps), rnorm = 1 / max(|x|, eps).
  * Backward: dx = (dy - y <y, dy>) * rnorm where |x| > eps, dy / eps otherwise.  One wave per row. */
@@ -291,6 +310,18 @@ int polus_l2norm_bwd(int dtype, const void* y, const float* rnorm, const void* d
  * non-null pointers. */
 int polus_topk_merge(const float* scores, long lds, int rows, int n, int32_t id0,
                      float* top_val, int32_t* top_id, int k, int init, void* stream);
+/* polus_topk_merge over columns that carry their own ids (the scores of polus_maxsim_rerank): column c of row r is the
+ * document ids[r*ldi + c] (int32 [rows, n], row stride ldi >= n; rows need no alignment beyond 4 bytes), and a column
+ * whose id is negative is dropped whatever its score.  Everything else is the contract above: NaN and -inf dropped,
+ * score descending by IEEE comparison, ties to the lower ID (not the lower column), (-inf, -1) padding, `init`, exact and
+ * independent of the chunking and of the column order, no float atomics, no workspace.  That guarantee is for rows
+ * whose ids, together with the incoming state's, are distinct.  A duplicate id is not detected: each copy competes as
+ * an entry of its own and may come back beside the others, but a copy whose (score, id) equals the k-th entry held
+ * when its tile is read is passed over, so how many copies of an id return can depend on the chunking and the column
+ * order.  Entries of other ids that rank above every copy are not affected.
+ * Limits (refused before any launch): 1 <= k <= 1024; rows >= 1; n >= 1; lds >= n; ldi >= n; non-null pointers. */
+int polus_topk_merge_ids(const float* scores, long lds, const int32_t* ids, long ldi, int rows, int n,
+                         float* top_val, int32_t* top_id, int k, int init, void* stream);
 
 /* ---- argmax over the last axis (PolusClassifier.inference, polus/models.py:148-150) */
 int polus_argmax(const float* x, long ldx, int32_t* out, int rows, int C, void* stream);

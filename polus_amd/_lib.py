@@ -59,10 +59,12 @@ SIGNATURES = {
     "polus_confusion_matrix": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp]),
     "polus_maxsim_fwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp]),
     "polus_maxsim_scores": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _vp]),
+    "polus_maxsim_rerank": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _l, _vp, _l, _i, _i, _i, _i, _i, _i, _vp]),
     "polus_maxsim_bwd": (_i, [_i, _vp, _vp, _vp, _l, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "polus_l2norm_fwd": (_i, [_i, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "polus_l2norm_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "polus_topk_merge": (_i, [_vp, _l, _i, _i, _c.c_int32, _vp, _vp, _i, _i, _vp]),
+    "polus_topk_merge_ids": (_i, [_vp, _l, _vp, _l, _i, _i, _vp, _vp, _i, _i, _vp]),
     "polus_argmax": (_i, [_vp, _l, _vp, _i, _i, _vp]),
     "polus_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64,
                              _f, _f, _f, _f, _f, _f, _f, _vp, _vp]),

@@ -1,0 +1,258 @@
+// MaxSim re-ranking: every query scores its OWN list of candidate documents (polus_amd/ir/search.py rerank).
+//
+//   score[b, c] = MaxSim(Q[b], D[cand[b, c]])      -inf where cand[b, c] is outside [0, N)
+//
+// polus_maxsim_scores (maxsim.hip) keeps a block of queries per workgroup so that a document leaves L2 once; here a
+// document is read by one query only, so the kernel is a row gather with MFMAs beside it.  One workgroup per
+// (query, block of 4 * dpw candidates), no LDS and no barrier: each wave keeps the query's 16-token tiles as MFMA B
+// fragments in registers and takes its own documents (candidates wave, wave + 4, ...).  It streams a document's
+// 16-token tiles from global memory straight into A fragments with 16-byte loads, the next tile (or the next
+// document's first tile) in flight while the current one is multiplied (two register buffers taken in turn).  The
+// wave's candidate ids are read once (one per lane), and the next document's mask is loaded a whole document ahead;
+// the mask becomes one 16-bit word per tile (ballots), held one tile per lane, so tiles behind the last valid token
+// are never fetched.
+// Queries of more tiles than a wave holds (RES = false) take rounds over the document: the query tiles are loaded
+// again each round and the document's tiles then come from L2.  The two routes are separate instantiations, because
+// one kernel with both keeps two sets of query registers.
+// The arithmetic is that of maxsim_fwd_body: the same fragments and MFMAs in ascending k, a max over document
+// tokens (a value, so order-free), the 16 maxima of a query tile summed by the same xor-shuffle tree, tiles added in
+// ascending order.  A present entry therefore has the bits polus_maxsim_scores gives that (query, document) pair.
+#include "common.h"
+
+namespace {
+
+constexpr int RR_LMAX = 512;            // Lq, Ld limit (maxsim.hip MS_LMAX)
+constexpr int RR_EMAX = 256;            // E limit (multiple of 32)
+constexpr int RR_MAXDPW = 8;            // documents per wave, at most
+
+// query tiles held per wave, as maxsim.hip's MsTiles: the B fragments of UT tiles x KS k-steps within 64 VGPRs
+template <typename T, int KS> struct RrTiles {
+    static constexpr int FR = sizeof(T) == 2 ? 4 : 8;
+    static constexpr int U = (64 / FR) / KS;
+    static constexpr int UT = U < 1 ? 1 : (U > 8 ? 8 : U);
+};
+
+// A fragments of document tile t: lane (i, g) takes row 16 t + i (rows past Ld re-read row Ld - 1), k = 8 g .. 8 g + 7
+// of every 32-wide k-step.  `base` is the document's first row plus this lane's 8 g elements.
+template <typename T, int KS>
+__device__ __forceinline__ void rr_tile_load(Frag<T> (&f)[KS], const unsigned char* base, int t, int i, int Ld) {
+    const unsigned char* p = base + (size_t)min(16 * t + i, Ld - 1) * (32 * KS * sizeof(T));
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) frag_load_row(f[ks], p + ks * 32 * sizeof(T));
+}
+
+// raw document mask, token 64 k + lane in mv[k], for use a whole document later: the loads are unconditional (tokens
+// past Ld re-read token Ld - 1), because a load under a per-lane condition is waited for where it is issued
+__device__ __forceinline__ void rr_mask_load(int (&mv)[8], const int32_t* dm, int lane, int Ld) {
+    if (dm) {                                                 // uniform
+#pragma unroll
+        for (int k = 0; k < 8; ++k) mv[k] = dm[min(64 * k + lane, Ld - 1)];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) mv[k] = 1;
+    }
+}
+
+// tm: lane t < 32 holds the 16 mask bits of document tile t; nvt: tiles up to the last valid token (0 for an absent
+// document)
+__device__ __forceinline__ void rr_mask_pack(const int (&mv)[8], bool present, int lane, int Ld, unsigned& tm, int& nvt) {
+    tm = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const unsigned long long bk = __ballot(present && 64 * k + lane < Ld && mv[k] != 0);
+        if ((lane >> 2) == k) tm = (unsigned)(bk >> (16 * (lane & 3))) & 0xffffu;
+    }
+    const unsigned long long nz = __ballot(tm != 0);
+    nvt = nz ? 64 - (int)__builtin_clzll(nz) : 0;
+}
+
+// B fragments of the query tiles r0 .. r0 + UT - 1 (tiles past the query and rows past Lq re-read a valid row) and
+// whether this lane's token of each tile counts
+template <typename T, int KS, int UT>
+__device__ __forceinline__ void rr_query_load(Frag<T> (&qf)[UT][KS], bool (&qok)[UT], const T* Qb, const int32_t* qm,
+                                              int r0, int nut, int Lq, int i, int g) {
+#pragma unroll
+    for (int u = 0; u < UT; ++u) {
+        const int tok = 16 * (r0 + u) + i;
+        const int tk = min(16 * min(r0 + u, nut - 1) + i, Lq - 1);
+        const unsigned char* p = reinterpret_cast<const unsigned char*>(Qb + (size_t)tk * (32 * KS) + 8 * g);
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) frag_load_row(qf[u][ks], p + ks * 32 * sizeof(T));
+        const bool on = !qm || qm[min(tok, Lq - 1)] != 0;
+        qok[u] = tok < Lq && on;
+    }
+}
+
+// one document tile against the wave's nu query tiles: m[u] = max(m[u], products of the valid rows).  bits: the
+// tile's 16 mask bits shifted to this lane's rows 4 g .. 4 g + 3
+template <typename T, int KS, int UT>
+__device__ __forceinline__ void rr_tile_max(float (&m)[UT], const Frag<T> (&df)[KS], const Frag<T> (&qf)[UT][KS],
+                                            unsigned bits, int nu) {
+#pragma unroll
+    for (int u = 0; u < UT; ++u) {
+        if (u < nu) {                                         // uniform
+            f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) mma16(acc, df[ks], qf[u][ks]);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (((bits >> r) & 1u) && acc[r] > m[u]) m[u] = acc[r];
+        }
+    }
+}
+
+template <typename T, int KS, bool RES>
+__global__ __launch_bounds__(256) void maxsim_rerank_kernel(const T* __restrict__ Q, const T* __restrict__ D,
+                                                            const int32_t* __restrict__ qmask,
+                                                            const int32_t* __restrict__ dmask,
+                                                            const int32_t* __restrict__ cand, long ldc,
+                                                            float* __restrict__ score, long lds, int C, int N, int Lq,
+                                                            int Ld, int dpw) {
+    constexpr int UT = RrTiles<T, KS>::UT;
+    constexpr int E = 32 * KS;
+    constexpr size_t ROWB = E * sizeof(T);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int i = lane & 15, g = lane >> 4;
+    const int b = blockIdx.y;
+    const int c0 = blockIdx.x * 4 * dpw + wave;               // this wave's candidates: c0, c0 + 4, ...
+    if (c0 >= C) return;                                      // wave-uniform; the kernel has no barrier
+    const int nd = min(dpw, (C - c0 + 3) >> 2);
+    const int myc = c0 + 4 * lane;
+    const int idv = cand[(size_t)b * ldc + min(myc, C - 1)];
+    const int ids = lane < nd ? idv : -1;                     // lane l: the wave's l-th candidate id
+
+    const int nut = (Lq + 15) >> 4;                           // query tiles
+    const T* Qb = Q + (size_t)b * Lq * E;
+    const int32_t* qm = qmask ? qmask + (size_t)b * Lq : nullptr;
+    const unsigned char* Dg = reinterpret_cast<const unsigned char*>(D) + 8 * g * sizeof(T);
+
+    const int idc = __builtin_amdgcn_readlane(ids, 0);
+    bool pres = (unsigned)idc < (unsigned)N;                  // absent: nothing of the document is dereferenced
+    const unsigned char* Dc = Dg + (size_t)(pres ? idc : 0) * Ld * ROWB;     // (document 0 stands in for the loads)
+    unsigned tm;
+    int nvt;
+    {
+        int mv[8];
+        rr_mask_load(mv, dmask ? dmask + (size_t)(pres ? idc : 0) * Ld : nullptr, lane, Ld);
+        rr_mask_pack(mv, pres, lane, Ld, tm, nvt);
+    }
+    // Two tile buffers used in turn, two tiles per trip, so that no tile is ever copied (a copy would wait for the
+    // load it copies).  Invariant: at the top of the document loop ta = (document l, tile 0).  A document of an odd
+    // number of tiles takes its last tile twice (from cache; a max is idempotent), which keeps the turns in step.
+    Frag<T> ta[KS], tb[KS];
+    rr_tile_load<T, KS>(ta, Dc, 0, i, Ld);
+    Frag<T> qf[UT][KS];
+    bool qok[UT];
+    if constexpr (RES) rr_query_load        // nut <= UT: the whole query stays in registers
+       <T, KS, UT>(qf, qok, Qb, qm, 0, nut, Lq, i, g);
+
+    for (int l = 0; l < nd; ++l) {
+        // the next document (the last one stands in for its own successor): id known, mask loads issued now, used
+        // after this document's tiles
+        const int idn = __builtin_amdgcn_readlane(ids, min(l + 1, nd - 1));
+        const bool presn = (unsigned)idn < (unsigned)N;
+        const unsigned char* Dn = Dg + (size_t)(presn ? idn : 0) * Ld * ROWB;
+        int mvn[8];
+        rr_mask_load(mvn, dmask ? dmask + (size_t)(presn ? idn : 0) * Ld : nullptr, lane, Ld);
+
+        float s = 0.f;
+        if (nvt > 0) {
+            for (int r0 = 0; r0 < nut; r0 += UT) {
+                if constexpr (!RES) rr_query_load<T, KS, UT>(qf, qok, Qb, qm, r0, nut, Lq, i, g);
+                const int nu = min(UT, nut - r0);
+                const bool last_round = r0 + UT >= nut;
+                float m[UT];
+#pragma unroll
+                for (int u = 0; u < UT; ++u) m[u] = -INFINITY;
+                for (int t = 0; t < nvt; t += 2) {
+                    const int t1 = min(t + 1, nvt - 1);
+                    const bool last = t + 2 >= nvt;
+                    rr_tile_load<T, KS>(tb, Dc, t1, i, Ld);
+                    rr_tile_max<T, KS, UT>(m, ta, qf, __builtin_amdgcn_readlane(tm, t) >> (4 * g), nu);
+                    rr_tile_load<T, KS>(ta, (last && last_round) ? Dn : Dc, last ? 0 : t + 2, i, Ld);
+                    rr_tile_max<T, KS, UT>(m, tb, qf, __builtin_amdgcn_readlane(tm, t1) >> (4 * g), nu);
+                }
+#pragma unroll
+                for (int u = 0; u < UT; ++u) {
+                    if (u < nu) {                             // uniform
+                        float mu = m[u];
+#pragma unroll
+                        for (int o = 16; o <= 32; o <<= 1) {
+                            const float m2 = __shfl_xor(mu, o, 64);
+                            if (m2 > mu) mu = m2;
+                        }
+                        // -inf: no valid document token gave a comparable value (maxsim_fwd_body's "no j")
+                        float contrib = (qok[u] && mu > -INFINITY) ? mu : 0.f;
+#pragma unroll
+                        for (int o = 1; o < 16; o <<= 1) contrib += __shfl_xor(contrib, o, 64);
+                        s += contrib;
+                    }
+                }
+            }
+        } else {
+            rr_tile_load<T, KS>(ta, Dn, 0, i, Ld);            // absent or empty document: nothing was streamed
+        }
+        if (lane == 0) score[(size_t)b * lds + c0 + 4 * l] = pres ? s : -INFINITY;
+        rr_mask_pack(mvn, presn, lane, Ld, tm, nvt);
+        pres = presn;
+        Dc = Dn;
+    }
+}
+
+template <typename T, int KS>
+void rr_launch(const void* Q, const void* D, const int32_t* qm, const int32_t* dm, const int32_t* cand, long ldc,
+               float* score, long lds, int B, int C, int N, int Lq, int Ld, hipStream_t st) {
+    // documents per wave: as many as leave at least 1024 workgroups
+    int dpw = RR_MAXDPW;
+    while (dpw > 1 && (long)B * ((C + 4 * dpw - 1) / (4 * dpw)) < 1024) dpw >>= 1;
+    dim3 grid((unsigned)((C + 4 * dpw - 1) / (4 * dpw)), (unsigned)B);
+    if ((Lq + 15) / 16 <= RrTiles<T, KS>::UT)
+        hipLaunchKernelGGL((maxsim_rerank_kernel<T, KS, true>), grid, dim3(256), 0, st, static_cast<const T*>(Q),
+                           static_cast<const T*>(D), qm, dm, cand, ldc, score, lds, C, N, Lq, Ld, dpw);
+    else
+        hipLaunchKernelGGL((maxsim_rerank_kernel<T, KS, false>), grid, dim3(256), 0, st, static_cast<const T*>(Q),
+                           static_cast<const T*>(D), qm, dm, cand, ldc, score, lds, C, N, Lq, Ld, dpw);
+}
+
+template <typename T>
+void rr_dispatch(int E, const void* Q, const void* D, const int32_t* qm, const int32_t* dm, const int32_t* cand,
+                 long ldc, float* score, long lds, int B, int C, int N, int Lq, int Ld, hipStream_t st) {
+    switch (E / 32) {
+    case 1: rr_launch<T, 1>(Q, D, qm, dm, cand, ldc, score, lds, B, C, N, Lq, Ld, st); break;
+    case 2: rr_launch<T, 2>(Q, D, qm, dm, cand, ldc, score, lds, B, C, N, Lq, Ld, st); break;
+    case 3: rr_launch<T, 3>(Q, D, qm, dm, cand, ldc, score, lds, B, C, N, Lq, Ld, st); break;
+    case 4: rr_launch<T, 4>(Q, D, qm, dm, cand, ldc, score, lds, B, C, N, Lq, Ld, st); break;
+    case 5: rr_launch<T, 5>(Q, D, qm, dm, cand, ldc, score, lds, B, C, N, Lq, Ld, st); break;
+    case 6: rr_launch<T, 6>(Q, D, qm, dm, cand, ldc, score, lds, B, C, N, Lq, Ld, st); break;
+    case 7: rr_launch<T, 7>(Q, D, qm, dm, cand, ldc, score, lds, B, C, N, Lq, Ld, st); break;
+    default: rr_launch<T, 8>(Q, D, qm, dm, cand, ldc, score, lds, B, C, N, Lq, Ld, st); break;
+    }
+}
+
+}  // namespace
+
+extern "C" int polus_maxsim_rerank(int dtype, const void* Q, const void* D, const int32_t* qmask, const int32_t* dmask,
+                                   const int32_t* cand, long ldc, float* score, long lds, int B, int C, int N, int Lq,
+                                   int Ld, int E, void* stream) {
+    const char* what = "polus_maxsim_rerank";
+    POLUS_REQUIRE(dtype == POLUS_F32 || dtype == POLUS_BF16, "%s: unknown dtype %d", what, dtype);
+    POLUS_REQUIRE(E >= 32 && E <= RR_EMAX && E % 32 == 0, "%s: E must be a multiple of 32 in [32, %d] (got %d)", what,
+                  RR_EMAX, E);
+    POLUS_REQUIRE(Lq >= 1 && Lq <= RR_LMAX, "%s: need 1 <= Lq <= %d (got %d)", what, RR_LMAX, Lq);
+    POLUS_REQUIRE(Ld >= 1 && Ld <= RR_LMAX, "%s: need 1 <= Ld <= %d (got %d)", what, RR_LMAX, Ld);
+    POLUS_REQUIRE(B >= 1 && B <= 65535, "%s: need 1 <= B <= 65535 (got %d)", what, B);
+    POLUS_REQUIRE(C >= 1 && C <= 65535, "%s: need 1 <= C <= 65535 (got %d)", what, C);
+    POLUS_REQUIRE(N >= 1, "%s: need 1 <= N <= 2^31 - 1 (got %d)", what, N);
+    POLUS_REQUIRE(ldc >= C, "%s: candidate row stride ldc must be >= C (got %ld < %d)", what, ldc, C);
+    POLUS_REQUIRE(lds >= C, "%s: score row stride lds must be >= C (got %ld < %d)", what, lds, C);
+    POLUS_REQUIRE(Q && D && cand && score, "%s: null pointer", what);
+    POLUS_REQUIRE(polus_aligned16(Q) && polus_aligned16(D), "%s: Q and D must be 16-byte aligned", what);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == POLUS_BF16)
+        rr_dispatch<bf16_t>(E, Q, D, qmask, dmask, cand, ldc, score, lds, B, C, N, Lq, Ld, st);
+    else
+        rr_dispatch<float>(E, Q, D, qmask, dmask, cand, ldc, score, lds, B, C, N, Lq, Ld, st);
+    POLUS_CHECK_LAUNCH(what);
+    return POLUS_OK;
+}

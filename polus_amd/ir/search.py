@@ -5,9 +5,17 @@ with the kernels the trainer uses, keep an exact running top-k on the device, an
     for docs in corpus_batches: index.add(docs)         # {"input_ids", "attention_mask"}
     scores, ids = index.search(queries, k=100)          # f32 / int32 [Q, k] on the device
 
-As in ir/training.py, arithmetic is hand-written HIP (ops.gemm / ops.maxsim_scores, ops.l2norm_fwd, ops.topk_merge);
-torch allocates, views and copies.  Data parallelism: every rank holds the whole index and searches its own shard of
-the queries; ValidationDataCallback gathers the predictions."""
+A token (late-interaction) index scores every document for every query, so its search is linear in the corpus.  Its
+other mode is re-ranking: a cheap first stage proposes candidates per query and MaxSim scores only those.
+
+    scores, ids = index.rerank(queries, candidates, k=100)           # candidates [Q, C], padded with -1
+    two = TwoStageSearch(cls_index, token_index, candidates=1000)    # first.search, then second.rerank
+    scores, ids = two.search(queries, k=100)
+
+As in ir/training.py, arithmetic is hand-written HIP (ops.gemm / ops.maxsim_scores / ops.maxsim_rerank,
+ops.l2norm_fwd, ops.topk_merge); torch allocates, views and copies.  Data parallelism: every rank holds the whole
+index and searches its own shard of the queries; ValidationDataCallback gathers the predictions."""
+import numpy as np
 import torch
 
 from .. import ops
@@ -15,6 +23,7 @@ from ..callbacks import ValidationDataCallback
 from .models import TokenReps
 
 MAX_CHUNK = 65535             # documents per launch: the MaxSim grid's limit, kept on the dot path too
+MAX_K = 1024                  # results per query: the limit of ops.topk_merge
 
 
 class CorpusIndex:
@@ -150,6 +159,90 @@ class CorpusIndex:
                 ops.gemm(qv, self._reps[a:b], s)
             ops.topk_merge(s, top_val, top_id, id0=a, init=(a == 0))
         return top_val, top_id
+
+    def rerank_chunks(self, Q, C):
+        """[(start, stop), ...]: the candidate columns one rerank launch scores: at most 65535, and at most as many as
+        keep the [Q, c] f32 scores within scratch_bytes."""
+        per = min(MAX_CHUNK, self.scratch_bytes // (4 * int(Q)))
+        if per < 1:
+            raise ValueError(f"scratch_bytes = {self.scratch_bytes} does not hold the scores of one candidate for "
+                             f"{Q} queries ({4 * int(Q)} bytes)")
+        return [(s, min(s + per, int(C))) for s in range(0, int(C), per)]
+
+    def rerank(self, queries, candidates, k):
+        """Score every query against its own candidates only (a token index): (scores f32 [Q, k], ids int32 [Q, k]) on
+        the device, the contract of `search` over the documents named in the query's row of `candidates`.
+
+        `candidates` is an integer [Q, C] array of document ids, padded with -1 anywhere in a row.  A host array is
+        checked: an id outside [-1, len(index)) raises ValueError.  A device tensor must be int32 (a wider id could
+        not be narrowed without a look at it) and is taken as it is, values unseen: an id outside [0, len(index)) is
+        absent.  The ids of a row should be distinct: the result is exact and independent of the chunking for
+        distinct ids only.  A repeated id is scored once per copy and may come back more than once; how many of its
+        copies return is not defined (ops.topk_merge).  A row without a candidate returns (-inf, -1)."""
+        if self._n == 0:
+            raise ValueError("the index is empty: add documents before re-ranking")
+        if not self.tokens:
+            raise ValueError("rerank scores token representations (MaxSim); the index holds [CLS] representations, "
+                             "whose search is already one GEMM")
+        q = self.encode_queries(queries)
+        qv = q.values
+        Q = qv.shape[0]
+        if isinstance(candidates, torch.Tensor) and candidates.is_cuda:
+            cand = candidates
+            if cand.dtype != torch.int32:
+                raise ValueError(f"candidates on the device must be int32, the ids a search returns (got {cand.dtype})")
+        else:
+            host = candidates.numpy() if isinstance(candidates, torch.Tensor) else np.asarray(candidates)
+            if host.dtype.kind not in "iu":
+                raise ValueError(f"candidates must be integers (got {host.dtype})")
+            if host.size and (int(host.min()) < -1 or int(host.max()) >= self._n):
+                raise ValueError(f"candidates must lie in [-1, {self._n}) (got {int(host.min())} .. {int(host.max())})")
+            cand = torch.as_tensor(np.ascontiguousarray(host.astype(np.int32))).to(qv.device)
+        if cand.dim() != 2 or cand.shape[0] != Q or cand.shape[1] < 1:
+            raise ValueError(f"candidates must be [{Q}, C] with C >= 1 (got {tuple(cand.shape)})")
+        if cand.stride(1) != 1:
+            cand = cand.contiguous()
+        spans = self.rerank_chunks(Q, cand.shape[1])
+        scratch = torch.empty((Q, max(b - a for a, b in spans)), dtype=torch.float32, device=qv.device)
+        top_val = torch.empty((Q, int(k)), dtype=torch.float32, device=qv.device)
+        top_id = torch.empty((Q, int(k)), dtype=torch.int32, device=qv.device)
+        reps, mask = self._reps[:self._n], self._mask[:self._n]
+        for a, b in spans:
+            s, c = scratch[:, :b - a], cand[:, a:b]
+            ops.maxsim_rerank(qv, reps, q.mask, mask, c, s)
+            ops.topk_merge(s, top_val, top_id, init=(a == 0), ids=c)
+        return top_val, top_id
+
+
+class TwoStageSearch:
+    """Retrieve with a cheap index, re-rank with the token index: `first` is anything with search(queries, k) ->
+    (scores, ids) and add(documents), in practice a [CLS] CorpusIndex over a DualEncoder; `second` is a token
+    CorpusIndex holding the same documents under the same ids; `candidates` is how many documents the first stage
+    proposes per query.  A CorpusIndex returns at most 1024 results per query (the limit of ops.topk_merge), so with
+    one as the first stage `candidates` is at most 1024; another first stage sets its own limit."""
+
+    def __init__(self, first, second, candidates):
+        if int(candidates) < 1:
+            raise ValueError(f"candidates must be >= 1 (got {candidates})")
+        if isinstance(first, CorpusIndex) and int(candidates) > MAX_K:
+            raise ValueError(f"a CorpusIndex as the first stage proposes at most {MAX_K} candidates per query "
+                             f"(got {candidates})")
+        self.first, self.second, self.candidates = first, second, int(candidates)
+
+    def __len__(self):
+        return len(self.second)
+
+    def add(self, documents):
+        """Add a batch to both stages; returns its ids.  The two stages must number it alike."""
+        a, b = self.first.add(documents), self.second.add(documents)
+        if tuple(a.shape) != tuple(b.shape) or not bool((torch.as_tensor(a).to(b.device) == b).all()):
+            raise ValueError("the two stages gave a document batch different ids: they must hold the same documents "
+                             "in the same order")
+        return b
+
+    def search(self, queries, k):
+        """(scores f32 [Q, k], ids int32 [Q, k]): the second stage's ranking of the first stage's candidates."""
+        return self.second.rerank(queries, self.first.search(queries, self.candidates)[1], k)
 
 
 class RetrievalValidationCallback(ValidationDataCallback):

@@ -336,17 +336,42 @@ def maxsim_scores(q, d, qmask, dmask, score):
                                           B, N, Lq, Ld, E, _st()), "polus_maxsim_scores")
 
 
-def topk_merge(scores, top_val, top_id, id0=0, init=False):
+def maxsim_rerank(q, d, qmask, dmask, cand, score):
+    """score[b, c] (f32 [B, C], any row stride) = the MaxSim score of query b and document cand[b, c] (int32 [B, C],
+    any row stride) of the corpus d [N, Ld, E], bit for bit what maxsim_scores gives that pair; -inf where cand[b, c]
+    is outside [0, N) (include/polus_hip.h polus_maxsim_rerank)."""
+    _req_cuda(q, d, qmask, dmask, cand, score)
+    B, Lq, E = q.shape
+    assert d.dim() == 3 and d.shape[2] == E and d.dtype == q.dtype and q.is_contiguous() and d.is_contiguous()
+    N, Ld = d.shape[0], d.shape[1]
+    assert cand.dtype == torch.int32 and cand.dim() == 2 and cand.shape[0] == B and (cand.stride(1) == 1 or cand.shape[1] == 1)
+    C = cand.shape[1]
+    assert score.dtype == torch.float32 and tuple(score.shape) == (B, C) and (score.stride(1) == 1 or C == 1)
+    check(_lib.load().polus_maxsim_rerank(dtype_code(q.dtype), ptr(q), ptr(d), ptr(_maxsim_mask(qmask, B, Lq, "qmask")),
+                                          ptr(_maxsim_mask(dmask, N, Ld, "dmask")), ptr(cand), cand.stride(0), ptr(score),
+                                          score.stride(0), B, C, N, Lq, Ld, E, _st()), "polus_maxsim_rerank")
+
+
+def topk_merge(scores, top_val, top_id, id0=0, init=False, ids=None):
     """Merge scores (f32 [rows, n], any row stride; column c is document id0 + c) into the running top-k state
     top_val f32 / top_id int32 [rows, k]: score descending, ties to the lower id, NaN and -inf dropped, (-inf, -1)
     padding.  init=True starts a new state (the old contents are not read).  Exact and bitwise reproducible
-    (include/polus_hip.h polus_topk_merge)."""
-    _req_cuda(scores, top_val, top_id)
+    (include/polus_hip.h polus_topk_merge).  With `ids` (int32 [rows, n], any row stride; not together with an id0)
+    column c of row r is document ids[r, c] and a negative id drops the column (polus_topk_merge_ids); exact for distinct
+    ids, while of a repeated id an undefined number of copies returns."""
+    _req_cuda(scores, top_val, top_id, ids)
     rows, n = scores.shape
     k = top_val.shape[1]
     assert scores.dtype == torch.float32 and scores.dim() == 2 and (scores.stride(1) == 1 or n == 1)
     assert top_val.dtype == torch.float32 and top_id.dtype == torch.int32 and top_val.is_contiguous() and top_id.is_contiguous()
     assert tuple(top_val.shape) == (rows, k) and tuple(top_id.shape) == (rows, k)
+    if ids is not None:
+        assert int(id0) == 0, "ids and a non-zero id0 exclude each other"
+        assert ids.dtype == torch.int32 and tuple(ids.shape) == (rows, n) and (ids.stride(1) == 1 or n == 1)
+        check(_lib.load().polus_topk_merge_ids(ptr(scores), scores.stride(0), ptr(ids), ids.stride(0), rows, n,
+                                               ptr(top_val), ptr(top_id), k, 1 if init else 0, _st()),
+              "polus_topk_merge_ids")
+        return
     check(_lib.load().polus_topk_merge(ptr(scores), scores.stride(0), rows, n, int(id0), ptr(top_val), ptr(top_id), k,
                                        1 if init else 0, _st()), "polus_topk_merge")
 
