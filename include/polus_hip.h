@@ -334,6 +334,36 @@ int polus_argmax(const float* x, long ldx, int32_t* out, int rows, int C, void* 
 int polus_confusion_matrix(const int32_t* row_idx, const int32_t* col_idx, int64_t n, int C,
                            int32_t* cm, int32_t* rejected, void* stream);
 
+/* ---- BIO span decoding and strict entity matching over tag tensors (bio.hip; polus/ner/bio.py decode_bio with
+ * allow_errors=True as documented, polus/ner/utils.py eval_list_of_entity_sets).  tags int32 [B, S], row stride >= S.
+ * scheme int32 [C]: -1 for an outside tag (O, PAD, ...), else 2 * type + (1 for I-, 0 for B-).  mask int32 [B, S]
+ * (NULL = every token kept): a token with mask 0 is removed before decoding, so the kept tokens on either side of it
+ * are neighbours, and its tag is never interpreted.  For a kept token j with previous kept token p of the row:
+ *   in an entity   iff scheme[tag] != -1; a tag outside [0, C) decodes as outside and is counted as rejected;
+ *   starts one     iff it is B-x, or I-x and p is absent, outside (counted as inside_tag_after_other_tag) or of
+ *                  another type (inside_tag_with_different_entity_type);
+ *   ends one       iff it is in one and the next kept token is absent, outside or a start.
+ * An entity is (row, start column, last column + 1, type); it never continues into the next row.
+ *
+ * polus_bio_entity_counts decodes tags_a and tags_b under one mask and ACCUMULATES (zero them to start)
+ *   counts int32 [T, 3]: per type (entities in both with the same row, start, end and type; entities of a; of b);
+ *   stats int32 [6]: kept tokens, rejected values (each tensor counted on its own), inside_tag_after_other_tag and
+ *                    inside_tag_with_different_entity_type of a, then the same two of b.
+ * polus_bio_spans writes a row's entities as (start, end_exclusive, type) in order of start into spans int32
+ * [B, M, 3] (contiguous) and their number into count int32 [B]: the true number even above M, of which only the first
+ * M are written; slots behind min(count, M) are not touched.  *rejected (device int32, may be null) is accumulated.
+ * One wave per row, lanes over 64 tokens per step, all flags as 64-bit ballot masks with a small carry between steps;
+ * per-type counts through an LDS histogram and integer atomics: exact, independent of launch order; span order from
+ * a popcount prefix of the start mask.  No workspace.  Memory-bound: every tag and mask element is read once.
+ * Limits (refused before any launch): 0 < C <= 256; 0 < T <= 128; S >= 1; M >= 1; row strides >= S; non-null tags,
+ * scheme and outputs.  B == 0 returns POLUS_OK without a launch.  The contents of scheme are the caller's to check
+ * (polus_amd/ner/bio.py check_scheme); a code naming a type >= T decodes as outside. */
+int polus_bio_entity_counts(const int32_t* tags_a, long lda, const int32_t* tags_b, long ldb,
+                            const int32_t* mask, long ldm, const int32_t* scheme, int C, int T, int B, int S,
+                            int32_t* counts, int32_t* stats, void* stream);
+int polus_bio_spans(const int32_t* tags, long ldt, const int32_t* mask, long ldm, const int32_t* scheme, int C,
+                    int B, int S, int32_t* spans, int M, int32_t* count, int32_t* rejected, void* stream);
+
 /* ---- optimizer (optimizer.apply_gradients, polus/training.py:191): Keras Adam /
  * HF AdamWeightDecay over a flat f32 arena.  `seg` is a device table of int64 triples
  * (begin, end, flags) covering [0,n) in chunks; flags bit0 = apply weight decay,

@@ -57,6 +57,8 @@ SIGNATURES = {
     "polus_crf_nll": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
     "polus_crf_viterbi": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
     "polus_confusion_matrix": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp]),
+    "polus_bio_entity_counts": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "polus_bio_spans": (_i, [_vp, _l, _vp, _l, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "polus_maxsim_fwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp]),
     "polus_maxsim_scores": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _vp]),
     "polus_maxsim_rerank": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _l, _vp, _l, _i, _i, _i, _i, _i, _i, _vp]),

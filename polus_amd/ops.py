@@ -433,6 +433,46 @@ def confusion_matrix(row_idx, col_idx, cm, rejected=None):
           "polus_confusion_matrix")
 
 
+def _bio_rows(t, B, S, what):
+    assert t.dtype == torch.int32 and tuple(t.shape) == (B, S) and (t.stride(1) == 1 or S == 1), what
+    return ptr(t), t.stride(0) if B > 1 else S          # the stride of a single row is never used and may be anything
+
+
+def bio_entity_counts(tags_a, tags_b, scheme, counts, stats, mask=None):
+    """Decode both int32 [B, S] tag tensors (any row stride) by the BIO rule under one optional int32 [B, S] mask and add
+    per type (common, n_a, n_b) to counts (int32 [T, 3]) and the decode statistics to stats (int32 [6]); scheme is the
+    int32 [C] table of polus_amd.ner.bio.parse_scheme, on the device (include/polus_hip.h polus_bio_entity_counts)."""
+    _req_cuda(tags_a, tags_b, scheme, counts, stats, mask)
+    assert tags_a.dim() == 2
+    B, S = tags_a.shape
+    pa, lda = _bio_rows(tags_a, B, S, "tags_a")
+    pb, ldb = _bio_rows(tags_b, B, S, "tags_b")
+    pm, ldm = _bio_rows(mask, B, S, "mask") if mask is not None else (None, 0)
+    assert scheme.dtype == torch.int32 and scheme.dim() == 1 and scheme.is_contiguous()
+    assert counts.dtype == torch.int32 and counts.dim() == 2 and counts.shape[1] == 3 and counts.is_contiguous()
+    assert stats.dtype == torch.int32 and stats.numel() == 6 and stats.is_contiguous()
+    check(_lib.load().polus_bio_entity_counts(pa, lda, pb, ldb, pm, ldm, ptr(scheme), scheme.numel(), counts.shape[0],
+                                              B, S, ptr(counts), ptr(stats), _st()), "polus_bio_entity_counts")
+
+
+def bio_spans(tags, scheme, spans, count, mask=None, rejected=None):
+    """A row's entities of the int32 [B, S] tag tensor (any row stride) as (start, end_exclusive, type) in order of
+    start into spans (int32 [B, M, 3]); count (int32 [B]) gets the row's true number of entities, of which the first M
+    are written and the slots behind them left alone; out-of-range tag ids are added to rejected (int32 [1])
+    (include/polus_hip.h polus_bio_spans)."""
+    _req_cuda(tags, scheme, spans, count, mask, rejected)
+    assert tags.dim() == 2
+    B, S = tags.shape
+    pt, ldt = _bio_rows(tags, B, S, "tags")
+    pm, ldm = _bio_rows(mask, B, S, "mask") if mask is not None else (None, 0)
+    assert scheme.dtype == torch.int32 and scheme.dim() == 1 and scheme.is_contiguous()
+    assert spans.dtype == torch.int32 and spans.dim() == 3 and spans.shape[0] == B and spans.shape[2] == 3 and spans.is_contiguous()
+    assert count.dtype == torch.int32 and count.numel() == B and count.is_contiguous()
+    assert rejected is None or (rejected.dtype == torch.int32 and rejected.numel() == 1)
+    check(_lib.load().polus_bio_spans(pt, ldt, pm, ldm, ptr(scheme), scheme.numel(), B, S, ptr(spans), spans.shape[1],
+                                      ptr(count), ptr(rejected), _st()), "polus_bio_spans")
+
+
 def adam_step(p, g, m, v, shadow, seg, n_seg, lr, lr_t, beta1, beta2, eps, weight_decay, grad_scale=1.0,
               clip_scale=None):
     lib = _lib.load()
