@@ -158,7 +158,14 @@ int polus_dense_thin_bwd(int dtype, const void* x, long ldx, int dy_dtype, const
  * head_dim must be 64.  Backward recomputes the probabilities from lse; dqkv [B*S, 3H].
  * drop_p > 0: inverted dropout of the probabilities after the softmax (HF attention_probs_dropout),
  * mask = keep(seed, ((b*A+h)*S+q)*S+key), regenerated in backward.
- * workspace for bwd: B*A*S floats (row dot products dO.O). */
+ * workspace for bwd: B*A*S floats (row dot products dO.O), plus S/256 f32 dQ slabs of [B*S, H] for
+ * S = 512 .. 2048 in whole 256-key blocks (key-resident one-pass backward).  The query is an upper bound over
+ * every kernel route: it depends on the shape alone, not on dtype or on a POLUS_* switch.
+ * polus_attention_route (host only, no HIP call) reports the kernels a call would run under the current
+ * switches: *fwd = 1 LDS-DMA 4 waves, 2 LDS-DMA 8 waves, 3 wide bf16 8 waves, 4 wide f32 4 waves; *bwd = 1 one pass
+ * 4 waves, 2 one pass 8 waves, 3 one pass 64-key blocks, 4 key-resident one block, 5 key-resident with dQ slabs,
+ * 6 two kernels bf16, 7 two kernels f32.  Fails on a bad dtype or S < 1. */
+int polus_attention_route(int dtype, int S, int* fwd, int* bwd);
 int polus_attention_fwd(int dtype, const void* qkv, const int32_t* mask, void* ctx, float* lse,
                         int B, int S, int n_heads, int head_dim, float drop_p, uint32_t seed, void* stream);
 size_t polus_attention_bwd_workspace_bytes(int B, int S, int n_heads);

@@ -35,6 +35,7 @@ SIGNATURES = {
     "polus_dropout": (_i, [_i, _vp, _vp, _i64, _f, _u32, _vp]),
     "polus_dense_bwd_params_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "polus_dense_bwd_params": (_i, [_i, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "polus_attention_route": (_i, [_i, _i, _c.POINTER(_i), _c.POINTER(_i)]),
     "polus_attention_fwd": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _u32, _vp]),
     "polus_attention_bwd_workspace_bytes": (_sz, [_i, _i, _i]),
     "polus_attention_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _u32, _vp, _sz, _vp]),

@@ -1386,66 +1386,106 @@ int check_common(const char* who, int dtype, int B, int S, int A, int hd) {
 }  // namespace
 
 namespace {
-// Forward (WHICH = 0) and dQ (WHICH = 1) kernels: waves per workgroup by sequence length.  bf16:
-// 8 waves (128 keys staged per load + barrier pair) from S >= 96, else 4; 16 waves (a whole
-// 256-token sequence resident, 83 KiB) measures the same as 8 and is reachable with
-// POLUS_ATTN_WAVES=16; f32 (288-byte rows, more registers): always 4.
-template <int WHICH, typename T, int NW>
-int launch_wide_nw(const AttnArgs& a, hipStream_t st) {
-    auto kern = WHICH == 0 ? attn_fwd_kernel<T, NW> : attn_bwd_dq_kernel<T, NW>;
+// ---- Which kernels an attention call runs: attn_fwd_route / attn_bwd_route are the whole decision, the entry points
+// below switch on it.  The codes are the F<n> / B<n> of tests/attention_cases.py, which restates the two functions
+// independently; polus_attention_route exports them and tests/test_attention_cases_cpu.py holds the two together.
+enum AttnFwdRoute { FWD_DMA_4 = 1, FWD_DMA_8, FWD_WIDE_BF16_8, FWD_WIDE_F32_4 };
+enum AttnBwdRoute { BWD_FUSED_4 = 1, BWD_FUSED_8, BWD_Q64_16, BWD_KRES_ONE, BWD_KRES_SLABS, BWD_TWO_BF16, BWD_TWO_F32 };
+
+// bf16 up to FWD_MAX_S keys: the LDS-DMA kernels, 8 waves (128 keys staged per load + barrier pair) from S >= 96, else 4;
+// longer bf16 rows: the wide kernel with 8 waves (S > FWD_MAX_S is never below 96); f32 (288-byte rows, more registers):
+// the wide kernel with 4.
+AttnFwdRoute attn_fwd_route(int dtype, int S) {
+    if (dtype != POLUS_BF16) return FWD_WIDE_F32_4;
+    if (S > FWD_MAX_S) return FWD_WIDE_BF16_8;
+    return S >= 96 ? FWD_DMA_8 : FWD_DMA_4;
+}
+
+// 256-key blocks of a sequence in the key-resident backward's range (whole blocks, S <= 2048), else 0.  From two blocks
+// on, each block writes an f32 dQ slab into the workspace.
+int attn_kres_blocks(int S) { return S % KR_KEYS == 0 && S <= 2048 ? S / KR_KEYS : 0; }
+
+// One-pass forms (bf16, POLUS_ATTN_FUSED): the key-resident kernel for sequences of several 256-key blocks (S = 512: 117 us
+// against 134 us for the two-kernel form at B = 16, 12 heads); at S = 256 the query-resident kernel with 64-key blocks by
+// LDS-DMA is faster (16 waves per CU against 8: 82 us against 90-100 us at B = 64; 80.5 -> 76.8 us over the 32-key-block
+// kernel, bit-identical) unless POLUS_ATTN_BWD_KRES=2 forces the key-resident one (tests, A/B); the 32-key-block kernel at
+// S = 64 / 128 (20.9 against 22.5 us at 32 x 128).  Everything else: the dQ kernel, then the dK/dV kernel.
+AttnBwdRoute attn_bwd_route(int dtype, int S) {
+    if (dtype != POLUS_BF16) return BWD_TWO_F32;
+    if (!polus_cfg().attn_fused) return BWD_TWO_BF16;
+    const int kres = polus_cfg().attn_bwd_kres, nkb = attn_kres_blocks(S);
+    if (kres && nkb > 1) return BWD_KRES_SLABS;
+    if (kres >= 2 && nkb == 1) return BWD_KRES_ONE;
+    if (S == 256) return BWD_Q64_16;
+    if (S == 128) return BWD_FUSED_8;
+    if (S == 64) return BWD_FUSED_4;
+    return BWD_TWO_BF16;
+}
+
+// The part of the kernels' argument block that forward and backward fill alike.
+int attn_args(const char* who, AttnArgs& a, int B, int S, int n_heads, float drop_p, uint32_t seed) {
+    POLUS_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (long)B * n_heads * S * S < (1LL << 32), "%s: bad dropout arguments", who);
+    a.B = B; a.S = S; a.A = n_heads; a.H = n_heads * D; a.scale = 0.125f;
+    a.drop_thresh = drop_p > 0.f ? polus_drop_thresh(drop_p) : 0u; a.drop_seed = seed; a.drop_inv = 1.0f / (1.0f - drop_p); a.dyn = polus_dyn();
+    return POLUS_OK;
+}
+
+// ---- Launchers: grid, LDS size, launch.
+// attn_fwd_kernel / attn_bwd_dq_kernel <T, NW>: one workgroup of NW waves per 16 * NW queries.
+template <auto Kern, typename T, int NW>
+int launch_wide(const char* who, const AttnArgs& a, hipStream_t st) {
     constexpr int QB = 16 * NW;
     const size_t lds = 2 * (size_t)QB * TileCfg<T>::RS + QB * 4;
-    static bool attr_done = false;
-    if (!attr_done && lds > 48 * 1024) {
-        POLUS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_done = true;
-    }
-    dim3 grid((a.S + QB - 1) / QB, a.A, a.B);
-    hipLaunchKernelGGL(kern, grid, dim3(64 * NW), lds, st, a);
-    return POLUS_OK;
+    return polus_launch_lds<Kern>(who, dim3((a.S + QB - 1) / QB, a.A, a.B), dim3(64 * NW), lds, lds, st, a);
 }
 template <int NW>
 int launch_fwd_dma(const AttnArgs& a, hipStream_t st) {
-    auto kern = attn_fwd_dma_kernel<NW>;
+    // the key-bias block grows with S: the limit is raised once, for the longest sequence the kernel takes
+    const size_t lds_max = FWD_RING * FWD_STAGE + (FWD_MAX_S + 64 * NW) * 4;
     const size_t lds = FWD_RING * FWD_STAGE + (size_t)((a.S + 64 * NW - 1) / (64 * NW)) * 64 * NW * 4;
-    static bool attr_done = false;
-    if (!attr_done) {       // once, for the longest sequence the kernel takes (the key-bias block grows with S)
-        POLUS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      FWD_RING * FWD_STAGE + (FWD_MAX_S + 64 * NW) * 4));
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((a.S + 16 * NW - 1) / (16 * NW), a.A, a.B), dim3(64 * NW), lds, st, a);
-    return POLUS_OK;
+    return polus_launch_lds<attn_fwd_dma_kernel<NW>>("polus_attention_fwd", dim3((a.S + 16 * NW - 1) / (16 * NW), a.A, a.B), dim3(64 * NW), lds_max, lds, st, a);
 }
+// one pass, one workgroup per (batch, head), 64-key blocks by LDS-DMA
 template <int NW>
-int launch_q64(const AttnArgs& a, int n_heads, int B, hipStream_t st) {
-    auto kern = attn_bwd_q64_kernel<NW>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        POLUS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, Q64Cfg<NW>::SMEM));
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(n_heads, B), dim3(64 * NW), Q64Cfg<NW>::SMEM, st, a);
-    return POLUS_OK;
+int launch_q64(const AttnArgs& a, hipStream_t st) {
+    return polus_launch_lds<attn_bwd_q64_kernel<NW>>("polus_attention_bwd(one pass, 64-key blocks)", dim3(a.A, a.B), dim3(64 * NW), Q64Cfg<NW>::SMEM, Q64Cfg<NW>::SMEM, st, a);
 }
+// one pass, one workgroup per (batch, head), 32-key blocks; S = 16 * NW
 template <int NW>
-int launch_fused(const AttnArgs& a, int n_heads, int B, size_t lds, hipStream_t st) {
-    auto kern = attn_bwd_fused_kernel<NW>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        POLUS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(n_heads, B), dim3(64 * NW), lds, st, a);
+int launch_fused(const AttnArgs& a, hipStream_t st) {
+    const size_t lds = 2 * (size_t)a.S * TileCfg<bf16_t>::RS + 4 * (size_t)KBLK * TileCfg<bf16_t>::RS + 2 * (size_t)a.S * RSS + (size_t)a.S * 4;
+    return polus_launch_lds<attn_bwd_fused_kernel<NW>>("polus_attention_bwd(fused)", dim3(a.A, a.B), dim3(64 * NW), lds, lds, st, a);
+}
+// key-resident one-pass backward: one workgroup per (256-key block, head, batch); with `slabs` (several blocks) each block
+// leaves its dQ in a slab of its own and a second kernel sums them into dqkv
+int launch_kres(const AttnArgs& a, float* slabs, hipStream_t st) {
+    const int nkb = a.S / KR_KEYS;
+    const size_t lds = KR_OFF_STAT + 2 * (size_t)a.S * sizeof(float);
+    int rc = polus_launch_lds<attn_bwd_kres_kernel>("polus_attention_bwd(key-resident)", dim3(nkb, a.A, a.B), dim3(512), 160 * 1024, lds, st, a, slabs);
+    if (rc != POLUS_OK || !slabs) return rc;
+    hipLaunchKernelGGL(attn_bwd_dq_finish_kernel, dim3(1024), dim3(256), 0, st, slabs, static_cast<bf16_t*>(a.dqkv), (long)a.B * a.S, a.H, nkb);
+    POLUS_CHECK_LAUNCH("polus_attention_bwd(dQ slabs)");
     return POLUS_OK;
 }
-template <int WHICH>
-int launch_wide(int dtype, const AttnArgs& a, hipStream_t st) {
-    if (dtype != POLUS_BF16) return launch_wide_nw<WHICH, float, 4>(a, st);
-    if (a.S >= 96) return launch_wide_nw<WHICH, bf16_t, 8>(a, st);
-    return launch_wide_nw<WHICH, bf16_t, 4>(a, st);
+// two kernels: dQ with NW waves per workgroup, then dK / dV
+template <typename T, int NW>
+int launch_two_kernel(const AttnArgs& a, hipStream_t st) {
+    int rc = launch_wide<attn_bwd_dq_kernel<T, NW>, T, NW>("polus_attention_bwd(dq)", a, st);
+    if (rc != POLUS_OK) return rc;
+    hipLaunchKernelGGL(attn_bwd_dkv_kernel<T>, dim3((a.S + BLK - 1) / BLK, a.A, a.B), dim3(256), 0, st, a);
+    POLUS_CHECK_LAUNCH("polus_attention_bwd(dkv)");
+    return POLUS_OK;
 }
 }  // namespace
+
+// Host only, no HIP call: the kernels polus_attention_fwd / polus_attention_bwd would run (the codes of the two enums above).
+extern "C" int polus_attention_route(int dtype, int S, int* fwd, int* bwd) {
+    POLUS_REQUIRE(dtype == POLUS_F32 || dtype == POLUS_BF16, "polus_attention_route: bad dtype %d", dtype);
+    POLUS_REQUIRE(S >= 1 && fwd && bwd, "polus_attention_route: bad arguments (S=%d)", S);
+    *fwd = attn_fwd_route(dtype, S);
+    *bwd = attn_bwd_route(dtype, S);
+    return POLUS_OK;
+}
 
 extern "C" int polus_attention_fwd(int dtype, const void* qkv, const int32_t* mask, void* ctx, float* lse,
                                    int B, int S, int n_heads, int head_dim, float drop_p, uint32_t seed, void* stream) {
@@ -1454,26 +1494,25 @@ extern "C" int polus_attention_fwd(int dtype, const void* qkv, const int32_t* ma
     POLUS_REQUIRE(qkv && ctx && lse, "polus_attention_fwd: null pointer");
     POLUS_REQUIRE(polus_aligned16(qkv) && polus_aligned16(ctx), "polus_attention_fwd: pointers must be 16-byte aligned");
     AttnArgs a = {};
-    POLUS_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (long)B * n_heads * S * S < (1LL << 32), "polus_attention_fwd: bad dropout arguments");
     a.qkv = qkv; a.mask = mask; a.ctx = ctx; a.lse = lse;
-    a.B = B; a.S = S; a.A = n_heads; a.H = n_heads * D; a.scale = 0.125f;
-    a.drop_thresh = drop_p > 0.f ? polus_drop_thresh(drop_p) : 0u; a.drop_seed = seed; a.drop_inv = 1.0f / (1.0f - drop_p); a.dyn = polus_dyn();
+    if ((rc = attn_args("polus_attention_fwd", a, B, S, n_heads, drop_p, seed))) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int rc2;
-    if (dtype == POLUS_BF16 && S <= FWD_MAX_S)
-        rc2 = S >= 96 ? launch_fwd_dma<8>(a, st) : launch_fwd_dma<4>(a, st);
-    else
-        rc2 = launch_wide<0>(dtype, a, st);
-    if (rc2 != POLUS_OK) return rc2;
-    POLUS_CHECK_LAUNCH("polus_attention_fwd");
-    return POLUS_OK;
+    switch (attn_fwd_route(dtype, S)) {
+        case FWD_DMA_4: return launch_fwd_dma<4>(a, st);
+        case FWD_DMA_8: return launch_fwd_dma<8>(a, st);
+        case FWD_WIDE_BF16_8: return launch_wide<attn_fwd_kernel<bf16_t, 8>, bf16_t, 8>("polus_attention_fwd", a, st);
+        case FWD_WIDE_F32_4: return launch_wide<attn_fwd_kernel<float, 4>, float, 4>("polus_attention_fwd", a, st);
+    }
+    POLUS_FAIL("polus_attention_fwd: no route");
 }
 
-// delta [B, heads, S] for the two-kernel form; sequences of several 256-key blocks add one f32 dQ slab per block
-// ([S / 256][B S][H], key-resident one-pass backward)
+// An upper bound over every route (it takes no dtype and reads no switch; callers size buffers from it): delta [B, heads, S]
+// for the two-kernel form, plus one f32 dQ slab per 256-key block ([S / 256][B S][H]) wherever the key-resident one-pass
+// backward could run with several blocks.
 extern "C" size_t polus_attention_bwd_workspace_bytes(int B, int S, int n_heads) {
     size_t n = (size_t)B * S * n_heads * sizeof(float);
-    if (S > KR_KEYS && S % KR_KEYS == 0 && S <= 2048) n += (size_t)(S / KR_KEYS) * B * S * n_heads * D * sizeof(float);      // (the key-resident kernel's range, polus_attention_bwd)
+    const int nkb = attn_kres_blocks(S);
+    if (nkb > 1) n += (size_t)nkb * B * S * n_heads * D * sizeof(float);
     return n;
 }
 
@@ -1491,61 +1530,17 @@ extern "C" int polus_attention_bwd(int dtype, const void* qkv, const int32_t* ma
     AttnArgs a = {};
     a.qkv = qkv; a.mask = mask; a.ctx = const_cast<void*>(ctx); a.lse = const_cast<float*>(lse); a.dctx = dctx; a.dqkv = dqkv;
     a.delta = static_cast<const float*>(workspace);
-    a.B = B; a.S = S; a.A = n_heads; a.H = n_heads * D; a.scale = 0.125f;
-    POLUS_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (long)B * n_heads * S * S < (1LL << 32), "polus_attention_bwd: bad dropout arguments");
-    a.drop_thresh = drop_p > 0.f ? polus_drop_thresh(drop_p) : 0u; a.drop_seed = seed; a.drop_inv = 1.0f / (1.0f - drop_p); a.dyn = polus_dyn();
+    if ((rc = attn_args("polus_attention_bwd", a, B, S, n_heads, drop_p, seed))) return rc;
     a.debug = polus_cfg().attn_debug;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    dim3 grid((S + BLK - 1) / BLK, n_heads, B);
-    // Which one-pass form: the key-resident kernel for sequences of several 256-key blocks (S = 512: 117 us against 134 us
-    // for the two-kernel form at B = 16, 12 heads); at S = 256 the query-resident kernel below is faster (16 waves per CU
-    // against 8: 82 us against 90-100 us at B = 64) unless POLUS_ATTN_BWD_KRES=2 forces the key-resident one (tests, A/B).
-    const int kres = polus_cfg().attn_bwd_kres;
-    if (dtype == POLUS_BF16 && polus_cfg().attn_fused && kres && S % KR_KEYS == 0 && S <= 2048 && (S > KR_KEYS || kres >= 2)) {
-        // key-resident one-pass backward: one workgroup per (256-key block, head, batch)
-        const int nkb = S / KR_KEYS;
-        float* slabs = nkb > 1 ? static_cast<float*>(workspace) + (size_t)B * S * n_heads : nullptr;
-        const size_t lds = KR_OFF_STAT + 2 * (size_t)S * sizeof(float);
-        static bool attr_done = false;
-        if (!attr_done) {
-            POLUS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kres_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_done = true;
-        }
-        hipLaunchKernelGGL(attn_bwd_kres_kernel, dim3(nkb, n_heads, B), dim3(512), lds, st, a, slabs);
-        POLUS_CHECK_LAUNCH("polus_attention_bwd(key-resident)");
-        if (nkb > 1) {
-            hipLaunchKernelGGL(attn_bwd_dq_finish_kernel, dim3(1024), dim3(256), 0, st, slabs, static_cast<bf16_t*>(dqkv), (long)B * S, a.H, nkb);
-            POLUS_CHECK_LAUNCH("polus_attention_bwd(dQ slabs)");
-        }
-        return POLUS_OK;
+    switch (attn_bwd_route(dtype, S)) {
+        case BWD_FUSED_4: return launch_fused<4>(a, st);
+        case BWD_FUSED_8: return launch_fused<8>(a, st);
+        case BWD_Q64_16: return launch_q64<16>(a, st);
+        case BWD_KRES_ONE: return launch_kres(a, nullptr, st);
+        case BWD_KRES_SLABS: return launch_kres(a, static_cast<float*>(workspace) + (size_t)B * S * n_heads, st);   // past delta
+        case BWD_TWO_BF16: return S >= 96 ? launch_two_kernel<bf16_t, 8>(a, st) : launch_two_kernel<bf16_t, 4>(a, st);
+        case BWD_TWO_F32: return launch_two_kernel<float, 4>(a, st);
     }
-    // query-resident one-pass forms: 64-key blocks by LDS-DMA at S = 256 (80.5 -> 76.8 us at 64 x 256, bit-identical), the 32-key-block
-    // kernel at S = 64 / 128 (20.9 against 22.5 us at 32 x 128); the two were bit-identical where both ran (rounds 2-3)
-    const int fused = polus_cfg().attn_fused;
-    if (dtype == POLUS_BF16 && fused && S == 256) {
-        // one pass, one workgroup per (batch, head), 64-key blocks by LDS-DMA
-        int rc2 = launch_q64<16>(a, n_heads, B, st);
-        if (rc2 != POLUS_OK) return rc2;
-        POLUS_CHECK_LAUNCH("polus_attention_bwd(one pass, 64-key blocks)");
-        return POLUS_OK;
-    }
-    if (dtype == POLUS_BF16 && fused && (S == 64 || S == 128)) {
-        // one pass, one workgroup per (batch, head)
-        const size_t lds = 2 * (size_t)S * TileCfg<bf16_t>::RS + 4 * (size_t)KBLK * TileCfg<bf16_t>::RS + 2 * (size_t)S * RSS + (size_t)S * 4;
-        int rc2 = S == 128 ? launch_fused<8>(a, n_heads, B, lds, st) : launch_fused<4>(a, n_heads, B, lds, st);
-        if (rc2 != POLUS_OK) return rc2;
-        POLUS_CHECK_LAUNCH("polus_attention_bwd(fused)");
-        return POLUS_OK;
-    }
-    if (dtype == POLUS_BF16) {
-        { int rc2 = launch_wide<1>(dtype, a, st); if (rc2 != POLUS_OK) return rc2; }
-        POLUS_CHECK_LAUNCH("polus_attention_bwd(dq)");
-        hipLaunchKernelGGL(attn_bwd_dkv_kernel<bf16_t>, grid, dim3(256), 0, st, a);
-    } else {
-        { int rc2 = launch_wide<1>(dtype, a, st); if (rc2 != POLUS_OK) return rc2; }
-        POLUS_CHECK_LAUNCH("polus_attention_bwd(dq)");
-        hipLaunchKernelGGL(attn_bwd_dkv_kernel<float>, grid, dim3(256), 0, st, a);
-    }
-    POLUS_CHECK_LAUNCH("polus_attention_bwd(dkv)");
-    return POLUS_OK;
+    POLUS_FAIL("polus_attention_bwd: no route");
 }

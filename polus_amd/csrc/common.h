@@ -24,6 +24,21 @@ void polus_set_error(const char* fmt, ...);
 #define POLUS_HIP(call) do { hipError_t e__ = (call); \
     if (e__ != hipSuccess) { polus_set_error("%s failed: %s", #call, hipGetErrorString(e__)); return POLUS_ERR_HIP; } } while (0)
 
+// Launch of a kernel whose dynamic LDS may pass the 48 KiB default: the first call (per kernel, per process) raises the
+// kernel's limit to `lds_max` -- the most any later launch of it asks for -- then every call launches with `lds` bytes.
+// `who` names the entry point in the error message.
+template <auto Kern, typename... A>
+int polus_launch_lds(const char* who, dim3 grid, dim3 block, size_t lds_max, size_t lds, hipStream_t st, const A&... args) {
+    static bool attr_done = false;
+    if (!attr_done) {
+        POLUS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(Kern, grid, block, lds, st, args...);
+    POLUS_CHECK_LAUNCH(who);
+    return POLUS_OK;
+}
+
 static inline size_t polus_dtype_size(int dt) { return dt == POLUS_BF16 ? 2 : 4; }
 static inline bool polus_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 

@@ -279,6 +279,7 @@ int nll_launch(int dtype, const float* pot, const int32_t* tags, const int32_t* 
                const float* sw, float* nll_b, void* dpot, float* dtb, float* ahat, float* m, int B, int S, int C,
                hipStream_t st) {
     using Cfg = CrfCfg<CP>;
+    // not polus_launch_lds: the limit is raised on every call and only above 64 KiB here; folding it in would change when it is set per device
     auto kf = crf_nll_wg_kernel<CP, float>;
     auto kb = crf_nll_wg_kernel<CP, bf16_t>;
     if (dtype == POLUS_BF16) {

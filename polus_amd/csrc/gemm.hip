@@ -256,16 +256,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_epi_kernel(GemmArgs p, cons
 
 template <typename T, bool A_KS, bool B_KS, typename TC, bool VEC, bool DROP = false>
 int launch_v(const GemmArgs& a, dim3 grid, hipStream_t st) {
-    static bool attr_done = false;  // per instantiation
-    auto kern = gemm_kernel<T, A_KS, B_KS, TC, VEC, DROP>;
-    if (!attr_done) {
-        POLUS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES));
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), SMEM_BYTES, st, a);
-    POLUS_CHECK_LAUNCH("polus_gemm");
-    return POLUS_OK;
+    return polus_launch_lds<gemm_kernel<T, A_KS, B_KS, TC, VEC, DROP>>("polus_gemm", grid, dim3(NTHREADS), SMEM_BYTES, SMEM_BYTES, st, a);
 }
 
 template <typename T, bool A_KS, bool B_KS, typename TC>

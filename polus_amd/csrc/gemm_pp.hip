@@ -374,16 +374,9 @@ __global__ __launch_bounds__(NTHR, 2) void gemm_ppp_kernel(GemmArgs p) {
 
 template <int NT, bool DROP, int MODE>
 int launch_ppp(const GemmArgs& a, int ncu, hipStream_t st) {
-    static bool attr_done = false;
-    auto kern = gemm_ppp_kernel<NT, DROP, MODE>;
-    if (!attr_done) {
-        POLUS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, PPPCfg<NT>::SMEM));
-        attr_done = true;
-    }
     const int tiles = ((a.M + TM - 1) / TM) * ((a.N + PPCfg<NT>::TN - 1) / PPCfg<NT>::TN);
-    hipLaunchKernelGGL(kern, dim3(tiles < ncu ? tiles : ncu), dim3(NTHR), PPPCfg<NT>::SMEM, st, a);
-    POLUS_CHECK_LAUNCH("polus_gemm(ping-pong 256-wide, persistent)");
-    return POLUS_OK;
+    return polus_launch_lds<gemm_ppp_kernel<NT, DROP, MODE>>("polus_gemm(ping-pong 256-wide, persistent)", dim3(tiles < ncu ? tiles : ncu), dim3(NTHR),
+                                                             PPPCfg<NT>::SMEM, PPPCfg<NT>::SMEM, st, a);
 }
 template <int NT>
 int launch_ppp_mode(const GemmArgs& a, int mode, int drop, int ncu, hipStream_t st) {
@@ -393,17 +386,8 @@ int launch_ppp_mode(const GemmArgs& a, int mode, int drop, int ncu, hipStream_t 
 template <int NT, bool DROP, int MODE>
 int launch_pp(const GemmArgs& a, hipStream_t st) {
     typedef PPCfg<NT> C;
-    static bool attr_done = false;
-    auto kern = gemm_pp_kernel<NT, DROP, MODE>;
-    if (!attr_done) {
-        POLUS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM));
-        attr_done = true;
-    }
     const int tiles = ((a.M + TM - 1) / TM) * ((a.N + C::TN - 1) / C::TN);
-    hipLaunchKernelGGL(kern, dim3(tiles), dim3(NTHR), C::SMEM, st, a);
-    POLUS_CHECK_LAUNCH("polus_gemm(ping-pong 256-wide)");
-    return POLUS_OK;
+    return polus_launch_lds<gemm_pp_kernel<NT, DROP, MODE>>("polus_gemm(ping-pong 256-wide)", dim3(tiles), dim3(NTHR), C::SMEM, C::SMEM, st, a);
 }
 
 template <int NT>

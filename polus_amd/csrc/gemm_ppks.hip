@@ -412,12 +412,6 @@ int polus_ppks_tiles(int n_out, int n_in) { return ((n_out + TM - 1) / TM) * ((n
 // probs[k]: A = dY (K-strided), B = X (K-strided), C = slab base or dW, ldc, c_split_stride, k_per_split (multiple of
 // 64), colsum_a or null, flags (ACCUM_C when a single slice writes dW); K % 64 == 0; M, N multiples of 8.
 int polus_launch_gemm_ppks_grouped_dw(const GemmArgs* probs, int n, const int* splits, hipStream_t st) {
-    static bool attr_done = false;
-    auto kern = gemm_ppks_grouped_kernel;
-    if (!attr_done) {
-        POLUS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
-        attr_done = true;
-    }
     PPKSGroupArgs ga;
     memset(&ga, 0, sizeof(ga));
     ga.n = n;
@@ -430,9 +424,7 @@ int polus_launch_gemm_ppks_grouped_dw(const GemmArgs* probs, int n, const int* s
         u0 += ga.tiles[k] * splits[k];
     }
     ga.unit0[n] = u0;
-    hipLaunchKernelGGL(kern, dim3(u0), dim3(NTHR), SMEM, st, ga);
-    POLUS_CHECK_LAUNCH("polus_dense_bwd_params_grouped(ping-pong 256x256)");
-    return POLUS_OK;
+    return polus_launch_lds<gemm_ppks_grouped_kernel>("polus_dense_bwd_params_grouped(ping-pong 256x256)", dim3(u0), dim3(NTHR), SMEM, SMEM, st, ga);
 }
 
 int polus_launch_dw_group_reduce(int n, const float* const* slabs, const float* const* cs, float* const* dW, float* const* db,
@@ -493,12 +485,6 @@ int polus_ppks_sk_plan(const int* n_out, const int* n_in, int n, int T, int ncu,
 }
 
 int polus_launch_gemm_ppks_sk(const GemmArgs* probs, const PPKSSKPlan& pl, float* slabs, float* const* cs, hipStream_t st) {
-    static bool attr_done = false;
-    auto kern = gemm_ppks_sk_kernel;
-    if (!attr_done) {
-        POLUS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
-        attr_done = true;
-    }
     PPKSSKArgs ga;
     memset(&ga, 0, sizeof(ga));
     for (int k = 0; k < pl.n; ++k) {
@@ -511,9 +497,7 @@ int polus_launch_gemm_ppks_sk(const GemmArgs* probs, const PPKSSKPlan& pl, float
     ga.slabs = slabs;
     ga.n = pl.n; ga.base = pl.base; ga.kr = pl.kr; ga.krem = pl.krem; ga.R = pl.R; ga.q_units = pl.q_units; ga.rem_units = pl.rem_units;
     ga.slots = pl.slots; ga.n_regular = pl.unit0[pl.n];
-    hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(NTHR), SMEM, st, ga);
-    POLUS_CHECK_LAUNCH("polus_dense_bwd_params_grouped(ping-pong 256x256, stream-K remainder)");
-    return POLUS_OK;
+    return polus_launch_lds<gemm_ppks_sk_kernel>("polus_dense_bwd_params_grouped(ping-pong 256x256, stream-K remainder)", dim3(pl.grid), dim3(NTHR), SMEM, SMEM, st, ga);
 }
 
 int polus_launch_dw_group_reduce_sk(const PPKSSKPlan& pl, const float* slabs, const float* const* cs, float* const* dW, float* const* db,

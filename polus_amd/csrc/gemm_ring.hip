@@ -259,17 +259,8 @@ typedef __attribute__((address_space(1))) void gvoid_t;
 
 template <typename TC, bool A_KS, bool B_KS, bool DROP = false, int MODE = -1>
 int launch_ring(const GemmArgs& a, int splits, hipStream_t st) {
-    static bool attr_done = false;
-    auto kern = gemm_ring_kernel<TC, A_KS, B_KS, DROP, MODE>;
-    if (!attr_done) {
-        POLUS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES));
-        attr_done = true;
-    }
     const int tiles = ((a.M + TM - 1) / TM) * ((a.N + TN - 1) / TN);
-    hipLaunchKernelGGL(kern, dim3(tiles, splits), dim3(NTHR), SMEM_BYTES, st, a);
-    POLUS_CHECK_LAUNCH("polus_gemm(ring 256x128)");
-    return POLUS_OK;
+    return polus_launch_lds<gemm_ring_kernel<TC, A_KS, B_KS, DROP, MODE>>("polus_gemm(ring 256x128)", dim3(tiles, splits), dim3(NTHR), SMEM_BYTES, SMEM_BYTES, st, a);
 }
 
 template <typename TC>
@@ -283,13 +274,6 @@ int launch_layout(const GemmArgs& a, int a_ks, int b_ks, int splits, hipStream_t
 }  // namespace
 
 int polus_launch_gemm_ring_grouped_dw(const GemmArgs* probs, int n, const int* splits, hipStream_t st) {
-    static bool attr_done = false;
-    auto kern = gemm_ring_grouped_kernel<float, true, true>;
-    if (!attr_done) {
-        POLUS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES));
-        attr_done = true;
-    }
     RingGroupArgs ga;
     memset(&ga, 0, sizeof(ga));
     ga.n = n;
@@ -302,9 +286,7 @@ int polus_launch_gemm_ring_grouped_dw(const GemmArgs* probs, int n, const int* s
         t0 += ga.tpad[k] * splits[k];
     }
     ga.wg0[n] = t0;
-    hipLaunchKernelGGL(kern, dim3(t0), dim3(NTHR), SMEM_BYTES, st, ga);
-    POLUS_CHECK_LAUNCH("polus_dense_bwd_params_grouped(ring)");
-    return POLUS_OK;
+    return polus_launch_lds<gemm_ring_grouped_kernel<float, true, true>>("polus_dense_bwd_params_grouped(ring)", dim3(t0), dim3(NTHR), SMEM_BYTES, SMEM_BYTES, st, ga);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -406,16 +388,8 @@ __global__ __launch_bounds__(NTHR, 3) void gemm_ring128_kernel(GemmArgs p) {
 
 template <bool DROP, int MODE>
 int launch_ring128(const GemmArgs& a, hipStream_t st) {
-    static bool attr_done = false;
-    auto kern = gemm_ring128_kernel<DROP, MODE>;
-    if (!attr_done) {
-        POLUS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, r128::SMEM_));
-        attr_done = true;
-    }
     const int tiles = ((a.M + r128::TM_ - 1) / r128::TM_) * ((a.N + r128::TN_ - 1) / r128::TN_);
-    hipLaunchKernelGGL(kern, dim3(tiles), dim3(NTHR), r128::SMEM_, st, a);
-    POLUS_CHECK_LAUNCH("polus_gemm(ring 128 x 128)");
-    return POLUS_OK;
+    return polus_launch_lds<gemm_ring128_kernel<DROP, MODE>>("polus_gemm(ring 128 x 128)", dim3(tiles), dim3(NTHR), r128::SMEM_, r128::SMEM_, st, a);
 }
 
 int polus_launch_gemm_ring128(const GemmArgs& a, int mode, int drop, hipStream_t st) {

@@ -38,6 +38,11 @@ def test_workspace_queries_are_host_only(lib):
     assert lib.polus_gemm_workspace_bytes(768, 768, 1) == 0
     assert lib.polus_gemm_workspace_bytes(768, 768, 4) == 4 * 768 * 768 * 4
     assert lib.polus_attention_bwd_workspace_bytes(2, 128, 12) == 2 * 128 * 12 * 4
+    # delta plus, for S = 512 .. 2048 in whole 256-key blocks, S / 256 f32 dQ slabs of [B S, H]: at the edges of that range
+    attn_ws = {(2, 512, 12): 6340608, (1, 768, 1): 592896, (1, 2048, 1): 4202496, (1, 256, 1): 1024, (1, 2304, 1): 9216,
+               (1, 1088, 1): 4352}
+    for shape, nbytes in attn_ws.items():
+        assert lib.polus_attention_bwd_workspace_bytes(*shape) == nbytes, shape
     # 512 block partials (POLUS_LN_BWD_BLOCKS default: every workgroup resident at once) + room for
     # ceil(512 / 128) second-stage group partials, [3H] f32 each
     assert lib.polus_layernorm_bwd_workspace_bytes(16384, 768) == (512 + 4) * 3 * 768 * 4
@@ -56,6 +61,12 @@ def test_workspace_queries_are_host_only(lib):
         assert lib.polus_dense_bwd_params_grouped_workspace_bytes(4, arr, 16384, 0) == 113357056
     finally:
         ops.set_env("POLUS_DW_STREAMK")
+    # the attention workspace is an upper bound over every route: no switch moves it
+    try:
+        ops.set_env("POLUS_ATTN_FUSED", 0)
+        assert lib.polus_attention_bwd_workspace_bytes(2, 512, 12) == 6340608
+    finally:
+        ops.set_env("POLUS_ATTN_FUSED")
 
 
 def test_argument_validation_happens_on_the_host(lib):

@@ -10,7 +10,12 @@ case's kernel path:
 "Moves by k x the tolerance" means the perturbed output, checked against the unperturbed one by the GPU test's two
 bounds (max-relative and per-element), fails the tighter of them by a factor k.  Attention treats the samples of a
 batch independently, so (a) and (b) recompute only the sample they change.  (mask=None without dropout has nothing to
-perturb.)"""
+perturb.)
+
+The paths those tolerances belong to come from attention_cases.fwd_path / bwd_path, a restatement of the library's
+routing: test_attention_route_matches_cases holds the restatement to the library (polus_attention_route, host only)."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -91,6 +96,39 @@ def test_path_selection_matches_the_host_code():
     assert ac.bwd_path("bf16", 256, kres=0) == "B3" and ac.bwd_path("bf16", 512) == "B5"
     assert ac.bwd_path("bf16", 2304) == "B6" and ac.bwd_path("bf16", 768, fused=0) == "B6"
     assert ac.bwd_path("bf16", 64) == "B1" and ac.bwd_path("bf16", 128) == "B2" and ac.bwd_path("bf16", 200) == "B6"
+
+
+def test_every_path_is_reached_by_a_case():
+    assert set(ac.PATHS) == {c.fwd for c in ac.CASES} | {c.bwd for c in ac.CASES}
+
+
+ROUTE_ENVS = ((), (("POLUS_ATTN_FUSED", 0),), (("POLUS_ATTN_BWD_KRES", 0),), (("POLUS_ATTN_BWD_KRES", 2),),
+              (("POLUS_ATTN_FUSED", 0), ("POLUS_ATTN_BWD_KRES", 2)))
+
+
+@pytest.mark.parametrize("env", ROUTE_ENVS, ids=lambda e: "-".join(f"{k.split('_')[-1].lower()}{v}" for k, v in e) or "default")
+def test_attention_route_matches_cases(env):
+    """polus_attention_route (the library's own routing, no device touched) against fwd_path / bwd_path for both dtypes and
+    every S in 1..2304 (past the key-resident range and the forward's LDS-DMA range), under each switch setting."""
+    from polus_amd import _lib, build, ops
+    build.build(verbose=False)
+    lib = _lib.load()
+    e = dict(env)
+    fused, kres = e.get("POLUS_ATTN_FUSED", 1), e.get("POLUS_ATTN_BWD_KRES", 1)
+    fwd, bwd = ctypes.c_int(), ctypes.c_int()
+    try:
+        for k, v in env:
+            ops.set_env(k, v)
+        for dtype, code in (("bf16", _lib.BF16), ("f32", _lib.F32)):
+            for S in range(1, 2305):
+                assert lib.polus_attention_route(code, S, ctypes.byref(fwd), ctypes.byref(bwd)) == 0
+                want = (int(ac.fwd_path(dtype, S)[1:]), int(ac.bwd_path(dtype, S, fused, kres)[1:]))
+                assert (fwd.value, bwd.value) == want, (dtype, S, env)
+    finally:
+        for k, _ in env:
+            ops.set_env(k)
+    assert lib.polus_attention_route(2, 128, ctypes.byref(fwd), ctypes.byref(bwd)) != 0 and b"bad dtype" in lib.polus_last_error()
+    assert lib.polus_attention_route(_lib.BF16, 0, ctypes.byref(fwd), ctypes.byref(bwd)) != 0
 
 
 def test_edge_keys():
