@@ -102,6 +102,24 @@ int polus_gemm_dropout(int dtype, int a_layout, int b_layout, int c_dtype,
                        const float* bias, const void* resid, long ldr, void* aux, long ldaux,
                        int act, int flags, int split_k, void* workspace, size_t workspace_bytes,
                        float drop_p, uint32_t seed, void* stream);
+/* polus_gemm_route (host only: no HIP call, no pointer dereferenced) reports what polus_gemm (drop_p == 0) or
+ * polus_gemm_dropout (drop_p > 0) would run for these arguments under the current switches.  The pointers count for their
+ * alignment alone (any integer address; NULL = absent for bias / resid / aux).  It fails where those calls fail in validation
+ * (the workspace aside), with the same message.  out[POLUS_GEMM_ROUTE_INTS]:
+ *   [0] kernel: 0 general 128 x 128, 1 ring 256 x 128, 2 ring 128 x 128, 3 ring 256 x 128 with dropout, 4 ping-pong one
+ *       workgroup per tile, 5 ping-pong persistent
+ *   [1] tile width   [2] compile-time epilogue class 0..3 (alpha / bias, activation forward, residual (+ dropout),
+ *       activation backward), -1 = run-time epilogue   [3] dropout   [4] K slices launched
+ *   [5] reduce after the slices: 0 none, 1 plain (alpha, bias, ACCUM_C), 2 with the whole epilogue
+ *   [6] workgroups of the persistent ping-pong form, else 0
+ *   [7] a_vec [8] b_vec: whole aligned 16-byte operand chunks   [9] epi_vec: 4-wide epilogue accesses   [10] epi_vec16: 16-byte
+ *       epilogue accesses   [11] kernel 0 runs its whole-chunk instantiation (a_vec and b_vec) */
+#define POLUS_GEMM_ROUTE_INTS 12
+int polus_gemm_route(int dtype, int a_layout, int b_layout, int c_dtype,
+                     const void* A, long lda, const void* B, long ldb, void* C, long ldc,
+                     int M, int N, int K, float alpha,
+                     const float* bias, const void* resid, long ldr, void* aux, long ldaux,
+                     int act, int flags, int split_k, float drop_p, int* out);
 /* y[i] = keep(seed, i) ? x[i]/(1-p) : 0 (tf.keras.layers.Dropout; apply the same call to dy for backward) */
 int polus_dropout(int dtype, const void* x, void* y, int64_t n, float drop_p, uint32_t seed, void* stream);
 /* mask[i] = 1 if element i is kept (i = idx0 .. idx0+n-1): the reference for every dropout site */
@@ -116,6 +134,11 @@ int polus_dense_bwd_params(int dtype, const void* dY, long lddy, const void* X, 
                            float* dW, long lddw, float* db, int T, int n_out, int n_in,
                            int accumulate, int split_k, void* workspace, size_t workspace_bytes,
                            void* stream);
+
+/* Host only, like polus_gemm_route: out[0] = 1 the ring kernel (column sums on the matrix pipe), 0 polus_gemm + polus_colsum;
+ * out[1] = K slices launched. */
+int polus_dense_bwd_params_route(int dtype, const void* dY, long lddy, const void* X, long ldx,
+                                 float* dW, long lddw, float* db, int T, int n_out, int n_in, int split_k, int* out);
 
 /* The same for up to POLUS_MAX_GROUP (8) Dense layers in ONE launch -- the four weight gradients of
  * an encoder layer (the per-variable MatMul grads tape.gradient emits for one TFBertLayer,
@@ -134,6 +157,11 @@ typedef struct polus_dw_problem {
 size_t polus_dense_bwd_params_grouped_workspace_bytes(int n, const polus_dw_problem* problems, int T, int split_k);
 int polus_dense_bwd_params_grouped(int dtype, int n, const polus_dw_problem* problems, int T, int accumulate,
                                    int split_k, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Host only, like polus_gemm_route: out[0] = 0 one call per problem, 1 ring grouped, 2 ping-pong grouped with an even
+ * split, 3 ping-pong stream-K; out[1] = 1 when every slab reduction and bias gradient of the group takes one launch;
+ * out[2 + k] = K slices of problem k (stream-K: its slots per tile).  out holds 2 + n ints. */
+int polus_dense_bwd_params_grouped_route(int dtype, int n, const polus_dw_problem* problems, int T, int split_k, int* out);
 
 /* ---- Dense layers with at most 8 output units (a token-classification head, polus/ner/models.py:26-44; the last layer of
  * tutorials/classifier_example.py:44-48): y = x W^T + b, W [C][H] row-major in `dtype`.  HBM-bound, one wave per row, no matrix

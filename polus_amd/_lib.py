@@ -31,10 +31,13 @@ SIGNATURES = {
                         _vp, _vp, _l, _vp, _l, _i, _i, _i, _vp, _sz, _vp]),
     "polus_gemm_dropout": (_i, [_i, _i, _i, _i, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _f,
                                 _vp, _vp, _l, _vp, _l, _i, _i, _i, _vp, _sz, _f, _u32, _vp]),
+    "polus_gemm_route": (_i, [_i, _i, _i, _i, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _f,
+                              _vp, _vp, _l, _vp, _l, _i, _i, _i, _f, _c.POINTER(_i)]),
     "polus_dropout_mask": (_i, [_u32, _f, _u32, _i64, _vp, _vp]),
     "polus_dropout": (_i, [_i, _vp, _vp, _i64, _f, _u32, _vp]),
     "polus_dense_bwd_params_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "polus_dense_bwd_params": (_i, [_i, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "polus_dense_bwd_params_route": (_i, [_i, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _c.POINTER(_i)]),
     "polus_attention_route": (_i, [_i, _i, _c.POINTER(_i), _c.POINTER(_i)]),
     "polus_attention_fwd": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _u32, _vp]),
     "polus_attention_bwd_workspace_bytes": (_sz, [_i, _i, _i]),
@@ -82,6 +85,7 @@ SIGNATURES = {
     "polus_transpose_bf16_batched": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "polus_dense_bwd_params_grouped_workspace_bytes": (_sz, [_i, _vp, _i, _i]),
     "polus_dense_bwd_params_grouped": (_i, [_i, _i, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    "polus_dense_bwd_params_grouped_route": (_i, [_i, _i, _vp, _i, _i, _c.POINTER(_i)]),
     "polus_dense_thin_supported": (_i, [_i, _i, _i]),
     "polus_dense_thin_fwd": (_i, [_i, _vp, _l, _vp, _l, _vp, _i, _vp, _l, _i, _i, _i, _vp]),
     "polus_dense_thin_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i]),

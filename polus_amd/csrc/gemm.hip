@@ -469,12 +469,22 @@ static int launch_splitk_reduce(int c_dtype, const float* slabs, int splits, int
     return POLUS_OK;
 }
 
-static int gemm_impl(int dtype, int a_layout, int b_layout, int c_dtype,
+// A validated polus_gemm(_dropout) call: the kernels' argument block (but for k_per_split and partial, which the launch
+// derives from the route), the route, and the K tiling the route was asked with.
+struct GemmPlan {
+    GemmArgs a;
+    GemmRoute r;
+    int bk, nkt, kt_per_split;
+};
+
+// Validates a call and decides its route; launches nothing and dereferences no pointer (polus_gemm_route hands it made-up
+// addresses).  ws_bytes: the caller's workspace size, null where there is no workspace to check (the route query).
+static int gemm_plan(int dtype, int a_layout, int b_layout, int c_dtype,
                      const void* A, long lda, const void* B, long ldb, void* C, long ldc,
                      int M, int N, int K, float alpha,
                      const float* bias, const void* resid, long ldr, void* aux, long ldaux,
-                     int act, int flags, int split_k, void* workspace, size_t workspace_bytes,
-                     float drop_p, uint32_t seed, void* stream) {
+                     int act, int flags, int split_k, const void* workspace, const size_t* ws_bytes,
+                     float drop_p, uint32_t seed, GemmPlan* p) {
     POLUS_REQUIRE(dtype == POLUS_F32 || dtype == POLUS_BF16, "polus_gemm: bad dtype %d", dtype);
     POLUS_REQUIRE(c_dtype == POLUS_F32 || c_dtype == dtype, "polus_gemm: c_dtype must be f32 or dtype");
     POLUS_REQUIRE(M > 0 && N > 0 && K > 0, "polus_gemm: empty problem M=%d N=%d K=%d", M, N, K);
@@ -496,14 +506,15 @@ static int gemm_impl(int dtype, int a_layout, int b_layout, int c_dtype,
         const bool epi = resid || aux || (flags & (POLUS_GEMM_ACT_FWD | POLUS_GEMM_ACT_BWD | POLUS_GEMM_DROPOUT));
         POLUS_REQUIRE(!epi || (dtype == POLUS_BF16 && c_dtype == POLUS_BF16 && both_kc && !(flags & POLUS_GEMM_ACCUM_C)),
                       "polus_gemm: split_k with a residual / activation / dropout epilogue needs bf16 K-contiguous operands and a bf16 C");
-        if (!workspace || workspace_bytes < polus_gemm_workspace_bytes(M, N, split_k)) {
-            polus_set_error("polus_gemm: workspace %zu < %zu", workspace_bytes, polus_gemm_workspace_bytes(M, N, split_k));
+        if (ws_bytes && (!workspace || *ws_bytes < polus_gemm_workspace_bytes(M, N, split_k))) {
+            polus_set_error("polus_gemm: workspace %zu < %zu", *ws_bytes, polus_gemm_workspace_bytes(M, N, split_k));
             return POLUS_ERR_WORKSPACE;
         }
     }
     // forward Dense only: K-contiguous operands, C in the compute dtype
     POLUS_REQUIRE(!(flags & POLUS_GEMM_DROPOUT) || (both_kc && c_dtype == dtype), "polus_gemm_dropout: needs K-contiguous operands and c_dtype == dtype");
-    GemmArgs a = {};
+    GemmArgs& a = p->a;
+    a = GemmArgs{};
     a.A = A; a.B = B; a.C = C; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
     a.M = M; a.N = N; a.K = K; a.alpha = alpha;
     a.bias = bias; a.resid = resid; a.ldr = ldr; a.aux = aux; a.ldaux = ldaux;
@@ -530,12 +541,31 @@ static int gemm_impl(int dtype, int a_layout, int b_layout, int c_dtype,
     const int kt_per_split = (nkt + split_k - 1) / split_k;
     const bool c_is_f32 = c_dtype == POLUS_F32;
     const int a_ks = a_layout == POLUS_K_STRIDED, b_ks = b_layout == POLUS_K_STRIDED;
-    const GemmRoute r = gemm_route(a, dtype, c_is_f32, a_ks, b_ks, (nkt + kt_per_split - 1) / kt_per_split);
+    p->r = gemm_route(a, dtype, c_is_f32, a_ks, b_ks, (nkt + kt_per_split - 1) / kt_per_split);
+    p->bk = bk; p->nkt = nkt; p->kt_per_split = kt_per_split;
+    return POLUS_OK;
+}
+
+static int gemm_impl(int dtype, int a_layout, int b_layout, int c_dtype,
+                     const void* A, long lda, const void* B, long ldb, void* C, long ldc,
+                     int M, int N, int K, float alpha,
+                     const float* bias, const void* resid, long ldr, void* aux, long ldaux,
+                     int act, int flags, int split_k, void* workspace, size_t workspace_bytes,
+                     float drop_p, uint32_t seed, void* stream) {
+    GemmPlan pl;
+    int rc = gemm_plan(dtype, a_layout, b_layout, c_dtype, A, lda, B, ldb, C, ldc, M, N, K, alpha, bias, resid, ldr, aux, ldaux,
+                       act, flags, split_k, workspace, &workspace_bytes, drop_p, seed, &pl);
+    if (rc != POLUS_OK) return rc;
+    GemmArgs& a = pl.a;
+    const GemmRoute& r = pl.r;
+    const int bk = pl.bk, nkt = pl.nkt, kt_per_split = pl.kt_per_split;
+    const bool c_is_f32 = c_dtype == POLUS_F32;
+    const int a_ks = a_layout == POLUS_K_STRIDED, b_ks = b_layout == POLUS_K_STRIDED;
     if (r.splits > 1) { a.k_per_split = kt_per_split * bk; a.partial = static_cast<float*>(workspace); }
     else a.k_per_split = r.kernel == GEMM_V1 ? nkt * bk : ((K + 31) / 32) * 32;
 
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int rc = POLUS_ERR_INVALID;
+    rc = POLUS_ERR_INVALID;
     switch (r.kernel) {
         case GEMM_V1: rc = launch_v1(dtype, c_dtype, a_layout, b_layout, a, r.drop, r.splits, st); break;
         case GEMM_RING:
@@ -580,6 +610,34 @@ extern "C" int polus_gemm_dropout(int dtype, int a_layout, int b_layout, int c_d
     if (drop_p > 0.0f) flags |= POLUS_GEMM_DROPOUT; else flags &= ~POLUS_GEMM_DROPOUT;
     return gemm_impl(dtype, a_layout, b_layout, c_dtype, A, lda, B, ldb, C, ldc, M, N, K, alpha, bias, resid, ldr,
                      aux, ldaux, act, flags, split_k, workspace, workspace_bytes, drop_p, seed, stream);
+}
+
+// Host only, no HIP call: what polus_gemm (drop_p == 0) or polus_gemm_dropout (drop_p > 0) would decide for these arguments
+// under the current switches.  The pointers count for their alignment alone.  Fails where those calls fail in validation.
+extern "C" int polus_gemm_route(int dtype, int a_layout, int b_layout, int c_dtype,
+                                const void* A, long lda, const void* B, long ldb, void* C, long ldc,
+                                int M, int N, int K, float alpha,
+                                const float* bias, const void* resid, long ldr, void* aux, long ldaux,
+                                int act, int flags, int split_k, float drop_p, int* out) {
+    POLUS_REQUIRE(out, "polus_gemm_route: null out");
+    if (drop_p > 0.0f) {
+        POLUS_REQUIRE(drop_p < 1.0f, "polus_gemm_dropout: need 0 <= p < 1 (got %f)", drop_p);
+        POLUS_REQUIRE((long)M * N < (1LL << 32), "polus_gemm_dropout: M*N must fit 32 bits");
+        flags |= POLUS_GEMM_DROPOUT;
+    } else {
+        POLUS_REQUIRE(drop_p == 0.0f, "polus_gemm_dropout: need 0 <= p < 1 (got %f)", drop_p);
+        POLUS_REQUIRE(!(flags & POLUS_GEMM_DROPOUT), "polus_gemm: use polus_gemm_dropout for POLUS_GEMM_DROPOUT");
+    }
+    GemmPlan pl;
+    int rc = gemm_plan(dtype, a_layout, b_layout, c_dtype, A, lda, B, ldb, C, ldc, M, N, K, alpha, bias, resid, ldr, aux, ldaux,
+                       act, flags, split_k, nullptr, nullptr, drop_p, 0u, &pl);
+    if (rc != POLUS_OK) return rc;
+    const GemmRoute& r = pl.r;
+    const GemmArgs& a = pl.a;
+    const int v[POLUS_GEMM_ROUTE_INTS] = {r.kernel, r.tn, r.mode, r.drop, r.splits, r.reduce, r.persist_cus,
+                                          a.a_vec, a.b_vec, a.epi_vec, a.epi_vec16, r.kernel == GEMM_V1 && a.a_vec && a.b_vec};
+    for (int i = 0; i < POLUS_GEMM_ROUTE_INTS; ++i) out[i] = v[i];
+    return POLUS_OK;
 }
 
 // ---- Dense backward for the parameters: dW = dY^T X (+)= and db = column sums of dY, one pass
@@ -630,6 +688,15 @@ static void dw_dest(GemmArgs& a, const polus_dw_problem& q, void* slabs, int acc
     }
 }
 
+// Which form a polus_dense_bwd_params call takes: the ring kernel with the bias gradient on the matrix pipe, or
+// polus_gemm + polus_colsum.
+static bool dw_use_ring(int dtype, const void* dY, long lddy, const void* X, long ldx, const float* db, int n_out, int n_in) {
+    const size_t es = polus_dtype_size(dtype);
+    const bool vec = polus_aligned16(dY) && polus_aligned16(X) && ((lddy * es) % 16 == 0) && ((ldx * es) % 16 == 0) &&
+                     (n_out % (16 / es) == 0) && (n_in % (16 / es) == 0);
+    return dtype == POLUS_BF16 && vec && n_out >= 256 && n_in >= 128 && db != nullptr && !polus_cfg().gemm_v1;
+}
+
 extern "C" int polus_dense_bwd_params(int dtype, const void* dY, long lddy, const void* X, long ldx,
                                       float* dW, long lddw, float* db, int T, int n_out, int n_in,
                                       int accumulate, int split_k, void* workspace, size_t workspace_bytes,
@@ -640,16 +707,13 @@ extern "C" int polus_dense_bwd_params(int dtype, const void* dY, long lddy, cons
     size_t need = polus_dense_bwd_params_workspace_bytes(T, n_out, n_in, split_k);
     if (!workspace || workspace_bytes < need) { polus_set_error("polus_dense_bwd_params: workspace %zu < %zu", workspace_bytes, need); return POLUS_ERR_WORKSPACE; }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t es = polus_dtype_size(dtype);
     const int bk = dtype == POLUS_BF16 ? 64 : 32;
     int nkt = (T + bk - 1) / bk;
     if (split_k > nkt) split_k = nkt;
     const size_t slab_bytes = split_k > 1 ? (((size_t)split_k * n_out * n_in * sizeof(float) + 255) / 256) * 256 : 0;
     unsigned char* ws = static_cast<unsigned char*>(workspace);
     float* cs_ws = reinterpret_cast<float*>(ws + slab_bytes);
-    const bool vec = polus_aligned16(dY) && polus_aligned16(X) && ((lddy * es) % 16 == 0) && ((ldx * es) % 16 == 0) &&
-                     (n_out % (16 / es) == 0) && (n_in % (16 / es) == 0);
-    const bool ring = dtype == POLUS_BF16 && vec && n_out >= 256 && n_in >= 128 && db != nullptr && !polus_cfg().gemm_v1;
+    const bool ring = dw_use_ring(dtype, dY, lddy, X, ldx, db, n_out, n_in);
     if (!ring) {
         int rc = polus_gemm(dtype, POLUS_K_STRIDED, POLUS_K_STRIDED, POLUS_F32, dY, lddy, X, ldx, dW, lddw, n_out, n_in, T,
                             1.0f, nullptr, nullptr, 0, nullptr, 0, 0, accumulate ? POLUS_GEMM_ACCUM_C : 0, split_k,
@@ -670,6 +734,30 @@ extern "C" int polus_dense_bwd_params(int dtype, const void* dY, long lddy, cons
         if (rc != POLUS_OK) return rc;
     }
     return launch_colsum_splits(cs_ws, splits, n_out, db, accumulate ? 1 : 0, "polus_dense_bwd_params(colsum)", st);
+}
+
+// Host only, no HIP call: out[0] = 1 the ring kernel, 0 the fallback (polus_gemm + polus_colsum); out[1] = K slices launched.
+// Fails where polus_dense_bwd_params fails in validation (the workspace aside).
+extern "C" int polus_dense_bwd_params_route(int dtype, const void* dY, long lddy, const void* X, long ldx,
+                                            float* dW, long lddw, float* db, int T, int n_out, int n_in, int split_k, int* out) {
+    POLUS_REQUIRE(out, "polus_dense_bwd_params_route: null out");
+    POLUS_REQUIRE(dY && X && dW, "polus_dense_bwd_params: null pointer");
+    POLUS_REQUIRE(T > 0 && n_out > 0 && n_in > 0, "polus_dense_bwd_params: bad shape");
+    if (split_k < 1) split_k = 1;
+    const int bk = dtype == POLUS_BF16 ? 64 : 32;
+    const int nkt = (T + bk - 1) / bk;
+    if (split_k > nkt) split_k = nkt;
+    if (!dw_use_ring(dtype, dY, lddy, X, ldx, db, n_out, n_in)) {
+        GemmPlan pl;
+        int rc = gemm_plan(dtype, POLUS_K_STRIDED, POLUS_K_STRIDED, POLUS_F32, dY, lddy, X, ldx, dW, lddw, n_out, n_in, T, 1.0f,
+                           nullptr, nullptr, 0, nullptr, 0, 0, 0, split_k, nullptr, nullptr, 0.0f, 0u, &pl);
+        if (rc != POLUS_OK) return rc;
+        out[0] = 0; out[1] = pl.r.splits;
+        return POLUS_OK;
+    }
+    const int kt_per_split = (nkt + split_k - 1) / split_k;
+    out[0] = 1; out[1] = (nkt + kt_per_split - 1) / kt_per_split;
+    return POLUS_OK;
 }
 
 // ---- The same for several Dense layers at once (all four of an encoder layer): one ring launch
@@ -793,6 +881,7 @@ struct DwGroupOut {
     long lddw[POLUS_MAX_GROUP]; int n_out[POLUS_MAX_GROUP], n_in[POLUS_MAX_GROUP];
     bool aligned;     // every dW allows the reductions' 16-byte accesses
 };
+static bool dw_reduce_aligned(const polus_dw_problem& q) { return (q.n_in % 4 == 0) && (q.lddw % 4 == 0) && polus_aligned16(q.dW); }
 // slab_off: null where the slabs are not per problem (stream-K) -- else problem k has slabs iff eff[k] > 1
 static DwGroupOut dw_group_out(int n, const polus_dw_problem* pr, unsigned char* ws, const size_t* cs_off, const size_t* slab_off, const int* eff) {
     DwGroupOut o;
@@ -802,13 +891,13 @@ static DwGroupOut dw_group_out(int n, const polus_dw_problem* pr, unsigned char*
         o.slabs[k] = slab_off && eff[k] > 1 ? reinterpret_cast<const float*>(ws + slab_off[k]) : nullptr;
         o.cs[k] = q.db ? reinterpret_cast<float*>(ws + cs_off[k]) : nullptr;
         o.dW[k] = q.dW; o.db[k] = q.db; o.lddw[k] = q.lddw; o.n_out[k] = q.n_out; o.n_in[k] = q.n_in;
-        o.aligned = o.aligned && (q.n_in % 4 == 0) && (q.lddw % 4 == 0) && polus_aligned16(q.dW);
+        o.aligned = o.aligned && dw_reduce_aligned(q);
     }
     return o;
 }
 
-extern "C" int polus_dense_bwd_params_grouped(int dtype, int n, const polus_dw_problem* problems, int T, int accumulate,
-                                              int split_k, void* workspace, size_t workspace_bytes, void* stream) {
+// Validates a grouped dW call; *ring: one grouped launch (every problem fits the ring kernel), else one call per problem.
+static int grouped_dw_check(int dtype, int n, const polus_dw_problem* problems, int T, bool* ring_out) {
     POLUS_REQUIRE(problems && n >= 1 && n <= POLUS_MAX_GROUP && T > 0, "polus_dense_bwd_params_grouped: bad arguments");
     const size_t es = polus_dtype_size(dtype);
     bool ring = dtype == POLUS_BF16 && !polus_cfg().gemm_v1 && !polus_cfg().dw_ungrouped;
@@ -818,6 +907,55 @@ extern "C" int polus_dense_bwd_params_grouped(int dtype, int n, const polus_dw_p
         ring = ring && polus_aligned16(q.dY) && polus_aligned16(q.X) && ((q.lddy * es) % 16 == 0) && ((q.ldx * es) % 16 == 0) &&
                (q.n_out % 8 == 0) && (q.n_in % 8 == 0) && q.n_out >= 256 && q.n_in >= 128;
     }
+    *ring_out = ring;
+    return POLUS_OK;
+}
+
+// Host only, no HIP call: out[0] = the kernel of a grouped dW call (0 one call per problem, 1 ring grouped, 2 ping-pong
+// grouped with an even split, 3 ping-pong stream-K), out[1] = 1 when the slab reductions and bias gradients of the group
+// take one launch, out[2 + k] = K slices of problem k (stream-K: its slots per tile).
+extern "C" int polus_dense_bwd_params_grouped_route(int dtype, int n, const polus_dw_problem* problems, int T, int split_k, int* out) {
+    POLUS_REQUIRE(out, "polus_dense_bwd_params_grouped_route: null out");
+    bool ring;
+    int rc = grouped_dw_check(dtype, n, problems, T, &ring);
+    if (rc != POLUS_OK) return rc;
+    GroupedDwPlan pl;
+    grouped_dw_plan(n, problems, T, split_k, &pl);
+    if (!ring) {
+        out[0] = 0; out[1] = 0;
+        for (int k = 0; k < n; ++k) {
+            const polus_dw_problem& q = problems[k];
+            int one[2];
+            if (q.db) rc = polus_dense_bwd_params_route(dtype, q.dY, q.lddy, q.X, q.ldx, q.dW, q.lddw, q.db, T, q.n_out, q.n_in, pl.splits[k], one);
+            else {
+                GemmPlan gp;
+                rc = gemm_plan(dtype, POLUS_K_STRIDED, POLUS_K_STRIDED, POLUS_F32, q.dY, q.lddy, q.X, q.ldx, q.dW, q.lddw, q.n_out, q.n_in, T,
+                               1.0f, nullptr, nullptr, 0, nullptr, 0, 0, 0, pl.splits[k], nullptr, nullptr, 0.0f, 0u, &gp);
+                one[1] = gp.r.splits;
+            }
+            if (rc != POLUS_OK) return rc;
+            out[2 + k] = one[1];
+        }
+        return POLUS_OK;
+    }
+    bool aligned = true;
+    for (int k = 0; k < n; ++k) aligned = aligned && dw_reduce_aligned(problems[k]);
+    if (pl.sk && aligned) {
+        out[0] = 3; out[1] = 1;
+        for (int k = 0; k < n; ++k) out[2 + k] = pl.skp.slots;
+        return POLUS_OK;
+    }
+    out[0] = pl.pp ? 2 : 1;
+    out[1] = polus_cfg().dw_fused_reduce && aligned;
+    for (int k = 0; k < n; ++k) out[2 + k] = pl.eff[k];
+    return POLUS_OK;
+}
+
+extern "C" int polus_dense_bwd_params_grouped(int dtype, int n, const polus_dw_problem* problems, int T, int accumulate,
+                                              int split_k, void* workspace, size_t workspace_bytes, void* stream) {
+    bool ring;
+    int rc0 = grouped_dw_check(dtype, n, problems, T, &ring);
+    if (rc0 != POLUS_OK) return rc0;
     GroupedDwPlan pl;
     grouped_dw_plan(n, problems, T, split_k, &pl);
     if (!workspace || workspace_bytes < pl.bytes) { polus_set_error("polus_dense_bwd_params_grouped: workspace %zu < %zu", workspace_bytes, pl.bytes); return POLUS_ERR_WORKSPACE; }

@@ -3,6 +3,9 @@
 torch is the allocator and the stream owner only.  Every function launches on torch's
 current stream and returns without synchronising.
 """
+import collections
+import ctypes
+
 import torch
 
 from . import _lib
@@ -148,6 +151,62 @@ def gemm(a, b, out, *, a_layout=K_CONTIG, b_layout=K_CONTIG, M=None, N=None, K=N
         kind = "fwd" if (a_layout == K_CONTIG and b_layout == K_CONTIG) else ("dx" if a_layout == K_CONTIG else "dw")
         prof.append((kind, 2.0 * M * N * K, e0, e1))
     return out
+
+
+# The host-only route reports (include/polus_hip.h): what the call with the same tensors and keywords would run.
+GEMM_KERNELS = ("v1", "ring", "ring128", "ring_drop", "pp", "pp_persist")
+GEMM_REDUCES = ("none", "plain", "epi")
+DW_GROUPED_KERNELS = ("one_by_one", "ring_grouped", "pp_grouped", "pp_streamk")
+GemmRoute = collections.namedtuple("GemmRoute", "kernel tn mode drop splits reduce persist_cus a_vec b_vec epi_vec epi_vec16 v1_vec")
+DwRoute = collections.namedtuple("DwRoute", "ring splits")
+DwGroupedRoute = collections.namedtuple("DwGroupedRoute", "kernel fused_reduce eff")
+
+
+def gemm_route(a, b, out, *, a_layout=K_CONTIG, b_layout=K_CONTIG, M=None, N=None, K=None, alpha=1.0,
+               bias=None, resid=None, aux=None, act=None, flags=0, split_k=1, drop_p=0.0, seed=0):
+    """The route `gemm` takes with these arguments under the current switches (polus_gemm_route); launches nothing."""
+    m_, k_ = a.shape if a_layout == K_CONTIG else a.shape[::-1]
+    n_ = b.shape[0] if b_layout == K_CONTIG else b.shape[1]
+    M, N, K = (m_ if M is None else M), (n_ if N is None else N), (k_ if K is None else K)
+    if split_k == "auto":
+        split_k = 1
+        if (a.dtype == torch.bfloat16 and out.dtype == a.dtype and a_layout == K_CONTIG and b_layout == K_CONTIG
+                and not (flags & GEMM_ACCUM_C)):
+            split_k = int(_lib.load().polus_gemm_auto_split(M, N, K))
+    r = (ctypes.c_int * 12)()
+    check(_lib.load().polus_gemm_route(
+        dtype_code(a.dtype), a_layout, b_layout, dtype_code(out.dtype),
+        ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(out), out.stride(0), M, N, K, float(alpha), ptr(bias),
+        ptr(resid), resid.stride(0) if resid is not None else 0, ptr(aux), aux.stride(0) if aux is not None else 0,
+        ACT_CODES[act] if not isinstance(act, int) else act, flags, split_k, float(drop_p), r), "polus_gemm_route")
+    v = list(r)
+    return GemmRoute(GEMM_KERNELS[v[0]], v[1], v[2], v[3], v[4], GEMM_REDUCES[v[5]], v[6], *map(bool, v[7:]))
+
+
+def dense_bwd_params_route(dy, x, dw, db, accumulate=False, split_k=1):
+    """The form `dense_bwd_params` takes with these arguments (polus_dense_bwd_params_route); launches nothing."""
+    r = (ctypes.c_int * 2)()
+    check(_lib.load().polus_dense_bwd_params_route(dtype_code(dy.dtype), ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(dw), dw.stride(0),
+                                                   ptr(db), dy.shape[0], dy.shape[1], x.shape[1], split_k, r),
+          "polus_dense_bwd_params_route")
+    return DwRoute(bool(r[0]), r[1])
+
+
+def _dw_problems(problems):
+    arr = (_lib.DwProblem * len(problems))()
+    for k, (dy, x, dw, db) in enumerate(problems):
+        arr[k] = _lib.DwProblem(ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(dw), dw.stride(0), ptr(db), dy.shape[1], x.shape[1])
+    return arr
+
+
+def dense_bwd_params_grouped_route(problems, accumulate=False, split_k=1):
+    """The kernel `dense_bwd_params_grouped` runs for these problems (polus_dense_bwd_params_grouped_route); launches nothing."""
+    n = len(problems)
+    r = (ctypes.c_int * (2 + n))()
+    check(_lib.load().polus_dense_bwd_params_grouped_route(dtype_code(problems[0][0].dtype), n, _dw_problems(problems),
+                                                           problems[0][0].shape[0], int(split_k), r),
+          "polus_dense_bwd_params_grouped_route")
+    return DwGroupedRoute(DW_GROUPED_KERNELS[r[0]], bool(r[1]), tuple(r[2:2 + n]))
 
 
 def attention_fwd(qkv, mask, ctx, lse, B, S, n_heads, drop_p=0.0, seed=0):

@@ -766,7 +766,7 @@ def test_dense_bwd_params_grouped_streamk(ops, T, shapes):
 
 
 @pytest.mark.parametrize("tn", [256, 192])
-@pytest.mark.parametrize("M,N,K", [(1024, 3072, 768), (1280, 2304, 320), (1000, 1500, 64), (2048, 3072, 768), (2000, 3072, 320)])
+@pytest.mark.parametrize("M,N,K", [(1024, 3072, 768), (1280, 2304, 320), (1032, 2200, 64), (2048, 3072, 768), (2000, 3072, 320)])
 def test_gemm_pingpong_persistent_equals_per_tile(ops, tn, M, N, K):
     """gemm_ppp_kernel (one workgroup per CU walks several tiles, the next tile's operand prologue issued before the current
     epilogue) against the one-workgroup-per-tile launch: same MFMA order, same epilogue arithmetic -- bit-identical, for
@@ -793,6 +793,8 @@ def test_gemm_pingpong_persistent_equals_per_tile(ops, tn, M, N, K):
                 kw2 = dict(kw)
                 if kw2.get("aux") == "new":
                     kw2["aux"] = torch.full((M, N), float("nan"), dtype=dt, device="cuda")
+                route = ops.gemm_route(a_t, b_t, out, **kw2)
+                assert (route.kernel, route.tn) == ("pp_persist" if pers else "pp", tn), (sorted(kw), route)
                 ops.gemm(a_t, b_t, out, **kw2)
                 outs.append((out, kw2.get("aux")))
             assert not torch.isnan(outs[0][0].float()).any()
