@@ -227,7 +227,8 @@ int polus_layernorm_bwd_finalize(void* workspace, size_t workspace_bytes, int ro
 /* ---- embeddings: word[ids] + pos[s] + type[tt] -> LayerNorm (HF TFBertEmbeddings; TF gather
  * has no padding_idx, so row 0 receives its gradient).  Tables and their gradients are f32.
  * bwd recomputes the pre-LN sum; gword rows are accumulated with f32 atomics unless
- * `deterministic`, in which case duplicates are summed in index order by one owner wave. */
+ * `deterministic`, in which case duplicates are summed in index order by one owner wave.
+ * drop_p in [0, 1); drop_p > 0 drops elements of y, mask index row*H+col as above, and needs B*S*H < 2^32. */
 size_t polus_embed_bwd_workspace_bytes(int B, int S, int H);
 int polus_embed_ln_fwd(int dtype, const int32_t* ids, const int32_t* type_ids,
                        const float* word, const float* pos, const float* type,
@@ -242,6 +243,20 @@ int polus_embed_ln_bwd(int dtype, const void* dy, const int32_t* ids, const int3
                        int B, int S, int H, int vocab, int max_pos, int type_vocab,
                        float drop_p, uint32_t seed,
                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* polus_rowwise_route (host only, no HIP call) reports what the LayerNorm and embedding calls above would run for `rows`
+ * rows of H features (rows = B*S for the embedding) under the current switches, from the functions their launchers call.
+ * out[POLUS_ROWWISE_ROUTE_INTS]:
+ *   [0] LayerNorm kernels: 1 f32 a wave per row, 2 bf16 a wave per row, 3 bf16 a half-wave per row
+ *   [1] workgroups of polus_layernorm_fwd
+ *   [2] workgroups of polus_layernorm_bwd given a 16-byte aligned dx_masked (one that is not takes route 2 where [0] says 3)
+ *   [3] finalize launches after the LayerNorm backward: 1, or 2 above POLUS_LN_FIN_SINGLE workgroups
+ *   [4] word-table scatter of polus_embed_ln_bwd: 1..4 atomic with runs combined, that many 256-feature chunks; 5 atomic, any H;
+ *       6 owner (`deterministic`)
+ *   [5] workgroups of the embedding forward   [6] workgroups of the embedding's LayerNorm backward (its finalize is always one launch)
+ * Fails on a bad dtype, rows < 1, or an H that is no multiple of 4 in [4, 2048]. */
+#define POLUS_ROWWISE_ROUTE_INTS 7
+int polus_rowwise_route(int dtype, int rows, int H, int deterministic, int* out);
 
 /* ---- column sums out[c] (+)= sum_r x[r][c]  (bias gradients) */
 size_t polus_colsum_workspace_bytes(int rows, int cols);

@@ -52,6 +52,7 @@ SIGNATURES = {
     "polus_embed_ln_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                 _vp, _vp, _vp, _vp, _vp, _i, _i,
                                 _i, _i, _i, _i, _i, _i, _f, _u32, _vp, _sz, _vp]),
+    "polus_rowwise_route": (_i, [_i, _i, _i, _i, _c.POINTER(_i)]),
     "polus_colsum_workspace_bytes": (_sz, [_i, _i]),
     "polus_colsum": (_i, [_i, _vp, _l, _i, _i, _vp, _i, _vp, _sz, _vp]),
     "polus_loss_workspace_bytes": (_sz, [_i]),

@@ -209,6 +209,19 @@ def dense_bwd_params_grouped_route(problems, accumulate=False, split_k=1):
     return DwGroupedRoute(DW_GROUPED_KERNELS[r[0]], bool(r[1]), tuple(r[2:2 + n]))
 
 
+LN_ROUTES = (None, "wave_f32", "wave_bf16", "halfwave")
+SCATTER_ROUTES = (None, "atomic1", "atomic2", "atomic3", "atomic4", "atomic_wide", "owner")
+RowwiseRoute = collections.namedtuple("RowwiseRoute", "ln ln_fwd_blocks ln_bwd_blocks ln_finalize_stages scatter embed_fwd_blocks embed_bwd_blocks")
+
+
+def rowwise_route(dtype, rows, H, deterministic=False):
+    """What layernorm_fwd / layernorm_bwd / embed_ln_fwd / embed_ln_bwd run for `rows` rows of H features of a torch
+    dtype under the current switches (polus_rowwise_route); launches nothing."""
+    r = (ctypes.c_int * 7)()
+    check(_lib.load().polus_rowwise_route(dtype_code(dtype), rows, H, 1 if deterministic else 0, r), "polus_rowwise_route")
+    return RowwiseRoute(LN_ROUTES[r[0]], r[1], r[2], r[3], SCATTER_ROUTES[r[4]], r[5], r[6])
+
+
 def attention_fwd(qkv, mask, ctx, lse, B, S, n_heads, drop_p=0.0, seed=0):
     lib = _lib.load()
     _req_cuda(qkv, mask, ctx, lse)

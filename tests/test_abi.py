@@ -78,6 +78,17 @@ def test_argument_validation_happens_on_the_host(lib):
     rc = lib.polus_gemm_dropout(1, 0, 0, 1, ctypes.c_void_p(16), 8, ctypes.c_void_p(16), 8, ctypes.c_void_p(16), 8, 8, 8, 8, 1.0,
                                 None, None, 0, None, 0, 0, 0, 1, None, 0, 1.5, 7, None)
     assert rc != 0 and b"0 <= p < 1" in lib.polus_last_error()
+    # the embedding checks its dropout arguments as polus_layernorm_bwd does: p in [0, 1) and, with dropout on, an element
+    # index row * H + col that fits 32 bits (B S H = 2^32 here)
+    p = ctypes.c_void_p(16)
+    emb_fwd = lambda B, S, H, drop_p: lib.polus_embed_ln_fwd(0, p, p, p, p, p, p, p, p, p, p, B, S, H, 10, S, 2, 1e-12, drop_p, 7, None)
+    emb_bwd = lambda B, S, H, drop_p: lib.polus_embed_ln_bwd(0, p, p, p, p, p, p, p, p, p, p, p, p, p, p, 0, 0, B, S, H, 10, S, 2,
+                                                             drop_p, 7, p, 1 << 40, None)
+    for call in (emb_fwd, emb_bwd):
+        for args in ((2, 8, 64, 1.0), (2, 8, 64, -0.1), (65536, 64, 1024, 0.1)):
+            assert call(*args) != 0 and b"drop_p" in lib.polus_last_error(), (call, args)
+    rc = lib.polus_layernorm_bwd(0, p, p, p, p, p, p, p, p, None, 0, 65536 * 64, 1024, p, 0.1, 7, p, 1 << 40, None)
+    assert rc != 0 and b"bad dropout arguments" in lib.polus_last_error()
 
 
 def test_no_cpu_fallback():

@@ -10,7 +10,14 @@ must move at least one output by 5x the tolerance the GPU test applies to that o
                          dropout index shifted by 1
   Adam                   grad_scale or clip_scale ignored; a segment's last len % 4 elements left unchanged; decay
                          applied to a no-decay segment
-and the case table reaches every kernel path with a dropout case, an accumulate case and a ragged tail."""
+and the case table reaches every kernel path with a dropout case, an accumulate case and a ragged tail.
+
+The case table restates two things of the launchers that decide what a case covers: the route (ln_path, scatter_path) and
+the grid caps (LN_*_CAP_ROWS).  test_rowwise_route_matches_cases and test_restated_caps_are_the_launchers_caps hold both
+to the library's own report, polus_rowwise_route (host only: the same functions the launchers call)."""
+import ctypes
+from contextlib import contextmanager
+
 import numpy as np
 import pytest
 import torch
@@ -93,6 +100,102 @@ def test_path_selection_matches_the_host_code():
     assert [rc.scatter_path(H, False) for H in (128, 256, 260, 512, 768, 772, 1024, 1028, 2048)] == \
         ["A1", "A1", "A2", "A2", "A3", "A4", "A4", "AW", "AW"]
     assert rc.scatter_path(128, True) == "OWN" and rc.scatter_path(1280, True) == "OWN"
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from polus_amd import _lib, build
+    build.build(verbose=False)
+    return _lib.load()
+
+
+@contextmanager
+def _switches(env):
+    from polus_amd import ops
+    try:
+        for k, v in env:
+            ops.set_env(k, v)
+        yield
+    finally:
+        for k, _ in env:
+            ops.set_env(k)
+
+
+def _route(lib, dtype, rows, H, deterministic=0):
+    """polus_rowwise_route: [0] LayerNorm path, [1] / [2] forward / backward workgroups, [3] finalize stages, [4] scatter path,
+    [5] / [6] workgroups of the embedding forward / backward."""
+    out = (ctypes.c_int * 7)()
+    rc = lib.polus_rowwise_route({"f32": 0, "bf16": 1}[dtype], rows, H, deterministic, out)
+    assert rc == 0, (dtype, rows, H, lib.polus_last_error())
+    return list(out)
+
+
+ROUTE_ENVS = ((), (("POLUS_LN_HALFWAVE", 0),), (("POLUS_LN_BWD_BLOCKS", 64),))
+
+
+@pytest.mark.parametrize("env", ROUTE_ENVS, ids=lambda e: "-".join(f"{k.split('_', 1)[1].lower()}{v}" for k, v in e) or "default")
+def test_rowwise_route_matches_cases(lib, env):
+    """The library's own routing (no device touched) against ln_path / scatter_path: both dtypes, rows 1..40 and the three
+    large row counts of the case table, every H the entry points take, both scatter forms, under each switch setting."""
+    e = dict(env)
+    halfwave, bwd_cap = e.get("POLUS_LN_HALFWAVE", 1), e.get("POLUS_LN_BWD_BLOCKS", 512)
+    out = (ctypes.c_int * 7)()
+    with _switches(env):
+        for code, dtype in enumerate(("f32", "bf16")):
+            for rows in list(range(1, 41)) + [4106, 65538, 131080]:
+                for H in range(4, 2049, 4):
+                    want_ln = 1 + rc.LN_PATHS.index(rc.ln_path(dtype, rows, H, halfwave))
+                    for det in (0, 1):
+                        assert lib.polus_rowwise_route(code, rows, H, det, out) == 0
+                        want = (want_ln, 1 + rc.SCATTER_PATHS.index(rc.scatter_path(H, det)))
+                        assert (out[0], out[4]) == want, (dtype, rows, H, det, env)
+                        assert out[2] == min((rows + 3) // 4, bwd_cap), (dtype, rows, H, env)      # the switch reaches the report
+    assert lib.polus_rowwise_route(2, 8, 256, 0, out) != 0 and b"bad dtype" in lib.polus_last_error()
+    for H in (0, 258, 2052):
+        assert lib.polus_rowwise_route(1, 8, H, 0, out) != 0 and b"bad arguments" in lib.polus_last_error(), H
+    assert lib.polus_rowwise_route(1, 0, 256, 0, out) != 0
+
+
+def test_restated_caps_are_the_launchers_caps(lib):
+    """The "above the cap" cases take a second trip round a grid-stride loop only while LN_*_CAP_ROWS are the launchers' caps.
+    Per cap: (dtype, index of the workgroup count in the report, rows a workgroup covers per trip, rows per workgroup the
+    launcher sizes its grid by).  The two differ for the half-wave backward alone: it runs on the wave-per-row grid,
+    ceil(rows / 4) workgroups, while its workgroups cover 8 rows each, so its grid is full from 2048 rows on and the
+    "one workgroup fewer" check is made there; where the cap lies is fixed by the other two checks."""
+    H = 256
+    caps = {"LN_FWD_CAP_ROWS": ("f32", 1, 16, 16), "LN_FWD_HW_CAP_ROWS": ("bf16", 1, 8, 8),
+            "LN_BWD_CAP_ROWS": ("f32", 2, 4, 4), "LN_BWD_HW_CAP_ROWS": ("bf16", 2, 8, 4)}
+    for name, (dtype, k, covers, sized_by) in caps.items():
+        cap = getattr(rc, name)
+        path = 1 + rc.LN_PATHS.index("HW" if "HW" in name else "W32")
+        at_cap, above = _route(lib, dtype, cap, H), _route(lib, dtype, cap + covers, H)
+        assert at_cap[0] == above[0] == path, name
+        assert at_cap[k] == above[k], (name, "the grid still grows at the cap")
+        assert at_cap[k] * covers == cap, (name, "the full grid does not cover exactly the cap in one trip")
+        below = _route(lib, dtype, (at_cap[k] - 1) * sized_by, H)
+        assert below[0] == path and below[k] == at_cap[k] - 1, (name, "the grid is full before its last workgroup is needed")
+    # every case meant to exceed a cap does: the backward of the 4106-row cases, the forward of the fwd_only ones
+    over_bwd = [c for c in rc.LN_CASES if c.rows == 4106]
+    over_fwd = [c for c in rc.LN_CASES if c.fwd_only]
+    assert {c.path for c in over_bwd} == {c.path for c in over_fwd} == set(rc.LN_PATHS)
+    for c in over_bwd + over_fwd + rc.LN_FINALIZE_CASES:
+        with _switches(c.env):
+            r = _route(lib, c.dtype, c.rows, c.H)
+        assert r[0] == 1 + rc.LN_PATHS.index(c.path), c.name
+        if c in over_bwd:
+            assert not c.fwd_only and r[2] * (8 if c.path == "HW" else 4) < c.rows, c.name
+        if c in over_fwd:
+            assert r[1] * (8 if c.path == "HW" else 16) < c.rows, c.name
+    B, S, H = rc.EMB_FWD_LARGE
+    assert _route(lib, "f32", B * S, H)[5] * 16 < B * S
+    # the finalize cases: one stage by default, two under the switch their test sets (and never for the embedding, whose
+    # backward grid the report gives apart)
+    for c in rc.LN_FINALIZE_CASES:
+        with _switches(c.env):
+            assert _route(lib, c.dtype, c.rows, c.H)[2:4] == [250, 1], c.name
+        with _switches(c.env + (("POLUS_LN_FIN_SINGLE", rc.LN_FIN_SINGLE),)):
+            assert _route(lib, c.dtype, c.rows, c.H)[2:4] == [250, 2], c.name
+    assert _route(lib, "bf16", 16384, 768) == [3, 2048, 512, 1, 3, 1024, 256]
 
 
 def test_eff_seed_restates_the_host_mix():

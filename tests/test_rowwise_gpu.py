@@ -1,4 +1,4 @@
-"""The row-wise kernels (norm.hip, optim.hip, runtime.hip, loss.hip) against the float64 oracle, on every kernel path.
+"""The row-wise kernels (norm.hip, embed.hip, optim.hip, runtime.hip, loss.hip) against the float64 oracle, on every kernel path.
 
 The cases, the map from case to kernel path, the references and the tolerances live in tests/rowwise_cases.py; a case's
 id starts with its path (W32 / WB / HW LayerNorm families, A1-A4 / AW / OWN word-table scatters).  Every output is
