@@ -335,6 +335,42 @@ int polus_maxsim_bwd(int dtype, const void* Q, const void* D, const float* dscor
 int polus_maxsim_rerank(int dtype, const void* Q, const void* D, const int32_t* qmask, const int32_t* dmask,
                         const int32_t* cand, long ldc, float* score, long lds,
                         int B, int C, int N, int Lq, int Ld, int E, void* stream);
+/* ---- FP8 token index (maxsim_fp8.hip): document token vectors stored as OCP e4m3fn codes (not fnuz) with one f32
+ * scale per token, an exact power of two, 8 + E bytes per token with the int32 mask against 4 + 2E in bf16.
+ * Quantiser, per row x[0..E), integers only:
+ *   amax = max |x_k| = m * 2^k with m in [0.5, 1) (frexp);   e = max(k - 9 + (m > 0.875), -100), e = 0 if amax == 0;
+ *   scale = 2^e;   code_k = e4m3fn(x_k / 2^e), round to nearest even.
+ * e is the smallest exponent with amax / 2^e <= 448, so nothing saturates and a non-zero row's largest code lies in
+ * (224, 448] unless the clamp at -100 holds it lower.  Contract: finite x with amax <= 2^100.  A NaN element is
+ * ignored by amax and becomes a NaN code; an infinite or larger amax gives unspecified codes and scale.  No input makes
+ * the kernel touch memory outside its rows.
+ * Dequantisation is y = T(code) * scale: an e4m3 value has at most 4 significant bits, so both steps are exact in f32
+ * and in bf16 (as long as code * scale stays a normal number of T, which scale >= 2^-100 guarantees).
+ * x, y [rows, E] in `dtype` (f32 or bf16), codes uint8 [rows, E], scale f32 [rows]; one wave per row.
+ * Limits (refused before any launch): rows >= 1; E a multiple of 4 in [4, 256]; non-null pointers; x / y and codes
+ * 16-byte aligned. */
+int polus_fp8_quantize_rows(int dtype, const void* x, uint8_t* codes, float* scale, int rows, int E, void* stream);
+int polus_fp8_dequantize_rows(int dtype, const uint8_t* codes, const float* scale, void* y, int rows, int E,
+                              void* stream);
+/* polus_maxsim_scores and polus_maxsim_rerank over an FP8 corpus: codes uint8 [N,Ld,E] and scale f32 [N,Ld] stand in
+ * for D; Q stays in `dtype` (f32 or bf16), every other argument and every word of the counterpart's contract holds
+ * (masks, strides, -inf for absent candidates with nothing dereferenced, columns past N / C not written, tiles behind
+ * a document's last valid token skipped, the resident-query and the rounds route).  The code bytes are converted to
+ * `dtype` in registers and fed to the counterpart's fragments and MFMAs in the same k order; an accumulator row (a
+ * document token) is multiplied by its token's scale before the mask and the max; the reduction is the counterpart's.
+ * A power-of-two scale commutes with every rounding of the sum, so
+ *   polus_maxsim_scores_fp8(Q, codes, scale) is bit for bit polus_maxsim_scores(Q, D) with D = T(codes) * scale,
+ *   polus_maxsim_rerank_fp8 is bit for bit polus_maxsim_scores_fp8 of each (query, candidate) pair,
+ * provided no product or partial sum under- or overflows f32 (scales of a unit-norm or N(0,1) corpus are ~2^-8).
+ * All quantisation error therefore sits in polus_fp8_quantize_rows.  Memory-bound like the counterparts, on half the
+ * document bytes.
+ * Limits (refused before any launch): those of the counterpart, with codes 16-byte aligned and scale non-null. */
+int polus_maxsim_scores_fp8(int dtype, const void* Q, const uint8_t* codes, const float* scale, const int32_t* qmask,
+                            const int32_t* dmask, float* score, long lds, int B, int N, int Lq, int Ld, int E,
+                            void* stream);
+int polus_maxsim_rerank_fp8(int dtype, const void* Q, const uint8_t* codes, const float* scale, const int32_t* qmask,
+                            const int32_t* dmask, const int32_t* cand, long ldc, float* score, long lds,
+                            int B, int C, int N, int Lq, int Ld, int E, void* stream);
 /* Row L2 normalisation, torch.nn.functional.normalize(x, dim=-1, eps) (ColBERT's cosine): x, y [rows,E] in
  * `dtype` (E <= 256), rnorm f32 [rows].  Forward (f32 arithmetic): y = x / max(|x|, eps), rnorm = 1 / max(|x|, eps).
  * Backward: dx = (dy - y <y, dy>) * rnorm where |x| > eps, dy / eps otherwise.  One wave per row. */

@@ -67,6 +67,10 @@ SIGNATURES = {
     "polus_maxsim_fwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp]),
     "polus_maxsim_scores": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _vp]),
     "polus_maxsim_rerank": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _l, _vp, _l, _i, _i, _i, _i, _i, _i, _vp]),
+    "polus_fp8_quantize_rows": (_i, [_i, _vp, _vp, _vp, _i, _i, _vp]),
+    "polus_fp8_dequantize_rows": (_i, [_i, _vp, _vp, _vp, _i, _i, _vp]),
+    "polus_maxsim_scores_fp8": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _vp]),
+    "polus_maxsim_rerank_fp8": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _l, _i, _i, _i, _i, _i, _i, _vp]),
     "polus_maxsim_bwd": (_i, [_i, _vp, _vp, _vp, _l, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "polus_l2norm_fwd": (_i, [_i, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "polus_l2norm_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),

@@ -13,60 +13,18 @@
 //   dQ: one wave per query token, ascending c;
 //   dD: one workgroup per (document, 64- or 32-wide column chunk), f32 accumulators in LDS; wave w of 16 owns
 //       a sixteenth of the document tokens and adds the entries whose argmax falls there in ascending (b, i).
-#include "common.h"
+#include "maxsim_common.h"
 
 namespace {
 
-constexpr int MS_LMAX = 512;            // Lq, Ld limit
-constexpr int MS_EMAX = 256;            // E limit (multiple of 32)
 constexpr int MS_NOJ = 0x7fffffff;      // "no valid j yet" while reducing
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ void ms_pick(float& m, int& j, float m2, int j2) {
     if (m2 > m || (m2 == m && j2 < j)) { m = m2; j = j2; }
 }
 
-// query tiles held per wave: the B fragments of UT tiles x KS k-steps stay within 64 (bf16) VGPRs
-template <typename T, int KS> struct MsTiles {
-    static constexpr int FR = sizeof(T) == 2 ? 4 : 8;           // VGPRs per fragment
-    static constexpr int U = (64 / FR) / KS;
-    static constexpr int UT = U < 1 ? 1 : (U > 8 ? 8 : U);
-};
-
-// document rows staged in LDS: SR rows per buffer (two buffers), rows padded by 16 B so that the 16 rows of a
-// fragment read fall into distinct banks; the workgroup copies a stage with 16-B loads, NCH per thread
-template <typename T, int KS> struct MsStage {
-    static constexpr int ROWB = 32 * KS * (int)sizeof(T);       // bytes of one document row
-    static constexpr int RS = ROWB + 16;                         // LDS row stride
-    static constexpr int SR = ROWB <= 512 ? 32 : 16;             // rows per stage
-    static constexpr int CPR = ROWB / 16;                        // 16-B chunks per row
-    static constexpr int NCH = (SR * CPR + 255) / 256;           // chunks per thread per stage
-};
-
-// stage st of a document: global -> registers, 16 B per chunk (rows past Ld re-read row Ld-1)
-template <typename T, int KS>
-__device__ __forceinline__ void ms_gload(u32x4* stg, const unsigned char* Dc, int st, int Ld) {
-    using S = MsStage<T, KS>;
-#pragma unroll
-    for (int k = 0; k < S::NCH; ++k) {
-        // unconditional (a clamped chunk past the stage): no branch, so nothing waits for the load here
-        const int ch = min((int)threadIdx.x + 256 * k, S::SR * S::CPR - 1);
-        const int row = min(st * S::SR + ch / S::CPR, Ld - 1);
-        stg[k] = *reinterpret_cast<const u32x4*>(Dc + (size_t)row * S::ROWB + (ch % S::CPR) * 16);
-    }
-}
-
-// registers -> one LDS stage buffer
-template <typename T, int KS>
-__device__ __forceinline__ void ms_sstore(const u32x4* stg, unsigned char* buf) {
-    using S = MsStage<T, KS>;
-#pragma unroll
-    for (int k = 0; k < S::NCH; ++k) {
-        const int ch = threadIdx.x + 256 * k;
-        if (ch < S::SR * S::CPR)
-            *reinterpret_cast<u32x4*>(buf + (ch / S::CPR) * S::RS + (ch % S::CPR) * 16) = stg[k];
-    }
-}
+// a document row of T in the LDS stages of maxsim_common.h
+template <typename T, int KS> using MsStage = MsStageB<32 * KS * (int)sizeof(T)>;
 
 // The forward of both entry points.  ARGMAX = false (polus_maxsim_scores) compiles the argmax stores out and nothing
 // else: the winning j is still tracked, because "no valid j" is how an empty document is told, so the scores are
@@ -115,11 +73,11 @@ __device__ __forceinline__ void maxsim_fwd_body(const T* Q, const T* D, const in
 #pragma unroll
         for (int u = 0; u < UT; ++u) { m[u] = -INFINITY; jb[u] = MS_NOJ; }
 
-        ms_gload<T, KS>(stg, Dc, 0, Ld);
-        ms_sstore<T, KS>(stg, sd);
+        ms_gload<S>(stg, Dc, 0, Ld);
+        ms_sstore<S>(stg, sd);
         __syncthreads();
         for (int st = 0; st < nst; ++st) {
-            if (st + 1 < nst) ms_gload<T, KS>(stg, Dc, st + 1, Ld);   // in flight while this stage is multiplied
+            if (st + 1 < nst) ms_gload<S>(stg, Dc, st + 1, Ld);   // in flight while this stage is multiplied
             if (active) {
                 const unsigned char* buf = sd + (st & 1) * S::SR * S::RS;
 #pragma unroll
@@ -158,7 +116,7 @@ __device__ __forceinline__ void maxsim_fwd_body(const T* Q, const T* D, const in
                 }
             }
             // into the buffer every wave finished reading before the last barrier
-            if (st + 1 < nst) ms_sstore<T, KS>(stg, sd + ((st + 1) & 1) * S::SR * S::RS);
+            if (st + 1 < nst) ms_sstore<S>(stg, sd + ((st + 1) & 1) * S::SR * S::RS);
             __syncthreads();
         }
         if (!active) continue;

@@ -17,20 +17,9 @@
 // The arithmetic is that of maxsim_fwd_body: the same fragments and MFMAs in ascending k, a max over document
 // tokens (a value, so order-free), the 16 maxima of a query tile summed by the same xor-shuffle tree, tiles added in
 // ascending order.  A present entry therefore has the bits polus_maxsim_scores gives that (query, document) pair.
-#include "common.h"
+#include "maxsim_common.h"
 
 namespace {
-
-constexpr int RR_LMAX = 512;            // Lq, Ld limit (maxsim.hip MS_LMAX)
-constexpr int RR_EMAX = 256;            // E limit (multiple of 32)
-constexpr int RR_MAXDPW = 8;            // documents per wave, at most
-
-// query tiles held per wave, as maxsim.hip's MsTiles: the B fragments of UT tiles x KS k-steps within 64 VGPRs
-template <typename T, int KS> struct RrTiles {
-    static constexpr int FR = sizeof(T) == 2 ? 4 : 8;
-    static constexpr int U = (64 / FR) / KS;
-    static constexpr int UT = U < 1 ? 1 : (U > 8 ? 8 : U);
-};
 
 // A fragments of document tile t: lane (i, g) takes row 16 t + i (rows past Ld re-read row Ld - 1), k = 8 g .. 8 g + 7
 // of every 32-wide k-step.  `base` is the document's first row plus this lane's 8 g elements.
@@ -39,48 +28,6 @@ __device__ __forceinline__ void rr_tile_load(Frag<T> (&f)[KS], const unsigned ch
     const unsigned char* p = base + (size_t)min(16 * t + i, Ld - 1) * (32 * KS * sizeof(T));
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) frag_load_row(f[ks], p + ks * 32 * sizeof(T));
-}
-
-// raw document mask, token 64 k + lane in mv[k], for use a whole document later: the loads are unconditional (tokens
-// past Ld re-read token Ld - 1), because a load under a per-lane condition is waited for where it is issued
-__device__ __forceinline__ void rr_mask_load(int (&mv)[8], const int32_t* dm, int lane, int Ld) {
-    if (dm) {                                                 // uniform
-#pragma unroll
-        for (int k = 0; k < 8; ++k) mv[k] = dm[min(64 * k + lane, Ld - 1)];
-    } else {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) mv[k] = 1;
-    }
-}
-
-// tm: lane t < 32 holds the 16 mask bits of document tile t; nvt: tiles up to the last valid token (0 for an absent
-// document)
-__device__ __forceinline__ void rr_mask_pack(const int (&mv)[8], bool present, int lane, int Ld, unsigned& tm, int& nvt) {
-    tm = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const unsigned long long bk = __ballot(present && 64 * k + lane < Ld && mv[k] != 0);
-        if ((lane >> 2) == k) tm = (unsigned)(bk >> (16 * (lane & 3))) & 0xffffu;
-    }
-    const unsigned long long nz = __ballot(tm != 0);
-    nvt = nz ? 64 - (int)__builtin_clzll(nz) : 0;
-}
-
-// B fragments of the query tiles r0 .. r0 + UT - 1 (tiles past the query and rows past Lq re-read a valid row) and
-// whether this lane's token of each tile counts
-template <typename T, int KS, int UT>
-__device__ __forceinline__ void rr_query_load(Frag<T> (&qf)[UT][KS], bool (&qok)[UT], const T* Qb, const int32_t* qm,
-                                              int r0, int nut, int Lq, int i, int g) {
-#pragma unroll
-    for (int u = 0; u < UT; ++u) {
-        const int tok = 16 * (r0 + u) + i;
-        const int tk = min(16 * min(r0 + u, nut - 1) + i, Lq - 1);
-        const unsigned char* p = reinterpret_cast<const unsigned char*>(Qb + (size_t)tk * (32 * KS) + 8 * g);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) frag_load_row(qf[u][ks], p + ks * 32 * sizeof(T));
-        const bool on = !qm || qm[min(tok, Lq - 1)] != 0;
-        qok[u] = tok < Lq && on;
-    }
 }
 
 // one document tile against the wave's nu query tiles: m[u] = max(m[u], products of the valid rows).  bits: the
@@ -108,7 +55,7 @@ __global__ __launch_bounds__(256) void maxsim_rerank_kernel(const T* __restrict_
                                                             const int32_t* __restrict__ cand, long ldc,
                                                             float* __restrict__ score, long lds, int C, int N, int Lq,
                                                             int Ld, int dpw) {
-    constexpr int UT = RrTiles<T, KS>::UT;
+    constexpr int UT = MsTiles<T, KS>::UT;
     constexpr int E = 32 * KS;
     constexpr size_t ROWB = E * sizeof(T);
     const int lane = threadIdx.x & 63;
@@ -203,11 +150,9 @@ __global__ __launch_bounds__(256) void maxsim_rerank_kernel(const T* __restrict_
 template <typename T, int KS>
 void rr_launch(const void* Q, const void* D, const int32_t* qm, const int32_t* dm, const int32_t* cand, long ldc,
                float* score, long lds, int B, int C, int N, int Lq, int Ld, hipStream_t st) {
-    // documents per wave: as many as leave at least 1024 workgroups
-    int dpw = RR_MAXDPW;
-    while (dpw > 1 && (long)B * ((C + 4 * dpw - 1) / (4 * dpw)) < 1024) dpw >>= 1;
+    const int dpw = rr_docs_per_wave(B, C);
     dim3 grid((unsigned)((C + 4 * dpw - 1) / (4 * dpw)), (unsigned)B);
-    if ((Lq + 15) / 16 <= RrTiles<T, KS>::UT)
+    if ((Lq + 15) / 16 <= MsTiles<T, KS>::UT)
         hipLaunchKernelGGL((maxsim_rerank_kernel<T, KS, true>), grid, dim3(256), 0, st, static_cast<const T*>(Q),
                            static_cast<const T*>(D), qm, dm, cand, ldc, score, lds, C, N, Lq, Ld, dpw);
     else
@@ -237,10 +182,10 @@ extern "C" int polus_maxsim_rerank(int dtype, const void* Q, const void* D, cons
                                    int Ld, int E, void* stream) {
     const char* what = "polus_maxsim_rerank";
     POLUS_REQUIRE(dtype == POLUS_F32 || dtype == POLUS_BF16, "%s: unknown dtype %d", what, dtype);
-    POLUS_REQUIRE(E >= 32 && E <= RR_EMAX && E % 32 == 0, "%s: E must be a multiple of 32 in [32, %d] (got %d)", what,
-                  RR_EMAX, E);
-    POLUS_REQUIRE(Lq >= 1 && Lq <= RR_LMAX, "%s: need 1 <= Lq <= %d (got %d)", what, RR_LMAX, Lq);
-    POLUS_REQUIRE(Ld >= 1 && Ld <= RR_LMAX, "%s: need 1 <= Ld <= %d (got %d)", what, RR_LMAX, Ld);
+    POLUS_REQUIRE(E >= 32 && E <= MS_EMAX && E % 32 == 0, "%s: E must be a multiple of 32 in [32, %d] (got %d)", what,
+                  MS_EMAX, E);
+    POLUS_REQUIRE(Lq >= 1 && Lq <= MS_LMAX, "%s: need 1 <= Lq <= %d (got %d)", what, MS_LMAX, Lq);
+    POLUS_REQUIRE(Ld >= 1 && Ld <= MS_LMAX, "%s: need 1 <= Ld <= %d (got %d)", what, MS_LMAX, Ld);
     POLUS_REQUIRE(B >= 1 && B <= 65535, "%s: need 1 <= B <= 65535 (got %d)", what, B);
     POLUS_REQUIRE(C >= 1 && C <= 65535, "%s: need 1 <= C <= 65535 (got %d)", what, C);
     POLUS_REQUIRE(N >= 1, "%s: need 1 <= N <= 2^31 - 1 (got %d)", what, N);

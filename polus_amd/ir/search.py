@@ -12,6 +12,12 @@ other mode is re-ranking: a cheap first stage proposes candidates per query and 
     two = TwoStageSearch(cls_index, token_index, candidates=1000)    # first.search, then second.rerank
     scores, ids = two.search(queries, k=100)
 
+A token index can be stored compressed, `CorpusIndex(..., storage="fp8")`: per document token E bytes of OCP e4m3fn
+codes and one f32 power-of-two scale beside the int32 mask, E + 8 bytes against 2 E + 4 in bf16 (0.52 at E = 128).
+`add` projects, normalises and then quantises (ops.fp8_quantize); `search` and `rerank` score the codes directly
+(ops.maxsim_scores_fp8 / ops.maxsim_rerank_fp8), bit for bit what a plain index holding the dequantised vectors
+returns, so the quantiser's rounding (about 3 % relative L2 per unit vector) is the only difference from a plain index.
+
 As in ir/training.py, arithmetic is hand-written HIP (ops.gemm / ops.maxsim_scores / ops.maxsim_rerank,
 ops.l2norm_fwd, ops.topk_merge); torch allocates, views and copies.  Data parallelism: every rank holds the whole
 index and searches its own shard of the queries; ValidationDataCallback gathers the predictions."""
@@ -33,9 +39,13 @@ class CorpusIndex:
     `compute_scores` is the trainer's InBatchDotScores or MaxSimScores; `normalize` and `eps` are taken from it.
     `post_process_logits` is the trainer's hook for [CLS] vectors, applied to queries and documents as the trainer
     applies it; token representations refuse it, as the trainer does.  `scratch_bytes` bounds the [Q, n] f32 score
-    buffer of one chunk."""
+    buffer of one chunk.  `storage` is None (the model's compute dtype) or "fp8" (token representations only: e4m3fn
+    codes uint8 [N, Ld, E] and power-of-two scales f32 [N, Ld], include/polus_hip.h polus_fp8_quantize_rows)."""
 
-    def __init__(self, model, compute_scores, post_process_logits=None, scratch_bytes=256 << 20):
+    def __init__(self, model, compute_scores, post_process_logits=None, scratch_bytes=256 << 20, storage=None):
+        if storage not in (None, "fp8"):
+            raise ValueError(f"storage must be None or 'fp8' (got {storage!r})")
+        self.storage = storage
         self.model, self.compute_scores = model, compute_scores
         self.post_process_logits = post_process_logits
         self.scratch_bytes = int(scratch_bytes)
@@ -45,7 +55,7 @@ class CorpusIndex:
 
     def clear(self):
         """Empty the index (the storage is released; the next `add` fixes the document length again)."""
-        self._reps = self._mask = None
+        self._reps = self._mask = self._scale = None
         self._n = 0
         self.tokens = None            # True: token representations; fixed by the first add
 
@@ -54,8 +64,31 @@ class CorpusIndex:
 
     @property
     def representations(self):
-        """[N, E] or [N, Ld, E]: a view of the stored documents."""
-        return None if self._reps is None else self._reps[:self._n]
+        """[N, E] or [N, Ld, E]: a view of the stored documents.  On an FP8 index a COPY: the codes dequantised into
+        a new tensor of the model's dtype (exactly codes * scales); writing to it does not change the index."""
+        if self._reps is None:
+            return None
+        if self.storage == "fp8":
+            y = torch.empty(self._reps[:self._n].shape, dtype=self._dtype, device=self._reps.device)
+            if self._n:
+                ops.fp8_dequantize(self._reps[:self._n], self._scale[:self._n], y)
+            return y
+        return self._reps[:self._n]
+
+    @property
+    def codes(self):
+        """uint8 [N, Ld, E]: a view of the stored e4m3fn codes (an FP8 index; None otherwise)."""
+        return None if self.storage != "fp8" or self._reps is None else self._reps[:self._n]
+
+    @property
+    def scales(self):
+        """f32 [N, Ld]: a view of the stored per-token scales, exact powers of two (an FP8 index; None otherwise)."""
+        return None if self._scale is None else self._scale[:self._n]
+
+    @property
+    def nbytes(self):
+        """Bytes of the stored representations, scales and mask of the len(index) documents."""
+        return sum(t[:self._n].numel() * t.element_size() for t in (self._reps, self._scale, self._mask) if t is not None)
 
     @property
     def mask(self):
@@ -74,6 +107,8 @@ class CorpusIndex:
                              "to the scorer (MaxSimScores(normalize=True))")
         if self.tokens is not None and tokens != self.tokens:
             raise ValueError("the index holds " + ("token" if self.tokens else "[CLS]") + " representations")
+        if self.storage == "fp8" and not tokens:
+            raise ValueError("storage='fp8' holds token representations only; a [CLS] index stays in the model's dtype")
         return tokens
 
     def _grow(self, need, like, tail):
@@ -83,18 +118,22 @@ class CorpusIndex:
             return
         cap = max(need, 2 * cap)
         # zeros: the padding of documents shorter than the index's length is never written
-        reps = torch.zeros((cap,) + tail, dtype=like.dtype, device=like.device)
+        fp8 = self.storage == "fp8"
+        reps = torch.zeros((cap,) + tail, dtype=torch.uint8 if fp8 else like.dtype, device=like.device)
         mask = torch.zeros((cap, tail[0]), dtype=torch.int32, device=like.device) if self.tokens else None
+        scale = torch.zeros((cap, tail[0]), dtype=torch.float32, device=like.device) if fp8 else None
         if self._n:
             reps[:self._n].copy_(self._reps[:self._n])
             if mask is not None:
                 mask[:self._n].copy_(self._mask[:self._n])
-        self._reps, self._mask = reps, mask
+            if scale is not None:
+                scale[:self._n].copy_(self._scale[:self._n])
+        self._reps, self._mask, self._scale = reps, mask, scale
 
     def add(self, documents):
         """Encode, project (and normalise) a batch of documents and append it; returns its ids, the consecutive int32
         positions in the index.  Token documents are padded with masked tokens to the length of the first batch;
-        a longer batch raises ValueError."""
+        a longer batch raises ValueError.  An FP8 index quantises the projected (and normalised) vectors here."""
         model = self.model
         rep = model.document_projection(model.encode_document(documents, training=False), training=False)
         tokens = self._check_kind(rep)
@@ -109,6 +148,14 @@ class CorpusIndex:
                 raise ValueError(f"a document batch of {L} tokens does not fit the index's document length {self._ld} "
                                  "(fixed by the first add)")
             self._grow(self._n + n, v, (self._ld, E))
+            if self.storage == "fp8":
+                self._dtype = v.dtype
+                v = v.contiguous()
+                codes = torch.empty(v.shape, dtype=torch.uint8, device=v.device)
+                scale = torch.empty(v.shape[:-1], dtype=torch.float32, device=v.device)
+                ops.fp8_quantize(v, codes, scale)
+                self._scale[self._n:self._n + n, :L].copy_(scale)
+                v = codes
             self._reps[self._n:self._n + n, :L].copy_(v)
             self._mask[self._n:self._n + n, :L].copy_(m)
         else:
@@ -153,7 +200,9 @@ class CorpusIndex:
         top_id = torch.empty((Q, int(k)), dtype=torch.int32, device=qv.device)
         for a, b in spans:
             s = scratch[:, :b - a]
-            if self.tokens:
+            if self.storage == "fp8":
+                ops.maxsim_scores_fp8(qv, self._reps[a:b], self._scale[a:b], q.mask, self._mask[a:b], s)
+            elif self.tokens:
                 ops.maxsim_scores(qv, self._reps[a:b], q.mask, self._mask[a:b], s)
             else:
                 ops.gemm(qv, self._reps[a:b], s)
@@ -209,7 +258,10 @@ class CorpusIndex:
         reps, mask = self._reps[:self._n], self._mask[:self._n]
         for a, b in spans:
             s, c = scratch[:, :b - a], cand[:, a:b]
-            ops.maxsim_rerank(qv, reps, q.mask, mask, c, s)
+            if self.storage == "fp8":
+                ops.maxsim_rerank_fp8(qv, reps, self._scale[:self._n], q.mask, mask, c, s)
+            else:
+                ops.maxsim_rerank(qv, reps, q.mask, mask, c, s)
             ops.topk_merge(s, top_val, top_id, init=(a == 0), ids=c)
         return top_val, top_id
 
@@ -249,13 +301,14 @@ class RetrievalValidationCallback(ValidationDataCallback):
     """Validation of a retrieval run: on each validated epoch the corpus (an iterable of document batches) is encoded
     again with the trainer's current model, compute_scores and post_process_logits, every validation sample
     `(queries, relevant)` becomes `(ids [Q, k], relevant)`, and the trainer's metrics (polus_amd/ir/metrics.py) land in
-    shared_dict["validation"][name], where SaveModelCallback(strategy="best") reads them."""
+    shared_dict["validation"][name], where SaveModelCallback(strategy="best") reads them.  `storage` is the
+    CorpusIndex's (None or "fp8", token representations only)."""
 
     def __init__(self, corpus, tf_validation, k, name=None, validation_interval=1, show_progress=False,
-                 scratch_bytes=256 << 20):
+                 scratch_bytes=256 << 20, storage=None):
         super().__init__(tf_validation, custom_inference_f=self._rank, name=name, show_progress=show_progress,
                          validation_interval=validation_interval)
-        self.corpus, self.k, self.scratch_bytes = corpus, int(k), scratch_bytes
+        self.corpus, self.k, self.scratch_bytes, self.storage = corpus, int(k), scratch_bytes, storage
         self.index = None
 
     def _rank(self, model, sample):
@@ -266,7 +319,8 @@ class RetrievalValidationCallback(ValidationDataCallback):
         if epoch % self.validation_interval:
             return
         trainer = self.coordinator.trainer
-        self.index = CorpusIndex(trainer.model, trainer.compute_scores, trainer.post_process_logits, self.scratch_bytes)
+        self.index = CorpusIndex(trainer.model, trainer.compute_scores, trainer.post_process_logits, self.scratch_bytes,
+                                 storage=self.storage)
         for documents in self.corpus:
             self.index.add(documents)
         super().on_epoch_end(epoch)

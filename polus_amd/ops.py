@@ -424,6 +424,62 @@ def maxsim_rerank(q, d, qmask, dmask, cand, score):
                                           score.stride(0), B, C, N, Lq, Ld, E, _st()), "polus_maxsim_rerank")
 
 
+def fp8_quantize(x, codes, scale):
+    """x [..., E] (f32 or bf16) -> codes uint8 [..., E] (OCP e4m3fn) and scale f32 [...], one power of two per row:
+    the integer rule of include/polus_hip.h polus_fp8_quantize_rows; x ~ e4m3fn(codes) * scale."""
+    _req_cuda(x, codes, scale)
+    E = x.shape[-1]
+    rows = x.numel() // E
+    assert x.is_contiguous() and codes.is_contiguous() and codes.dtype == torch.uint8 and codes.shape == x.shape
+    assert scale.dtype == torch.float32 and scale.numel() == rows and scale.is_contiguous()
+    check(_lib.load().polus_fp8_quantize_rows(dtype_code(x.dtype), ptr(x), ptr(codes), ptr(scale), rows, E, _st()),
+          "polus_fp8_quantize_rows")
+
+
+def fp8_dequantize(codes, scale, y):
+    """y [..., E] (f32 or bf16) = e4m3fn(codes) * scale, exact (codes uint8 [..., E], scale f32 [...])."""
+    _req_cuda(codes, scale, y)
+    E = y.shape[-1]
+    rows = y.numel() // E
+    assert y.is_contiguous() and codes.is_contiguous() and codes.dtype == torch.uint8 and codes.shape == y.shape
+    assert scale.dtype == torch.float32 and scale.numel() == rows and scale.is_contiguous()
+    check(_lib.load().polus_fp8_dequantize_rows(dtype_code(y.dtype), ptr(codes), ptr(scale), ptr(y), rows, E, _st()),
+          "polus_fp8_dequantize_rows")
+
+
+def _fp8_corpus(q, codes, scale):
+    B, Lq, E = q.shape
+    assert codes.dim() == 3 and codes.shape[2] == E and codes.dtype == torch.uint8 and q.is_contiguous() and codes.is_contiguous()
+    N, Ld = codes.shape[0], codes.shape[1]
+    assert scale.dtype == torch.float32 and tuple(scale.shape) == (N, Ld) and scale.is_contiguous()
+    return B, Lq, E, N, Ld
+
+
+def maxsim_scores_fp8(q, codes, scale, qmask, dmask, score):
+    """maxsim_scores over an FP8 corpus (codes uint8 [N, Ld, E], scale f32 [N, Ld]; q stays f32 or bf16): bit for bit
+    maxsim_scores(q, dequantised corpus) (include/polus_hip.h polus_maxsim_scores_fp8)."""
+    _req_cuda(q, codes, scale, qmask, dmask, score)
+    B, Lq, E, N, Ld = _fp8_corpus(q, codes, scale)
+    assert score.dtype == torch.float32 and score.dim() == 2 and score.shape[0] >= B and score.shape[1] >= N and score.stride(1) == 1
+    check(_lib.load().polus_maxsim_scores_fp8(dtype_code(q.dtype), ptr(q), ptr(codes), ptr(scale),
+                                              ptr(_maxsim_mask(qmask, B, Lq, "qmask")), ptr(_maxsim_mask(dmask, N, Ld, "dmask")),
+                                              ptr(score), score.stride(0), B, N, Lq, Ld, E, _st()), "polus_maxsim_scores_fp8")
+
+
+def maxsim_rerank_fp8(q, codes, scale, qmask, dmask, cand, score):
+    """maxsim_rerank over an FP8 corpus: score[b, c] is bit for bit what maxsim_scores_fp8 gives query b and document
+    cand[b, c]; -inf where cand[b, c] is outside [0, N) (include/polus_hip.h polus_maxsim_rerank_fp8)."""
+    _req_cuda(q, codes, scale, qmask, dmask, cand, score)
+    B, Lq, E, N, Ld = _fp8_corpus(q, codes, scale)
+    assert cand.dtype == torch.int32 and cand.dim() == 2 and cand.shape[0] == B and (cand.stride(1) == 1 or cand.shape[1] == 1)
+    C = cand.shape[1]
+    assert score.dtype == torch.float32 and tuple(score.shape) == (B, C) and (score.stride(1) == 1 or C == 1)
+    check(_lib.load().polus_maxsim_rerank_fp8(dtype_code(q.dtype), ptr(q), ptr(codes), ptr(scale),
+                                              ptr(_maxsim_mask(qmask, B, Lq, "qmask")), ptr(_maxsim_mask(dmask, N, Ld, "dmask")),
+                                              ptr(cand), cand.stride(0), ptr(score), score.stride(0), B, C, N, Lq, Ld, E, _st()),
+          "polus_maxsim_rerank_fp8")
+
+
 def topk_merge(scores, top_val, top_id, id0=0, init=False, ids=None):
     """Merge scores (f32 [rows, n], any row stride; column c is document id0 + c) into the running top-k state
     top_val f32 / top_id int32 [rows, k]: score descending, ties to the lower id, NaN and -inf dropped, (-inf, -1)
