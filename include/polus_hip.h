@@ -409,6 +409,59 @@ int polus_topk_merge(const float* scores, long lds, int rows, int n, int32_t id0
 int polus_topk_merge_ids(const float* scores, long lds, const int32_t* ids, long ldi, int rows, int n,
                          float* top_val, int32_t* top_id, int k, int init, void* stream);
 
+/* ---- centroid-pruned search of a token index (centroid.hip; ColBERTv2 / PLAID candidate generation).  Every stored
+ * document token is replaced by the id of its nearest centroid, an unsigned 16-bit code; 0xFFFF means "no token"
+ * (masked or padding), and any other code >= K is absent too: nothing is dereferenced for it.
+ *
+ * polus_centroid_scores, the approximate MaxSim by table look-ups:
+ *   table  f32 [K, >= B*Lq], row stride ldt:  table[c*ldt + b*Lq + i] = <centroid c, Q[b,i]>   (one polus_gemm)
+ *   qmask  int32 [B, Lq] or NULL (all ones);  codes uint16 [N, Ld] contiguous;  score f32 [B, N], row stride lds >= N
+ *   score[b*lds + n] = sum over valid i of  max over present j of  table[codes[n,j]*ldt + b*Lq + i]
+ * A query token without a present document token adds 0.0, so an empty document and an empty query score 0.0 as in
+ * polus_maxsim_scores.  Columns of score past N are not written.  The table is assumed finite.  The max is exact; the
+ * sum over i is f32 in an order fixed by Lq alone (a lane's query tokens i, i + 64, ... ascending, then one xor-shuffle
+ * tree over the wave), so the bits of score[b, n] depend on that (query, document) pair only: not on B, N, the other
+ * queries and documents of the launch, the chunking of a corpus, or the route.  No atomics, no workspace, bitwise
+ * reproducible.  One workgroup per (query, contiguous range of documents, sized so that a launch has about four
+ * workgroups per CU and a range at least 4 documents per wave); a wave owns a pair from its first look-up to the store.
+ * Two routes, chosen from Lq and K alone:
+ *   1 LDS-resident: the workgroup (1024 threads) copies the query's [K, Lq] slice of the table into dynamic LDS, rows
+ *     packed at a stride of Lq floats without padding, plus one row of -inf that absent codes read:
+ *     LDS bytes = (K + 1) * Lq * 4, and the route is taken iff that is <= 163840 (160 KiB, one CU's LDS; K <= 1279 at
+ *     Lq = 32).  A step of a wave reads whole contiguous rows: one row (Lq > 32), two (17 .. 32) or 64 / P rows of
+ *     P = 2^ceil(log2 Lq) floats (Lq <= 16).
+ *   2 global gather: 256 threads, the same loop with the rows read from global memory (L2 / Infinity Cache resident in
+ *     practice); serves every K * Lq too large for LDS.
+ * polus_centroid_scores_route (host only, no HIP call) reports out[0] = the route (1 or 2) and out[1] = the dynamic LDS
+ * bytes of route 1 (0 for route 2); it applies the shape limits below.
+ * Limits (refused before any launch): 1 <= Lq, Ld <= 512; 1 <= K <= 65535; 1 <= B, N <= 65535; ldt >= B*Lq; lds >= N;
+ * table, codes, score non-null. */
+#define POLUS_CENTROID_ROUTE_INTS 2
+int polus_centroid_scores_route(int B, int N, int Lq, int Ld, int K, int* out);
+int polus_centroid_scores(const float* table, long ldt, const int32_t* qmask, const uint16_t* codes,
+                          float* score, long lds, int B, int N, int Lq, int Ld, int K, void* stream);
+/* The nearest centroid of each row of a similarity matrix (tokens x centroids^T from polus_gemm):
+ *   sim f32 [rows, K], row stride lds >= K;  mask int32 [rows] or NULL;  codes uint16 [rows]
+ *   codes[r] = 0xFFFF where mask[r] == 0, else the first (lowest) c that maximises sim[r, c] by IEEE comparison
+ *              (-0.0 equals +0.0).  A NaN never wins; a row of NaN only gives 0.
+ * One wave per row, 16-byte reads where the row is 16-byte aligned (4-byte reads otherwise); candidates are ordered by
+ * (value descending, column ascending), a total order, so the result does not depend on how lanes split the row.
+ * Limits (refused before any launch): rows >= 1; 1 <= K <= 65535; lds >= K; sim, codes non-null. */
+int polus_centroid_codes(const float* sim, long lds, const int32_t* mask, uint16_t* codes, int rows, int K, void* stream);
+/* One spherical k-means update:
+ *   x [T, E] in `dtype` (f32 / bf16);  codes uint16 [T];  prev, out [K, E] in `dtype` (out must not alias prev);
+ *   counts int32 [K]
+ *   sum_k     = f32 sum of x[t] over the t with codes[t] == k;   counts[k] = how many such t
+ *   out[k]    = sum_k / |sum_k|, rounded once to `dtype`, if counts[k] > 0 and |sum_k| > eps;   prev[k] otherwise
+ * Codes >= K (0xFFFF among them) belong to no centroid and are skipped.  One workgroup of 4 waves per centroid scans the
+ * code array: wave w adds the rows of tokens [w*ceil(T/4), (w+1)*ceil(T/4)) in ascending t, the four partials are added
+ * as (w0 + w1) + (w2 + w3); |sum_k|^2 is an f32 sum over the features in a fixed tree.  No atomics, no workspace, bitwise
+ * reproducible.  Index-build time work: K reads of the code array.
+ * Limits (refused before any launch): dtype f32 or bf16; E a multiple of 32 in [32, 256]; T >= 1; 1 <= K <= 65535;
+ * non-null pointers. */
+int polus_centroid_update(int dtype, const void* x, const uint16_t* codes, const void* prev, void* out,
+                          int32_t* counts, int T, int K, int E, float eps, void* stream);
+
 /* ---- argmax over the last axis (PolusClassifier.inference, polus/models.py:148-150) */
 int polus_argmax(const float* x, long ldx, int32_t* out, int rows, int C, void* stream);
 

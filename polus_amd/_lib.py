@@ -76,6 +76,10 @@ SIGNATURES = {
     "polus_l2norm_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "polus_topk_merge": (_i, [_vp, _l, _i, _i, _c.c_int32, _vp, _vp, _i, _i, _vp]),
     "polus_topk_merge_ids": (_i, [_vp, _l, _vp, _l, _i, _i, _vp, _vp, _i, _i, _vp]),
+    "polus_centroid_scores_route": (_i, [_i, _i, _i, _i, _i, _c.POINTER(_i)]),
+    "polus_centroid_scores": (_i, [_vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _vp]),
+    "polus_centroid_codes": (_i, [_vp, _l, _vp, _vp, _i, _i, _vp]),
+    "polus_centroid_update": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "polus_argmax": (_i, [_vp, _l, _vp, _i, _i, _vp]),
     "polus_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64,
                              _f, _f, _f, _f, _f, _f, _f, _vp, _vp]),

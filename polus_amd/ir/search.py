@@ -18,8 +18,23 @@ codes and one f32 power-of-two scale beside the int32 mask, E + 8 bytes against 
 (ops.maxsim_scores_fp8 / ops.maxsim_rerank_fp8), bit for bit what a plain index holding the dequantised vectors
 returns, so the quantiser's rounding (about 3 % relative L2 per unit vector) is the only difference from a plain index.
 
+A token index whose scorer normalises (MaxSimScores(normalize=True)) can also prune its own search, without a second
+model (ColBERTv2 / PLAID candidate generation): every stored token carries the 16-bit id of its nearest centroid, a
+query token's similarity to all K centroids is one GEMM, and MaxSim is approximated by table look-ups
+(ops.centroid_scores), one gathered load and one max per token pair where the exact score spends E multiply-adds.
+
+    index.fit_centroids(1024)                           # spherical k-means on the device, or index.set_centroids(c)
+    scores, ids = index.search_pruned(queries, k=100, candidates=1000)
+
+The best `candidates` documents under the approximation go through `rerank`.  What is exact: every returned score is
+the MaxSim score of its document with the bits `search` gives it, and the returned documents are in `search`'s order.
+What is approximate: WHICH documents get scored; a document the look-up score ranks below `candidates` is never
+seen, however good its exact score.  How often that happens (recall against `search`) depends on K, `candidates`
+and the data; it has not been measured on a real collection.  With candidates >= len(index) the result is `search`'s.
+
 As in ir/training.py, arithmetic is hand-written HIP (ops.gemm / ops.maxsim_scores / ops.maxsim_rerank,
-ops.l2norm_fwd, ops.topk_merge); torch allocates, views and copies.  Data parallelism: every rank holds the whole
+ops.l2norm_fwd, ops.topk_merge, ops.centroid_scores / centroid_codes / centroid_update); torch allocates, views and
+copies.  Data parallelism: every rank holds the whole
 index and searches its own shard of the queries; ValidationDataCallback gathers the predictions."""
 import numpy as np
 import torch
@@ -30,6 +45,8 @@ from .models import TokenReps
 
 MAX_CHUNK = 65535             # documents per launch: the MaxSim grid's limit, kept on the dot path too
 MAX_K = 1024                  # results per query: the limit of ops.topk_merge
+MAX_CENTROIDS = 65535         # codes are 16 bits and 0xFFFF is "no token"
+ASSIGN_ROWS = 16384           # tokens per nearest-centroid GEMM, at most (see CorpusIndex._assign_rows)
 
 
 class CorpusIndex:
@@ -56,6 +73,7 @@ class CorpusIndex:
     def clear(self):
         """Empty the index (the storage is released; the next `add` fixes the document length again)."""
         self._reps = self._mask = self._scale = None
+        self._codes = self._centroids = None          # centroid codes int16 [cap, Ld] and centroids [K, E]
         self._n = 0
         self.tokens = None            # True: token representations; fixed by the first add
 
@@ -86,9 +104,21 @@ class CorpusIndex:
         return None if self._scale is None else self._scale[:self._n]
 
     @property
+    def centroids(self):
+        """[K, E] in the index's dtype: the centroids of set_centroids / fit_centroids (None before)."""
+        return self._centroids
+
+    @property
+    def centroid_codes(self):
+        """int16 [N, Ld]: a view of the stored tokens' nearest-centroid ids; the 16 bits are the unsigned code, so -1
+        is 0xFFFF, "no token" (None before centroids exist)."""
+        return None if self._codes is None else self._codes[:self._n]
+
+    @property
     def nbytes(self):
-        """Bytes of the stored representations, scales and mask of the len(index) documents."""
-        return sum(t[:self._n].numel() * t.element_size() for t in (self._reps, self._scale, self._mask) if t is not None)
+        """Bytes of the stored representations, scales, mask and centroid codes of the len(index) documents."""
+        return sum(t[:self._n].numel() * t.element_size() for t in (self._reps, self._scale, self._mask, self._codes)
+                   if t is not None)
 
     @property
     def mask(self):
@@ -128,6 +158,10 @@ class CorpusIndex:
                 mask[:self._n].copy_(self._mask[:self._n])
             if scale is not None:
                 scale[:self._n].copy_(self._scale[:self._n])
+        if self._codes is not None:
+            codes = torch.full((cap, tail[0]), -1, dtype=torch.int16, device=like.device)         # 0xFFFF: no token
+            codes[:self._n].copy_(self._codes[:self._n])
+            self._codes = codes
         self._reps, self._mask, self._scale = reps, mask, scale
 
     def add(self, documents):
@@ -158,6 +192,8 @@ class CorpusIndex:
                 v = codes
             self._reps[self._n:self._n + n, :L].copy_(v)
             self._mask[self._n:self._n + n, :L].copy_(m)
+            if self._centroids is not None:
+                self._assign(self._n, self._n + n)
         else:
             v = rep if self.post_process_logits is None else self.post_process_logits(rep)
             n, E = v.shape
@@ -233,7 +269,10 @@ class CorpusIndex:
         if not self.tokens:
             raise ValueError("rerank scores token representations (MaxSim); the index holds [CLS] representations, "
                              "whose search is already one GEMM")
-        q = self.encode_queries(queries)
+        return self._rerank_encoded(self.encode_queries(queries), candidates, k)
+
+    def _rerank_encoded(self, q, candidates, k):
+        """`rerank` behind the query encoder: q is encode_queries' TokenReps."""
         qv = q.values
         Q = qv.shape[0]
         if isinstance(candidates, torch.Tensor) and candidates.is_cuda:
@@ -264,6 +303,137 @@ class CorpusIndex:
                 ops.maxsim_rerank(qv, reps, q.mask, mask, c, s)
             ops.topk_merge(s, top_val, top_id, init=(a == 0), ids=c)
         return top_val, top_id
+
+    # ------------------------------------------------------------ centroid-pruned search
+    def _check_centroid_support(self):
+        if self._n == 0:
+            raise ValueError("the index is empty: add documents before setting or fitting centroids")
+        if not self.tokens:
+            raise ValueError("centroids prune a token (MaxSim) index; the index holds [CLS] representations, whose "
+                             "search is already one GEMM")
+        if not self.normalize:
+            raise ValueError("centroids need a scorer that normalises (MaxSimScores(normalize=True)): the nearest "
+                             "centroid by dot product means something on unit vectors only")
+
+    def _token_dtype(self):
+        return self._dtype if self.storage == "fp8" else self._reps.dtype
+
+    def _assign_rows(self, load, T, mask, codes, centroids):
+        """codes[t] (int16 [T]) = the nearest row of `centroids` to token t, 0xFFFF where mask[t] == 0 (mask int32 [T]
+        or None); load(a, b, dst) writes tokens a .. b into dst [b - a, E].  Every GEMM of a call runs at the same
+        shape [rows, E] x [K, E]^T, rows = the largest power of two with rows * K * 4 <= scratch_bytes, at most
+        ASSIGN_ROWS, the last chunk's tail being zero rows: ops.gemm picks its kernel from the shape, and kernels may
+        sum in different orders, so a token's similarities, and with them its code at a near tie, depend on nothing
+        but the token, the centroids and (through rows) K and scratch_bytes."""
+        K, E = centroids.shape
+        rows = ASSIGN_ROWS
+        while rows > 1 and rows * K * 4 > self.scratch_bytes:
+            rows >>= 1
+        if rows * K * 4 > self.scratch_bytes:
+            raise ValueError(f"scratch_bytes = {self.scratch_bytes} does not hold one token's similarities to "
+                             f"{K} centroids ({4 * K} bytes)")
+        x = torch.zeros((rows, E), dtype=centroids.dtype, device=centroids.device)
+        sim = torch.empty((rows, K), dtype=torch.float32, device=centroids.device)
+        for a in range(0, T, rows):
+            b = min(a + rows, T)
+            load(a, b, x[:b - a])
+            ops.gemm(x, centroids, sim)
+            ops.centroid_codes(sim, None if mask is None else mask[a:b], codes[a:b], rows=b - a)
+
+    def _assign(self, a, b):
+        """Codes of the stored documents a .. b from their stored representation (an FP8 index: the dequantised
+        vectors) and the centroids: the same function in `add` and in `set_centroids`."""
+        Ld, E = self._ld, self._reps.shape[2]
+        reps = self._reps[a:b].view(-1, E)
+        if self.storage == "fp8":
+            scale = self._scale[a:b].view(-1)
+            load = lambda s, e, dst: ops.fp8_dequantize(reps[s:e], scale[s:e], dst)
+        else:
+            load = lambda s, e, dst: dst.copy_(reps[s:e])
+        self._assign_rows(load, (b - a) * Ld, self._mask[a:b].view(-1), self._codes[a:b].view(-1), self._centroids)
+
+    def set_centroids(self, centroids):
+        """Take `centroids` ([K, E] array or tensor, 1 <= K <= 65535, as given: cast to the index's dtype, not
+        normalised) and give every stored token the id of its nearest one by dot product (ops.gemm +
+        ops.centroid_codes; ties to the lower id; masked and padding slots get 0xFFFF).  Documents added later are
+        assigned in `add`.  Codes are a function of the stored representation and the centroids (and of the GEMM
+        shape _assign_rows fixes from K and scratch_bytes), so assigning again never changes a code."""
+        self._check_centroid_support()
+        c = centroids if isinstance(centroids, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(centroids))
+        E = self._reps.shape[2]
+        if c.dim() != 2 or c.shape[1] != E or not 1 <= c.shape[0] <= MAX_CENTROIDS:
+            raise ValueError(f"centroids must be [K, {E}] with 1 <= K <= {MAX_CENTROIDS} (got {tuple(c.shape)})")
+        self._centroids = c.to(device=self._reps.device, dtype=self._token_dtype()).contiguous().clone()
+        self._codes = torch.full((self._reps.shape[0], self._ld), -1, dtype=torch.int16, device=self._reps.device)
+        self._assign(0, self._n)
+
+    def fit_centroids(self, K, iters=4, sample=1 << 18, seed=0):
+        """Spherical k-means on the device over a sample of the stored tokens, then set_centroids.
+
+        Sample: with r = numpy.random.Generator(PCG64(seed)) and S = N * Ld token slots (slot = document * Ld +
+        position), the slots are r.permutation(S) when S <= sample and r.choice(S, size=sample, replace=False)
+        otherwise, in the order drawn; slots whose mask is 0 are dropped.  It depends on seed, N, Ld and the masks
+        only.  The sampled rows are gathered by a torch index copy (an FP8 index: codes and scales, then
+        ops.fp8_dequantize).  The first K of them are the initial centroids; fewer than K raises ValueError.
+        Each of `iters` rounds assigns every sampled token to its nearest centroid (ops.gemm + ops.centroid_codes)
+        and replaces a centroid by the normalised sum of its tokens (ops.centroid_update; a centroid without tokens
+        stays).  All sums run in a fixed order: the same index and seed give the same bits, so data-parallel ranks
+        holding the same corpus agree without communication."""
+        self._check_centroid_support()
+        K = int(K)
+        if not 1 <= K <= MAX_CENTROIDS:
+            raise ValueError(f"need 1 <= K <= {MAX_CENTROIDS} centroids (got {K})")
+        S, E = self._n * self._ld, self._reps.shape[2]
+        r = np.random.Generator(np.random.PCG64(int(seed)))
+        slots = r.permutation(S) if S <= int(sample) else r.choice(S, size=int(sample), replace=False)
+        slots = slots[self._mask[:self._n].reshape(-1).cpu().numpy()[slots] != 0]
+        if len(slots) < K:
+            raise ValueError(f"{K} centroids need at least as many valid sampled tokens (got {len(slots)})")
+        dev = self._reps.device
+        at = torch.as_tensor(slots.astype(np.int64)).to(dev)
+        flat = self._reps[:self._n].view(-1, E)
+        if self.storage == "fp8":
+            x = torch.empty((len(slots), E), dtype=self._dtype, device=dev)
+            ops.fp8_dequantize(flat[at].contiguous(), self._scale[:self._n].view(-1)[at].contiguous(), x)
+        else:
+            x = flat[at].contiguous()
+        T = x.shape[0]
+        cent, nxt = x[:K].clone(), torch.empty((K, E), dtype=x.dtype, device=dev)
+        codes = torch.empty((T,), dtype=torch.int16, device=dev)
+        counts = torch.empty((K,), dtype=torch.int32, device=dev)
+        for _ in range(int(iters)):
+            self._assign_rows(lambda a, b, dst: dst.copy_(x[a:b]), T, None, codes, cent)
+            ops.centroid_update(x, codes, cent, nxt, counts, self.eps)
+            cent, nxt = nxt, cent
+        self.set_centroids(cent)
+
+    def search_pruned(self, queries, k, candidates):
+        """`search` over the `candidates` documents per query that score best under the centroid approximation:
+        (scores f32 [Q, k], ids int32 [Q, k]) with exactly the contract of `search`.  The returned scores are exact
+        MaxSim scores, bit for bit what `search` gives those documents; which documents are scored is approximate
+        (see the module docstring).  One GEMM builds the table <centroid, query token>, ops.centroid_scores and
+        ops.topk_merge keep the best `candidates` per chunk of documents, and the rerank path scores them."""
+        if self._n == 0:
+            raise ValueError("the index is empty: add documents before searching")
+        if self._centroids is None:
+            raise ValueError("search_pruned needs centroids: call fit_centroids or set_centroids first")
+        if not 1 <= int(candidates) <= MAX_K:
+            raise ValueError(f"need 1 <= candidates <= {MAX_K}, the limit of ops.topk_merge, which keeps the candidates "
+                             f"(got {candidates})")
+        q = self.encode_queries(queries)
+        qv = q.values
+        Q, Lq, E = qv.shape
+        table = torch.empty((self._centroids.shape[0], Q * Lq), dtype=torch.float32, device=qv.device)
+        ops.gemm(self._centroids, qv.view(Q * Lq, E), table)
+        spans = self.chunks(Q)
+        scratch = torch.empty((Q, max(b - a for a, b in spans)), dtype=torch.float32, device=qv.device)
+        cand_val = torch.empty((Q, int(candidates)), dtype=torch.float32, device=qv.device)
+        cand_id = torch.empty((Q, int(candidates)), dtype=torch.int32, device=qv.device)
+        for a, b in spans:
+            s = scratch[:, :b - a]
+            ops.centroid_scores(table, q.mask, self._codes[a:b], s, Q, Lq)
+            ops.topk_merge(s, cand_val, cand_id, id0=a, init=(a == 0))
+        return self._rerank_encoded(q, cand_id, k)
 
 
 class TwoStageSearch:
@@ -302,17 +472,23 @@ class RetrievalValidationCallback(ValidationDataCallback):
     again with the trainer's current model, compute_scores and post_process_logits, every validation sample
     `(queries, relevant)` becomes `(ids [Q, k], relevant)`, and the trainer's metrics (polus_amd/ir/metrics.py) land in
     shared_dict["validation"][name], where SaveModelCallback(strategy="best") reads them.  `storage` is the
-    CorpusIndex's (None or "fp8", token representations only)."""
+    CorpusIndex's (None or "fp8", token representations only).  With `centroids` (a number K) the index fits that many
+    centroids once the corpus is added (CorpusIndex.fit_centroids) and ranks with search_pruned over `candidates`
+    documents per query (None: 1024, the most it takes); the defaults rank with the exhaustive `search`."""
 
     def __init__(self, corpus, tf_validation, k, name=None, validation_interval=1, show_progress=False,
-                 scratch_bytes=256 << 20, storage=None):
+                 scratch_bytes=256 << 20, storage=None, centroids=None, candidates=None):
         super().__init__(tf_validation, custom_inference_f=self._rank, name=name, show_progress=show_progress,
                          validation_interval=validation_interval)
         self.corpus, self.k, self.scratch_bytes, self.storage = corpus, int(k), scratch_bytes, storage
+        self.centroids = centroids
+        self.candidates = MAX_K if candidates is None else int(candidates)
         self.index = None
 
     def _rank(self, model, sample):
         queries, relevant = sample
+        if self.centroids is not None:
+            return self.index.search_pruned(queries, self.k, self.candidates)[1], relevant
         return self.index.search(queries, self.k)[1], relevant
 
     def on_epoch_end(self, epoch):
@@ -323,5 +499,7 @@ class RetrievalValidationCallback(ValidationDataCallback):
                                  storage=self.storage)
         for documents in self.corpus:
             self.index.add(documents)
+        if self.centroids is not None:
+            self.index.fit_centroids(int(self.centroids))
         super().on_epoch_end(epoch)
         self.index.clear()

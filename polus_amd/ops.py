@@ -504,6 +504,60 @@ def topk_merge(scores, top_val, top_id, id0=0, init=False, ids=None):
                                        1 if init else 0, _st()), "polus_topk_merge")
 
 
+CENTROID_ROUTES = (None, "lds", "global")
+CentroidRoute = collections.namedtuple("CentroidRoute", "route lds_bytes")
+
+
+def centroid_scores_route(B, N, Lq, Ld, K):
+    """What `centroid_scores` runs for these shapes (polus_centroid_scores_route): the route, "lds" or "global", and the
+    dynamic LDS bytes of the LDS route; launches nothing."""
+    r = (ctypes.c_int * 2)()
+    check(_lib.load().polus_centroid_scores_route(int(B), int(N), int(Lq), int(Ld), int(K), r), "polus_centroid_scores_route")
+    return CentroidRoute(CENTROID_ROUTES[r[0]], r[1])
+
+
+def centroid_scores(table, qmask, codes, score, B, Lq):
+    """score[b, n] (f32, any row stride >= N) = sum over valid i of max over present j of table[codes[n, j], b * Lq + i]:
+    MaxSim approximated by look-ups.  table f32 [K, >= B * Lq] (any row stride) holds <centroid c, query token (b, i)>;
+    codes int16 [N, Ld] (the bits are the unsigned code; 0xFFFF or any code >= K: no token); qmask int32 [B, Lq] or
+    None (include/polus_hip.h polus_centroid_scores)."""
+    _req_cuda(table, qmask, codes, score)
+    K = table.shape[0]
+    N, Ld = codes.shape
+    assert table.dtype == torch.float32 and table.dim() == 2 and table.shape[1] >= B * Lq and (table.stride(1) == 1 or table.shape[1] == 1)
+    assert codes.dtype == torch.int16 and codes.is_contiguous()
+    assert score.dtype == torch.float32 and score.dim() == 2 and score.shape[0] >= B and score.shape[1] >= N and (score.stride(1) == 1 or score.shape[1] == 1)
+    check(_lib.load().polus_centroid_scores(ptr(table), table.stride(0), ptr(_maxsim_mask(qmask, B, Lq, "qmask")), ptr(codes),
+                                            ptr(score), score.stride(0), int(B), N, int(Lq), Ld, K, _st()), "polus_centroid_scores")
+
+
+def centroid_codes(sim, mask, codes, rows=None, K=None):
+    """codes[r] (int16, the bits of the unsigned code) = 0xFFFF where mask[r] == 0, else the first column maximising
+    sim[r] (f32 [rows, K], any row stride); NaN never wins (include/polus_hip.h polus_centroid_codes)."""
+    _req_cuda(sim, mask, codes)
+    rows = sim.shape[0] if rows is None else rows
+    K = sim.shape[1] if K is None else K
+    assert sim.dtype == torch.float32 and sim.dim() == 2 and sim.shape[0] >= rows and sim.shape[1] >= K and (sim.stride(1) == 1 or sim.shape[1] == 1)
+    assert codes.dtype == torch.int16 and codes.is_contiguous() and codes.numel() >= rows
+    assert mask is None or (mask.dtype == torch.int32 and mask.is_contiguous() and mask.numel() >= rows)
+    check(_lib.load().polus_centroid_codes(ptr(sim), sim.stride(0), ptr(mask), ptr(codes), rows, K, _st()), "polus_centroid_codes")
+
+
+def centroid_update(x, codes, prev, out, counts, eps=1e-12):
+    """One spherical k-means update: out[k] = the normalised f32 sum of the rows x[t] with codes[t] == k, rounded once to
+    x's dtype, or prev[k] where no row has code k or the sum's norm is <= eps; counts[k] (int32) = how many rows.
+    x [T, E], codes int16 [T], prev / out [K, E] (distinct buffers) (include/polus_hip.h polus_centroid_update)."""
+    _req_cuda(x, codes, prev, out, counts)
+    T, E = x.shape
+    K = prev.shape[0]
+    assert x.is_contiguous() and prev.is_contiguous() and out.is_contiguous() and out.data_ptr() != prev.data_ptr()
+    assert prev.dtype == x.dtype and out.dtype == x.dtype and tuple(prev.shape) == (K, E) and tuple(out.shape) == (K, E)
+    assert codes.dtype == torch.int16 and codes.is_contiguous() and codes.numel() == T
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == K
+    check(_lib.load().polus_centroid_update(dtype_code(x.dtype), ptr(x), ptr(codes), ptr(prev), ptr(out), ptr(counts), T, K, E,
+                                            float(eps), _st()), "polus_centroid_update")
+
+
 def maxsim_bwd(q, d, dscore, argmax, dq, dd):
     """dq [B, Lq, E] and dd [N, Ld, E] from dscore (f32 [B, N], row stride free) and the forward's argmax; every
     element is written."""
