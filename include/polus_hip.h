@@ -282,7 +282,11 @@ int polus_sigmoid_xent(int dtype, const float* logits, long ldl, const float* y_
  * crf_decode restated).  potentials f32 [B,S,C]; tags int32 [B,S]; lengths int32 [B];
  * trans f32 [C,C] (already masked by the caller, polus/layers.py:58-63);
  * sample_w f32 [B] or NULL.  loss = mean_b(-ll_b * w_b).  dpot in `dtype`, dtrans f32 [C,C].
- * C <= 16: one thread per sequence; 17 <= C <= 128: one workgroup per sequence (crf.hip). */
+ * C <= 16: one thread per sequence; 17 <= C <= 128: one workgroup per sequence (crf.hip).
+ * lengths outside [0, S] and tags outside [0, C) are clamped; tags at and past a sequence's length are
+ * not read; dpot rows at and past it are written as zeros; the workspace need not be initialised.
+ * Both paths agree with the float64 definition for any finite f32 potentials and transitions (masked
+ * ones at -10000 included), however far apart, within the bounds recorded in tests/crf_cases.py. */
 size_t polus_crf_workspace_bytes(int B, int S, int C);
 int polus_crf_nll(int dtype, const float* potentials, const int32_t* tags, const int32_t* lengths,
                   const float* trans, const float* sample_w, float* loss, void* dpot,

@@ -6,15 +6,35 @@
 // NLL: the scans run in the scaled domain.  E[k][j] = exp(T[k][j] - cmax_j) (cmax_j = column j's max;
 // an all-masked column of -10000 entries stays finite) lives in LDS with a padded row stride, so that
 // the forward's column reads (lane j, fixed k) and the backward's row reads (lane k, fixed j) are both
-// free of bank conflicts.  Per step:
-//   forward   m = max(alpha), a = exp(alpha - m), alpha'[j] = pot[j] + cmax_j + m + log(sum_k a[k] E[k][j])
-//   backward  v = pot + beta + cmax, n = max(v), q = exp(v - n), beta_prev[k] = n + log(sum_j E[k][j] q[j])
-// (one GEMV plus C exps and C logs).  The forward stores a (the scaled alpha) and m per step in the
-// workspace; marginals come back as a * exp(beta + m - logZ), pair marginals as
-// E[k][j] * a_prev[k] * q[j] * exp(m_prev + n - logZ): the lane owning row k keeps sum_s a_prev[k] q_s[j]
-// exp(m_prev + n_s - logZ) for every j in registers, and E multiplies the sum once at the end.  Gold
-// counts are subtracted by the owning lane, the sequence's [C,C] slab goes to the workspace and a
-// finalize launch sums the slabs in b order: no atomics, bitwise reproducible.
+// free of bank conflicts.  alpha[j] = M + d[j] and beta[k] = N + e[k]: the parts M, N that every tag shares
+// (and logZ) are doubles, uniform over the workgroup, the per-tag parts f32 of small magnitude, and the two
+// are never added in f32.  alpha grows with S and with the potentials' scale; summed in f32 it rounds at its
+// ulp every step (1e-3 at |alpha| = 1e4), and the marginals exp(alpha + beta - logZ) see that at full size.
+// Per step:
+//   forward   dm = max(d), a = exp(d - dm), M += dm, d'[j] = (pot[j] + cmax_j) + log(sum_k a[k] E[k][j])
+//   backward  v = (pot + e) + cmax, vm = max(v), q = exp(v - vm), e'[k] = log(sum_j E[k][j] q[j]), N += vm
+// (one GEMV plus C exps and C logs; M after its update is the step's largest alpha).  The forward stores a
+// and dm per step in the workspace, the backward steps M back down by the same dm.  Marginals come back as
+// a * exp(e + c), c = M + N - logZ (one double, rounded to f32 where it is used), pair marginals as E[k][j] *
+// a_prev[k] * q[j] * exp(g), g = M_prev + N + vm - logZ: the lane owning row k keeps sum_s a_prev[k] q_s[j] exp(g_s) for every
+// j in registers, and E multiplies the sum once at the end.  Gold counts are subtracted by the owning lane,
+// the sequence's [C,C] slab goes to the workspace and a finalize launch sums the slabs in b order: no
+// atomics, bitwise reproducible.
+//
+// Where the scaled domain runs out of range the same quantities are taken in the log domain, as loss.hip
+// does for C <= 16, so that any finite f32 potentials give the float64 definition's result (confident
+// emissions against a BIO mask: both allowed predecessors of an I-X tag more than 88 below the step's best
+// tag, so that their a is 0 and the sum was once floored at FLT_MIN):
+//   - a lane whose GEMV sum falls under CRF_RESCUE_SUM recomputes d'[j] = pot[j] + (lse_k(d[k] + T[k][j]) -
+//     dm), resp. e'[k] = lse_j(T[k][j] + pot[j] + e[j]) - vm, from the step's d, resp. pot + e, kept in LDS
+//     beside a, resp. q, and trans in global memory;
+//   - where a is below FLT_MIN the workspace holds log a = d - dm in its place (negative, so the two cannot
+//     be confused), and a marginal whose exponent e + c exceeds CRF_RESCUE_EXP is exp(log a + (e + c));
+//   - at a step whose g exceeds CRF_RESCUE_EXP, a_prev * exp(g) would be 0 * inf: lane k adds
+//     exp(log a_prev[k] + T[k][j] + pot[j] + e[j] + c_prev) straight into row k of the sequence's slab
+//     (zeroed at the first such step) and folds the row in at the end.
+// Under the two thresholds an underflowed factor costs a sum or a marginal at most e^-29 resp. e^-47 of
+// its value, and the rescues change nothing.
 //
 // Viterbi: f32 max-plus, the same arithmetic and tie-break (first maximum over ascending k, first
 // maximum for the final tag) as crf_viterbi_kernel; back-pointers as uint8 [B,S,C_PAD] in the
@@ -28,11 +48,35 @@ template <int CP> struct CrfCfg {
     static constexpr int NT = CP < 64 ? 64 : CP;   // threads per workgroup (lanes >= C idle in the tag work)
     static constexpr int NW = NT / 64;
     static constexpr int LDE = CP + 1;              // E row stride (floats): rows start on distinct banks
-    static constexpr size_t NLL_LDS = (size_t)(CP * LDE + 2 * CP + 8) * sizeof(float);
+    static constexpr size_t NLL_LDS = (size_t)(CP * LDE + 4 * CP + 8) * sizeof(float);
     static constexpr size_t VIT_LDS = (size_t)(CP * CP + 2 * CP) * sizeof(float);
 };
 
 __device__ __forceinline__ int clamp_tag(int t, int C) { return t < 0 ? 0 : (t >= C ? C - 1 : t); }
+
+// A GEMV sum below this is recomputed in the log domain.  Far above the denormal range: whatever a or E flushed
+// to zero (each factor < 2^-126 ~ e^-87) is below C * e^-29 of a sum that stays on the scaled path.
+constexpr float CRF_RESCUE_SUM = 1e-25f;
+// A scale exponent above this leaves the scaled products: below it an underflowed factor costs at most e^-47.
+constexpr float CRF_RESCUE_EXP = 40.f;
+
+// The workspace keeps per step and tag a = exp(d - dm), or where that is below FLT_MIN the negative log a =
+// d - dm itself (the backward scan then takes a as 0).
+// log a back from it, for the rescues alone: the empty asm is never executed speculatively, so the logf stays
+// inside their branches and out of the common path.
+__device__ __forceinline__ float crf_log_a(float v) {
+    asm volatile("" : "+v"(v));
+    return v < 0.f ? v : logf(v);
+}
+
+// max + log(sum(exp(. - max))) of v[i] + t[i * stride], i < n: the rescue of one lane, trans read from global memory
+__device__ __forceinline__ float lse_rescue(const float* v, const float* __restrict__ t, int stride, int n) {
+    float mx = -FLT_MAX;
+    for (int i = 0; i < n; ++i) mx = fmaxf(mx, v[i] + t[(long)i * stride]);
+    float sm = 0.f;
+    for (int i = 0; i < n; ++i) sm += expf(v[i] + t[(long)i * stride] - mx);
+    return mx + logf(sm);
+}
 
 // block-wide max / sum in fixed order.  red[slot], red[slot + 1] are written before the barrier; a caller
 // separates two uses of the same slot by another barrier.
@@ -67,7 +111,8 @@ __global__ __launch_bounds__(CrfCfg<CP>::NT) void crf_nll_wg_kernel(
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* E = lds;                      // [CP][LDE]
     float* vec = E + CP * LDE;           // [2][CP] double-buffered a (forward) / q (backward)
-    float* red = vec + 2 * CP;           // [8]
+    float* lvec = vec + 2 * CP;          // [2][CP] the same steps' alpha (forward) / pot + beta (backward), for the rescues
+    float* red = lvec + 2 * CP;          // [8]
     const int b = blockIdx.x, j = threadIdx.x;
     const bool live = j < C;             // C <= CP <= NT
     const float* x = pot + (long)b * S * C;
@@ -97,6 +142,11 @@ __global__ __launch_bounds__(CrfCfg<CP>::NT) void crf_nll_wg_kernel(
     if (j < CP)
         for (int k = 0; k < CP; ++k) E[k * LDE + j] = (live && k < C) ? expf(trans[k * C + j] - cmax) : 0.f;
 
+    // d of step 0 (alpha itself: M starts at 0), loaded here so that the gold score's reduction has waited for it
+    // before the forward loop
+    const int jj = live ? j : 0;
+    float d = live ? x[j] : -FLT_MAX;
+
     // gold path score
     float sc = 0.f;
     for (int s = j; s < L; s += NT) {
@@ -107,18 +157,24 @@ __global__ __launch_bounds__(CrfCfg<CP>::NT) void crf_nll_wg_kernel(
     const float score = block_sum<NW>(sc, red, 2);
     __syncthreads();                     // E complete; red[2..3] free again
 
-    // forward
-    float alpha = live ? x[j] : -FLT_MAX;
-    float a_last = 0.f, m_last = 0.f;
+    // forward.  The loops' global loads are unconditional (index clamped, idle lanes read tag 0) and a step ahead
+    // of their use: the rescues' own loads make the compiler wait for everything in flight wherever it waits for
+    // one load, so what a step waits for was issued a step before.
+    float a_last = 0.f, va_last = 0.f;
+    double M = 0.0;                      // uniform; after a step's update, that step's largest alpha
     for (int s = 0; s < L; ++s) {
-        const float xn = (live && s + 1 < L) ? x[(long)(s + 1) * C + j] : 0.f;
-        const float m = block_max<NW>(live ? alpha : -FLT_MAX, red, 0);
-        const float a = live ? expf(alpha - m) : 0.f;
-        if (j < CP) ah[(long)s * CP + j] = a;
-        if (j == 0) ms[s] = m;
-        if (s + 1 == L) { a_last = a; m_last = m; break; }
+        const float xn = x[(long)(s + 1 < L ? s + 1 : s) * C + jj];  // the last step's is not used
+        const float dm = block_max<NW>(live ? d : -FLT_MAX, red, 0);
+        const float la = d - dm;
+        const float a = live ? expf(la) : 0.f;
+        const float va = a >= FLT_MIN ? a : la;                     // a denormal a carries too few bits for its log
+        if (live) ah[(long)s * CP + j] = va;
+        if (j == 0) ms[s] = dm;
+        M += (double)dm;
+        if (s + 1 == L) { a_last = a; va_last = va; break; }
         float* av = vec + (s & 1) * CP;
-        if (j < CP) av[j] = a;
+        float* lv = lvec + (s & 1) * CP;
+        if (j < CP) { av[j] = a; lv[j] = d; }
         __syncthreads();
         if (live) {
             float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -131,33 +187,68 @@ __global__ __launch_bounds__(CrfCfg<CP>::NT) void crf_nll_wg_kernel(
                 acc[3] = fmaf(a4.w, E[(k + 3) * LDE + j], acc[3]);
             }
             const float sum = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-            alpha = xn + cmax + m + logf(fmaxf(sum, FLT_MIN));
+            if (sum >= CRF_RESCUE_SUM) d = (xn + cmax) + logf(sum);
+            else d = xn + (lse_rescue(lv, trans + j, C, C) - dm);   // every predecessor far below the step's best tag
         }
     }
-    const float logz = m_last + logf(block_sum<NW>(a_last, red, 2));
-    if (j == 0) nll_b[b] = -(score - logz) * wsw;
+    const double logz = M + (double)logf(block_sum<NW>(a_last, red, 2));
+    if (j == 0) nll_b[b] = -(score - (float)logz) * wsw;
 
     // backward + gradients
     float accT[CP];
 #pragma unroll
     for (int i = 0; i < CP; ++i) accT[i] = 0.f;
-    float beta = 0.f, a_s = a_last, m_s = m_last;
+    float e = 0.f, va_s = va_last, a_s = a_last;
+    double c = M - logz;                 // uniform: M + N - logZ, M stepped back down by each dm, N up by each vm
+    bool slab = false;                   // uniform: some step added its pair marginals to the slab directly
+    __syncthreads();                     // lane 0's ms[] visible to every wave
+    // what step s reads (a of s - 1, dm, pot and tag of s) is loaded during step s + 1, clamped at the bottom
+    const int s0 = L >= 2 ? L - 2 : 0;
+    float va_n = ah[(long)s0 * CP + jj], dm_n = ms[L - 1], x_n = x[(long)(L - 1) * C + jj];
+    int t_n = t[L - 1];
     for (int s = L - 1; s >= 0; --s) {
+        const float va_p = va_n, dm_s = dm_n, xs = x_n;
+        const int ts = clamp_tag(t_n, C);
+        const int s1 = s >= 1 ? s - 1 : 0, s2 = s >= 2 ? s - 2 : 0;
+        va_n = ah[(long)s2 * CP + jj];
+        dm_n = ms[s1];
+        x_n = x[(long)s1 * C + jj];
+        t_n = t[s1];
         if (live) {
-            const float marg = a_s * expf(beta + (m_s - logz));
-            const int ts = clamp_tag(t[s], C);
+            const float ec = e + (float)c;                          // beta + m - logZ
+            float marg;
+            if (ec > CRF_RESCUE_EXP) marg = expf(crf_log_a(va_s) + ec);     // = exp(alpha + beta - logZ)
+            else marg = a_s * expf(ec);
             dx[(long)s * C + j] = from_f<T>((marg - (j == ts ? 1.0f : 0.0f)) * w);
         }
         if (s == 0) break;
-        const float a_p = j < CP ? ah[(long)(s - 1) * CP + j] : 0.f;
-        const float m_p = ms[s - 1];
-        const float v = live ? x[(long)s * C + j] + beta + cmax : -FLT_MAX;
-        const float n = block_max<NW>(v, red, 0);
+        c -= (double)dm_s;                                          // M is now the largest alpha of step s - 1
+        const float a_p = live ? fmaxf(va_p, 0.f) : 0.f;
+        const float u = live ? xs + e : -FLT_MAX;
+        const float v = live ? u + cmax : -FLT_MAX;
+        const float vm = block_max<NW>(v, red, 0);
         float* qv = vec + (s & 1) * CP;
-        if (j < CP) qv[j] = live ? expf(v - n) : 0.f;
+        float* uv = lvec + (s & 1) * CP;
+        if (j < CP) { qv[j] = live ? expf(v - vm) : 0.f; uv[j] = u; }
         __syncthreads();
+        const float cp = (float)c;
+        c += (double)vm;
+        const float g = (float)c;                                   // uniform over the workgroup
+        const bool direct = g > CRF_RESCUE_EXP;
+        if (direct) {
+            // a_prev * exp(g) would be 0 * inf: this step's pair marginals go straight into the lane's slab row
+            if (live) {
+                float* row = dT + (long)j * C;
+                const float* Tr = trans + (long)j * C;
+                if (!slab)
+                    for (int i = 0; i < C; ++i) row[i] = 0.f;
+                const float la_p = crf_log_a(va_p);
+                for (int i = 0; i < C; ++i) row[i] += expf((la_p + Tr[i] + uv[i]) + cp);
+            }
+            slab = true;
+        }
         if (j < CP) {
-            const float ck = a_p * expf(m_p + n - logz);
+            const float ck = direct ? 0.f : a_p * expf(g);
             const float* Er = E + j * LDE;
             float acc[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -172,16 +263,22 @@ __global__ __launch_bounds__(CrfCfg<CP>::NT) void crf_nll_wg_kernel(
                 accT[i + 2] = fmaf(ck, q4.z, accT[i + 2]);
                 accT[i + 3] = fmaf(ck, q4.w, accT[i + 3]);
             }
-            beta = n + logf(fmaxf((acc[0] + acc[1]) + (acc[2] + acc[3]), FLT_MIN));
+            const float sum = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+            if (sum >= CRF_RESCUE_SUM) e = logf(sum);
+            else if (live) e = lse_rescue(uv, trans + (long)j * C, 1, C) - vm;
         }
+        va_s = va_p;
         a_s = a_p;
-        m_s = m_p;
     }
     // row k of the slab: E[k][.] * accT - gold counts, in place of E's row (each lane owns its row)
     if (j < CP) {
         float* Er = E + j * LDE;
 #pragma unroll
         for (int i = 0; i < CP; ++i) Er[i] *= accT[i];
+        if (live && slab) {
+            const float* row = dT + (long)j * C;
+            for (int i = 0; i < C; ++i) Er[i] += row[i];
+        }
     }
     if (live)
         for (int s = 1; s < L; ++s)
@@ -313,8 +410,9 @@ int viterbi_launch(const float* pot, const int32_t* lengths, const float* trans,
 
 }  // namespace
 
-// Workspace of the workgroup-per-sequence path: scaled alpha [B,S,C_PAD] (Viterbi: uint8 back-pointers
-// in the same bytes) + log scales [B,S] + per-sequence nll [B] + per-sequence dtrans [B,C,C], f32.
+// Workspace of the workgroup-per-sequence path: scaled alpha, or its log where that is below FLT_MIN, [B,S,C_PAD]
+// (Viterbi: uint8 back-pointers in the same bytes) + each step's increment of the log scale [B,S] + per-sequence
+// nll [B] + per-sequence dtrans [B,C,C], f32.
 size_t polus_crf_wg_workspace_bytes(int B, int S, int C) {
     const int CP = crf_bucket(C);
     return ((size_t)B * S * CP + (size_t)B * S + (size_t)B + (size_t)B * C * C) * sizeof(float) + 64;

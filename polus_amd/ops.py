@@ -352,11 +352,27 @@ def sigmoid_xent(logits, y_true, class_weights, negative_weight, loss, dlogits):
                                  rows, C, ptr(ws), nb, _st()), "polus_sigmoid_xent")
 
 
+def _crf_arg(name, t, dtype, shape, optional=False):
+    """The CRF kernels index their arguments as dense arrays of one element type: anything else is read as garbage."""
+    if t is None:
+        assert optional, f"crf: {name} is required"
+        return
+    assert t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous(), \
+        f"crf: {name} must be contiguous {dtype} {list(shape)} (got {t.dtype} {list(t.shape)}, strides {list(t.stride())})"
+
+
 def crf_nll(potentials, tags, lengths, trans, sample_w, loss, dpot, dtrans, accumulate=False):
     lib = _lib.load()
     _req_cuda(potentials, tags, lengths, trans, sample_w, loss, dpot, dtrans)
     B, S, C = potentials.shape
     assert potentials.dtype == torch.float32 and potentials.is_contiguous() and dpot.is_contiguous()
+    assert dpot.shape == potentials.shape
+    _crf_arg("tags", tags, torch.int32, (B, S))
+    _crf_arg("lengths", lengths, torch.int32, (B,), optional=True)
+    _crf_arg("trans", trans, torch.float32, (C, C))
+    _crf_arg("sample_w", sample_w, torch.float32, (B,), optional=True)
+    _crf_arg("dtrans", dtrans, torch.float32, (C, C))
+    assert loss.dtype == torch.float32 and loss.numel() >= 1, "crf: loss must be f32"
     nb = lib.polus_crf_workspace_bytes(B, S, C)
     ws = workspace(potentials.device).get(nb)
     check(lib.polus_crf_nll(dtype_code(dpot.dtype), ptr(potentials), ptr(tags), ptr(lengths), ptr(trans), ptr(sample_w),
@@ -368,6 +384,10 @@ def crf_viterbi(potentials, lengths, trans, out_tags):
     lib = _lib.load()
     _req_cuda(potentials, lengths, trans, out_tags)
     B, S, C = potentials.shape
+    assert potentials.dtype == torch.float32 and potentials.is_contiguous()
+    _crf_arg("lengths", lengths, torch.int32, (B,), optional=True)
+    _crf_arg("trans", trans, torch.float32, (C, C))
+    _crf_arg("out_tags", out_tags, torch.int32, (B, S))
     nb = lib.polus_crf_workspace_bytes(B, S, C)
     ws = workspace(potentials.device).get(nb)
     check(lib.polus_crf_viterbi(ptr(potentials), ptr(lengths), ptr(trans), ptr(out_tags), B, S, C, ptr(ws), nb, _st()),
