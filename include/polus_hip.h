@@ -278,6 +278,37 @@ int polus_sigmoid_xent(int dtype, const float* logits, long ldl, const float* y_
                        void* dlogits, long lddl, int rows, int C,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- softmax cross-entropy over rows of any width with ignored rows (xent_wide.hip): the masked-LM objective of the
+ * original BERT recipe (HF BertForMaskedLM: CrossEntropyLoss(ignore_index = -100) over [rows, vocab]); the reference has no
+ * pre-training step, its users start from checkpoints made by this objective.  One workgroup per row.
+ *   logits [rows, V] in `dtype` (f32 or bf16), row stride ldl; labels int32 [rows]; dlogits in `dtype`, row stride lddl.
+ *   label < 0: the row is ignored (0 to the loss, a zero dlogits row).  label >= V: ignored as well and counted in
+ *   stats[1] (as polus_confusion_matrix counts `rejected`).  stats (device int32 [2], may be NULL) = {counted, rejected}.
+ *   loss = sum over counted rows of (lse(row) - x[label]) / max(counted, 1); dlogits = (softmax - onehot) / max(counted, 1).
+ *   dlogits may be the logits buffer itself (then lddl == ldl); any other overlap is undefined.
+ * All arithmetic f32, expf / logf, gradient as exp((x - max) - log(sum)).  A row of at most 128 KiB is staged in LDS (one
+ * HBM read, one write per element); a wider one is streamed (online max / sum, then a second read).  16-byte accesses
+ * when logits, dlogits and both strides in bytes are multiples of 16, single elements otherwise: same results to the
+ * last bit on the staged path.  No atomics; per-row losses are added in index order: bitwise reproducible.
+ * polus_softmax_xent_wide_route (host only: no HIP call, no pointer dereferenced; the pointers count for their alignment)
+ * reports what the call would run and fails where its validation fails: out[0] 0 staged / 1 streaming, out[1] 1 = 16-byte
+ * accesses, out[2] dynamic LDS bytes. */
+#define POLUS_XENT_WIDE_ROUTE_INTS 3
+size_t polus_softmax_xent_wide_workspace_bytes(int rows);
+int polus_softmax_xent_wide_route(int dtype, const void* logits, long ldl, const void* dlogits, long lddl,
+                                  int rows, int V, int* out);
+int polus_softmax_xent_wide(int dtype, const void* logits, long ldl, const int32_t* labels, float* loss,
+                            void* dlogits, long lddl, int32_t* stats, int rows, int V,
+                            void* workspace, size_t workspace_bytes, void* stream);
+/* y[i] = x[idx[i]] for i < n where 0 <= idx[i] < rows, a zero row otherwise; x [rows, H] and y [n, H] in `dtype` with free
+ * row strides (>= H), y != x.  Every element of y[0..n) is written.  Picks the masked positions out of [B S, H]; with the
+ * inverse map it is also the scatter of the backward pass: deterministic, no atomics.
+ * polus_inverse_map: inv[j] (int32 [rows]) = the LAST i < n with idx[i] == j, or -1; entries of idx outside [0, rows) are
+ * skipped.  One workgroup; for index lists of a few thousand entries. */
+int polus_gather_rows(int dtype, const void* x, long ldx, const int32_t* idx, void* y, long ldy,
+                      int n, int rows, int H, void* stream);
+int polus_inverse_map(const int32_t* idx, int n, int32_t* inv, int rows, void* stream);
+
 /* ---- linear-chain CRF (polus/layers.py:58-126; tensorflow-addons crf_log_likelihood /
  * crf_decode restated).  potentials f32 [B,S,C]; tags int32 [B,S]; lengths int32 [B];
  * trans f32 [C,C] (already masked by the caller, polus/layers.py:58-63);

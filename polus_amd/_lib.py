@@ -58,6 +58,11 @@ SIGNATURES = {
     "polus_loss_workspace_bytes": (_sz, [_i]),
     "polus_softmax_xent": (_i, [_i, _vp, _l, _vp, _vp, _vp, _vp, _l, _i, _i, _vp, _sz, _vp]),
     "polus_sigmoid_xent": (_i, [_i, _vp, _l, _vp, _l, _vp, _f, _vp, _vp, _l, _i, _i, _vp, _sz, _vp]),
+    "polus_softmax_xent_wide_workspace_bytes": (_sz, [_i]),
+    "polus_softmax_xent_wide_route": (_i, [_i, _vp, _l, _vp, _l, _i, _i, _c.POINTER(_i)]),
+    "polus_softmax_xent_wide": (_i, [_i, _vp, _l, _vp, _vp, _vp, _l, _vp, _i, _i, _vp, _sz, _vp]),
+    "polus_gather_rows": (_i, [_i, _vp, _l, _vp, _vp, _l, _i, _i, _i, _vp]),
+    "polus_inverse_map": (_i, [_vp, _i, _vp, _i, _vp]),
     "polus_crf_workspace_bytes": (_sz, [_i, _i, _i]),
     "polus_crf_nll": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
     "polus_crf_viterbi": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),

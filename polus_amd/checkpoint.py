@@ -18,11 +18,16 @@ HF_LAYER_MAP = [
     ("output.dense.weight", "ffn2.w"), ("output.dense.bias", "ffn2.b"),
     ("output.LayerNorm.weight", "ln2.g"), ("output.LayerNorm.bias", "ln2.b"),
 ]
+HF_MLM_MAP = [
+    ("transform.dense.weight", "mlm.dense.w"), ("transform.dense.bias", "mlm.dense.b"),
+    ("transform.LayerNorm.weight", "mlm.ln.g"), ("transform.LayerNorm.bias", "mlm.ln.b"), ("bias", "mlm.bias"),
+]
 
 
 def hf_state_to_params(state, num_layers):
     """HF BertModel state dict (name -> ndarray; an optional 'bert.' prefix is stripped, old
-    'gamma'/'beta' LayerNorm names accepted) -> this repo's names with Q/K/V fused into qkv.{w,b}."""
+    'gamma'/'beta' LayerNorm names accepted) -> this repo's names with Q/K/V fused into qkv.{w,b}.  The masked-LM head
+    (cls.predictions.*) arrives as mlm.* when the state has it; a decoder matrix that is not the word table is an error."""
     st = {}
     for k, v in state.items():
         k = k[5:] if k.startswith("bert.") else k
@@ -41,6 +46,14 @@ def hf_state_to_params(state, num_layers):
         p["pooler.w"], p["pooler.b"] = st["pooler.dense.weight"], st["pooler.dense.bias"]
     if "classifier.weight" in state:
         p["head.w"], p["head.b"] = np.asarray(state["classifier.weight"]), np.asarray(state["classifier.bias"])
+    # the masked-LM head of HF BertForMaskedLM / BertForPreTraining; the decoder matrix IS the word table
+    for hf, ours in HF_MLM_MAP:
+        if "cls.predictions." + hf in st:
+            p[ours] = st["cls.predictions." + hf]
+    dec = st.get("cls.predictions.decoder.weight")
+    if dec is not None and not (dec.shape == p["emb.word"].shape and np.array_equal(dec, p["emb.word"])):
+        raise ValueError("cls.predictions.decoder.weight differs from embeddings.word_embeddings.weight: the weights are "
+                         "untied, and BertForMaskedLM keeps one table for both")
     return p
 
 
@@ -70,6 +83,24 @@ def load_bert_from_local(path, compute_dtype="bf16", num_labels=None, add_poolin
                      hidden_dropout_prob=c.get("hidden_dropout_prob", 0.1),
                      attention_probs_dropout_prob=c.get("attention_probs_dropout_prob", 0.1), _name_or_path=path)
     model = BertModel(cfg, compute_dtype=compute_dtype, num_labels=num_labels, add_pooling_layer=add_pooling_layer)
+    model.load_numpy_params(params)
+    return model
+
+
+def load_bert_for_masked_lm_from_local(path, compute_dtype="bf16"):
+    """A local HF BertForMaskedLM / BertForPreTraining directory -> BertForMaskedLM (encoder + cls.predictions.*; a
+    checkpoint without the head keeps the head's initial values)."""
+    from .models import BertConfig, BertForMaskedLM
+    if not os.path.isdir(path):
+        raise FileNotFoundError(f"'{path}' is not a local directory: checkpoints cannot be fetched by name (no network)")
+    c, params = read_local_hf_checkpoint(path)
+    cfg = BertConfig(vocab_size=c["vocab_size"], hidden_size=c["hidden_size"], num_hidden_layers=c["num_hidden_layers"],
+                     num_attention_heads=c["num_attention_heads"], intermediate_size=c["intermediate_size"],
+                     max_position_embeddings=c["max_position_embeddings"], type_vocab_size=c.get("type_vocab_size", 2),
+                     layer_norm_eps=c.get("layer_norm_eps", 1e-12),
+                     hidden_dropout_prob=c.get("hidden_dropout_prob", 0.1),
+                     attention_probs_dropout_prob=c.get("attention_probs_dropout_prob", 0.1), _name_or_path=path)
+    model = BertForMaskedLM(cfg, compute_dtype=compute_dtype)
     model.load_numpy_params(params)
     return model
 

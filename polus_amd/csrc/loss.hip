@@ -1,7 +1,8 @@
 // Losses of the Polus training step (gfx950): sparse / class-weighted softmax CE,
 // class-weighted sigmoid CE, linear-chain CRF negative log-likelihood + Viterbi, argmax.
-// All are tiny next to the encoder (C <= a few dozen classes): one thread per row (CE) or
-// per sequence (CRF scan), f32 arithmetic, per-block partial losses combined in a fixed
+// The ones in this file are tiny next to the encoder (C <= a few dozen classes): one thread per row (CE) or
+// per sequence (CRF scan); a vocabulary-wide class axis (the masked-LM loss) is xent_wide.hip's, a workgroup
+// per row.  f32 arithmetic, per-block partial losses combined in a fixed
 // order by a second single-block kernel (bitwise reproducible, no atomics).
 #include "common.h"
 

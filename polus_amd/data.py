@@ -561,3 +561,54 @@ class CachedDataLoaderwLookup(CachedDataLoader):
         index_info["lookup_file"] = lookup_file
         with open(self.cache_index_path, "w") as f:
             json.dump(index_info, f)
+
+
+# ------------------------------------------------------------------------------- masked-LM input side
+def mask_tokens(input_ids, attention_mask, *, mask_id, vocab_size, special_ids, max_predictions, p=0.15, rng):
+    """The masking of the original BERT recipe (create_pretraining_data.py: masked_lm_prob, max_predictions_per_seq),
+    on the host like the rest of the input pipeline.  input_ids, attention_mask: int [B, S].
+
+    Per sequence, of its n attended tokens that are not in `special_ids`, min(max_predictions, max(1, round(p * n)))
+    distinct positions are drawn (none when n = 0); 80 % of them are replaced by `mask_id`, 10 % by a random id that is
+    not special, 10 % stay as they are.  Returns (input_ids' [B, S], masked_positions [B, P], masked_labels [B, P]) as
+    int32 with P = max_predictions: a row's positions ascending, then -1 in both arrays for the unused slots -- the
+    `masked_positions` BertForMaskedLM takes and the labels MaskedSparseCategoricalCrossentropy ignores.  `rng` is a
+    np.random.Generator: the same state gives the same output.
+
+    As the `map` of a batched Dataset:
+        ds.map(lambda x: mlm_batch(x, mask_id=103, vocab_size=30522, special_ids=(0, 100, 101, 102, 103),
+                                   max_predictions=40, rng=rng))"""
+    ids = np.array(input_ids, dtype=np.int32, copy=True)
+    att = np.asarray(attention_mask)
+    assert ids.ndim == 2 and att.shape == ids.shape
+    B, S = ids.shape
+    P = int(max_predictions)
+    special = np.zeros(int(vocab_size), bool)
+    special[[int(s) for s in special_ids if 0 <= int(s) < vocab_size]] = True
+    fill = np.nonzero(~special)[0].astype(np.int32)
+    assert fill.size > 0, "every id is special"
+    pos = np.full((B, P), -1, np.int32)
+    lab = np.full((B, P), -1, np.int32)
+    for b in range(B):
+        in_vocab = (ids[b] >= 0) & (ids[b] < vocab_size)
+        cand = np.nonzero((att[b] != 0) & in_vocab & ~special[np.where(in_vocab, ids[b], 0)])[0]
+        n = cand.size
+        if n == 0:
+            continue
+        k = min(P, n, max(1, int(round(p * n))))
+        chosen = np.sort(rng.choice(cand, size=k, replace=False)).astype(np.int32)
+        u = rng.random(k)
+        rand_ids = fill[rng.integers(0, fill.size, size=k)]
+        pos[b, :k] = chosen
+        lab[b, :k] = ids[b, chosen]
+        ids[b, chosen] = np.where(u < 0.8, np.int32(mask_id), np.where(u < 0.9, rand_ids, ids[b, chosen]))
+    return ids, pos, lab
+
+
+def mlm_batch(x, **kw):
+    """A batch {input_ids, attention_mask, ...} -> ({..., input_ids', masked_positions}, masked_labels): the (x, y) pair
+    ClassifierTrainer.train_step takes for a BertForMaskedLM.  Keywords as mask_tokens."""
+    x = dict(x[0] if isinstance(x, (tuple, list)) else x)
+    ids, pos, lab = mask_tokens(x["input_ids"], x["attention_mask"], **kw)
+    x["input_ids"], x["masked_positions"] = ids, pos
+    return x, lab

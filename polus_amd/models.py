@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .layers import CRF, Dense, Dropout, Flatten, Layer, dense_bwd_params_group, gemm_dx
+from .layers import CRF, Dense, Dropout, Flatten, Layer, dense_bwd_params_group, dw_split_k, gemm_dx
 from .tensor import ParamArena, to_device, device
 from .utils import complex_json_deserializer, complex_json_serializer, flatten_dict, merge_dicts
 
@@ -296,9 +296,16 @@ class BertEmbeddings:
         self._stash = (input_ids, token_type_ids, p_hid, seed)
         return bb["y"]
 
-    def backward(self, dy, accumulate=False, deterministic=False):
+    def backward(self, dy, accumulate=False, deterministic=False, word_grad_holds_tied_share=False):
+        """`word_grad_holds_tied_share`: emb.word's gradient window already holds this step's share of a tied decoder
+        (BertForMaskedLM) and is added to, whatever `accumulate` says; the four small windows are still overwritten
+        unless `accumulate` (the kernel has one flag for all five, so they are zeroed and accumulated into)."""
         ids, tts, p_hid, seed = self._stash
         bb = self._bufs
+        if word_grad_holds_tied_share and not accumulate:
+            for v in (self.pos, self.type, self.ln_g, self.ln_b):
+                v.grad.zero_()
+            accumulate = True
         ops.embed_ln_bwd(dy, ids, tts, self.word.value, self.pos.value, self.type.value, self.ln_g.value,
                          bb["mean"], bb["rstd"], self.word.grad, self.pos.grad, self.type.grad,
                          self.ln_g.grad, self.ln_b.grad, accumulate=accumulate, deterministic=deterministic,
@@ -549,9 +556,10 @@ class BertModel(SavableModel):
             return BaseModelOutputWithPooling(last_hidden_state=h3, pooler_output=self.pooler.forward(h3[:, 0, :], training))
         return BaseModelOutputWithPooling(last_hidden_state=h3, pooler_output=h3[:, 0, :])
 
-    def backward(self, dy=None, accumulate=False, dpooled=None):
+    def backward(self, dy=None, accumulate=False, dpooled=None, word_grad_holds_tied_share=False):
         """dy: gradient wrt the logits [B,S,C] (head) or wrt last_hidden_state [B,S,H] (None = zero);
-        dpooled: gradient wrt pooler_output [B,H] (models with the HF pooler, or the raw [CLS] slice)."""
+        dpooled: gradient wrt pooler_output [B,H] (models with the HF pooler, or the raw [CLS] slice);
+        word_grad_holds_tied_share: see BertEmbeddings.backward (default: today's behaviour)."""
         B, S = self._shape
         H = self.config.hidden_size
         if self.head is not None:
@@ -592,7 +600,7 @@ class BertModel(SavableModel):
         for lay in pending:
             retire(lay)
         if self.embeddings is not None:
-            self.embeddings.backward(dy, accumulate, self.deterministic)
+            self.embeddings.backward(dy, accumulate, self.deterministic, word_grad_holds_tied_share)
             self._notify(self.embeddings.variables())
             return None
         return dy.view(B, S, -1)
@@ -625,6 +633,205 @@ def bert_model(**kw):
     cfg = BertConfig(**{k: kw[k] for k in cfg_keys if k in kw})
     return BertModel(cfg, compute_dtype=kw.get("compute_dtype", "bf16"), num_labels=kw.get("num_labels"),
                      seed=kw.get("seed", 1234), add_pooling_layer=kw.get("add_pooling_layer", False))
+
+
+_BERT_CFG_KEYS = ("vocab_size", "hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size",
+                  "max_position_embeddings", "type_vocab_size", "layer_norm_eps", "hidden_dropout_prob",
+                  "attention_probs_dropout_prob", "_name_or_path")
+
+
+class BertForMaskedLM(SavableModel):
+    """BERT with the masked-LM head of HF BertForMaskedLM (cls.predictions): Dense(H -> H, gelu) -> LayerNorm -> decoder
+    against the WORD-EMBEDDING TABLE (tied: there is no second matrix) + a vocabulary bias.  The step before every
+    fine-tuning task of this engine: continued pre-training of a checkpoint on the user's own corpus.
+
+    One arena: the encoder's variables first, then mlm.dense.{w,b}, mlm.ln.{g,b}, mlm.bias -- the head has the highest
+    offsets and is reported final first, the descending order the bucketed reducer and the in-backward optimizer update
+    expect.  Only the masked positions are projected onto the vocabulary: `masked_positions` int32 [B, P] (position in
+    the sequence, -1 = unused slot; P fixed per dataset, BERT's max_predictions_per_seq, so every buffer is static)
+    picks [B P, H] rows out of the encoder output (polus_gather_rows), and the call returns logits [B, P, V] in the
+    compute dtype, a view of a buffer whose rows start on 16-byte boundaries.  Unused slots see a zero hidden row; their
+    labels must be negative (polus_amd.data.mask_tokens pads both with -1).
+
+    backward(dlogits): the decoder's weight gradient dlogits^T . t goes straight into emb.word's gradient window, then
+    the embedding backward ADDS its scatter to it, and only then is the window reported final.
+    bf16 engine: emb.word is not a GEMM weight of the arena, so the fused AdamW does not refresh its bf16 shadow; the
+    decoder reads a model-owned bf16 copy of the table, re-cast from the f32 master at every forward pass."""
+
+    def __init__(self, cfg, compute_dtype="bf16", seed=1234, name="bert_for_masked_lm"):
+        super().__init__(name)
+        self.config = cfg
+        self.compute_dtype = COMPUTE_DTYPES[compute_dtype]
+        mode = "bf16" if self.compute_dtype == torch.bfloat16 else "f32"
+        self.savable_config = {"func_name": "bert_for_masked_lm", "model": dict(cfg.to_dict(), compute_dtype=mode, seed=seed)}
+        self.arena = ParamArena(self.compute_dtype)
+        self.bert = BertModel(cfg, compute_dtype=mode, seed=seed, arena=self.arena, with_embeddings=True)
+        self.bert.grad_ready_hook = self.__dict__.get("_hook")
+        H, V = cfg.hidden_size, cfg.vocab_size
+        self.dense = Dense(H, activation="gelu", name="mlm.dense")
+        self.dense.build(self.arena, H, "mlm.dense")
+        self.ln_g = self.arena.add("mlm.ln.g", (H,), np.ones(H, np.float32), decay=False)
+        self.ln_b = self.arena.add("mlm.ln.b", (H,), np.zeros(H, np.float32), decay=False)
+        self.bias = self.arena.add("mlm.bias", (V,), np.zeros(V, np.float32), decay=False)
+        self.arena.finalize()
+        self._bufs = {}
+        self._table = None
+
+    # the trainer sets the hook on the model it holds; the encoder inside reports its own windows
+    @property
+    def grad_ready_hook(self):
+        return self.__dict__.get("_hook")
+
+    @grad_ready_hook.setter
+    def grad_ready_hook(self, hook):
+        self.__dict__["_hook"] = hook
+        if "bert" in self.__dict__:
+            self.bert.grad_ready_hook = hook
+
+    @property
+    def dropout_step(self):
+        return self.bert.dropout_step
+
+    @dropout_step.setter
+    def dropout_step(self, step):
+        self.bert.dropout_step = step
+
+    def head_variables(self):
+        return self.dense.variables() + [self.ln_g, self.ln_b, self.bias]
+
+    def load_numpy_params(self, params):
+        """params: dict in the emb.* / layer{i}.* / mlm.* naming (checkpoint.hf_state_to_params); names it lacks keep
+        their values."""
+        for v in self.arena.vars:
+            if v.name in params:
+                v.assign(params[v.name])
+
+    def encoder_params(self):
+        """The encoder's weights as the dict BertModel.load_numpy_params takes (emb.*, layer{i}.*): the pre-trained
+        encoder goes straight into a BertModel(num_labels=...), a DualEncoder or split_bert_model."""
+        return {v.name: v.numpy() for v in self.arena.vars if v.name.startswith(("emb.", "layer"))}
+
+    def _buf(self, key, shape, dtype):
+        t = self._bufs.get(key)
+        if t is None or t.shape != tuple(shape) or t.dtype != dtype:
+            t = self._bufs[key] = torch.empty(tuple(shape), dtype=dtype, device=self.arena.device)
+        return t
+
+    def _flat_positions(self, masked_positions, B, S):
+        """[B P] int32 rows of the [B S, H] encoder output, -1 for unused slots.  Host arrays are checked: a position
+        outside the sequence or repeated inside a row is an error (a repeat would count one token's loss twice while
+        the scatter of the backward pass keeps only the last of the two gradient rows)."""
+        dev = self.arena.device
+        if isinstance(masked_positions, torch.Tensor) and masked_positions.is_cuda:
+            mp = masked_positions.to(torch.int32)
+            base = torch.arange(B, dtype=torch.int32, device=dev).unsqueeze(1) * S
+            return torch.where(mp >= 0, mp + base, torch.full_like(mp, -1)).reshape(-1).contiguous()
+        mp = _to_numpy(masked_positions).astype(np.int64)
+        if mp.ndim != 2 or mp.shape[0] != B:
+            raise ValueError(f"masked_positions must be [B, P] with B = {B}, got {mp.shape}")
+        if (mp >= S).any():
+            raise ValueError(f"masked_positions holds a position >= the sequence length {S}")
+        for b in range(B):
+            used = mp[b][mp[b] >= 0]
+            if np.unique(used).size != used.size:
+                raise ValueError(f"masked_positions row {b} repeats a position")
+        flat = np.where(mp >= 0, mp + np.arange(B)[:, None] * S, -1).astype(np.int32).reshape(-1)
+        return to_device(flat, torch.int32, dev)
+
+    def decoder_table(self):
+        """The decoder's B operand: the f32 word table, or a fresh bf16 copy of it."""
+        word = self.bert.embeddings.word
+        if self.compute_dtype == torch.float32:
+            return word.value
+        if self._table is None:
+            self._table = torch.empty(word.shape, dtype=torch.bfloat16, device=self.arena.device)
+        ops.cast(word.value, self._table)
+        return self._table
+
+    def call(self, input_ids=None, attention_mask=None, token_type_ids=None, masked_positions=None, training=False, **kw):
+        if isinstance(input_ids, dict):
+            d = input_ids
+            input_ids, attention_mask = d.get("input_ids"), d.get("attention_mask", attention_mask)
+            token_type_ids = d.get("token_type_ids", token_type_ids)
+            masked_positions = d.get("masked_positions", masked_positions)
+        if masked_positions is None:
+            raise ValueError("BertForMaskedLM needs masked_positions [B, P] (polus_amd.data.mask_tokens makes them)")
+        cfg, dt = self.config, self.compute_dtype
+        H, V = cfg.hidden_size, cfg.vocab_size
+        out = self.bert(input_ids=input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids, training=training)
+        B, S = self.bert._shape
+        self.tokens_per_step = self.bert.tokens_per_step
+        hidden = out.last_hidden_state.view(B * S, H)
+        flat = self._flat_positions(masked_positions, B, S)
+        R = flat.numel()
+        P = R // B
+        hm = ops.gather_rows(hidden, flat, self._buf("hm", (R, H), dt))
+        buf = self.head_forward(hm, training)
+        self._stash = (flat, B, S, P) if training else None
+        return buf.as_strided((B, P, V), (P * buf.stride(0), buf.stride(0), 1))
+
+    def head_forward(self, hm, training=False):
+        """hm [R, H] (compute dtype, contiguous) -> logits [R, V], a view of a buffer whose row stride is a whole number
+        of 16-byte chunks (the loss kernel's wide accesses)."""
+        cfg, dt = self.config, self.compute_dtype
+        H, V, R = cfg.hidden_size, cfg.vocab_size, hm.shape[0]
+        t0 = self.dense.forward(hm, training)
+        t, mean, rstd = self._buf("t", (R, H), dt), self._buf("mean", (R,), torch.float32), self._buf("rstd", (R,), torch.float32)
+        ops.layernorm_fwd(t0, self.ln_g.value, self.ln_b.value, t, mean, rstd, cfg.layer_norm_eps)
+        es = 2 if dt == torch.bfloat16 else 4
+        ld = (V * es + 15) // 16 * 16 // es
+        buf = self._buf("logits", (R, ld), dt)
+        table = self.decoder_table()
+        ops.gemm(t, table, buf[:, :V], bias=self.bias.value)
+        self._head_stash = (t0, t, mean, rstd, table) if training else None
+        return buf[:, :V]
+
+    def head_backward(self, d2, accumulate=False):
+        """d2 [R, V] (row stride free) -> dhm [R, H].  The head's gradients are final afterwards; emb.word's window holds the
+        decoder's share dlogits^T . t (overwritten, or added with `accumulate`) and still waits for the embedding's."""
+        t0, t, mean, rstd, table = self._head_stash
+        cfg, dt = self.config, self.compute_dtype
+        H, V, R = cfg.hidden_size, cfg.vocab_size, d2.shape[0]
+        word = self.bert.embeddings.word
+        ops.dense_bwd_params(d2, t, word.grad, self.bias.grad, accumulate, dw_split_k(V, H, R))
+        dt_ = self._buf("dt", (R, H), dt)
+        ops.gemm(d2, table, dt_, b_layout=ops.K_STRIDED)
+        dt0 = self._buf("dt0", (R, H), dt)
+        ops.layernorm_bwd(dt_, t0, self.ln_g.value, mean, rstd, dt0, self.ln_g.grad, self.ln_b.grad, None, accumulate)
+        return self.dense.backward(dt0, accumulate)
+
+    def backward(self, dlogits, accumulate=False):
+        """dlogits [B, P, V] in the compute dtype (the in-place gradient of MaskedSparseCategoricalCrossentropy: the
+        logits buffer itself).  Parameter gradients land in the arena, overwritten or, with `accumulate`, added to."""
+        if self._stash is None:
+            raise RuntimeError("BertForMaskedLM.backward: the last forward pass ran with training=False (nothing was kept for backward)")
+        flat, B, S, P = self._stash
+        cfg, dt = self.config, self.compute_dtype
+        H, V, R = cfg.hidden_size, cfg.vocab_size, B * P
+        if dlogits.dtype != dt:
+            raise TypeError(f"BertForMaskedLM.backward: dlogits must be {dt} (the logits' dtype), got {dlogits.dtype}")
+        st = dlogits.stride()
+        if tuple(dlogits.shape) == (B, P, V) and st[2] == 1 and st[0] == P * st[1]:
+            d2 = dlogits.as_strided((R, V), (st[1], 1))
+        else:
+            d2 = dlogits.reshape(R, V).contiguous()
+        # 1.-4. decoder dW into emb.word's window, dX through the table, LayerNorm, Dense
+        dhm = self.head_backward(d2, accumulate)
+        # 5. the head is final; emb.word is NOT: the embedding backward still adds to it
+        self._notify(self.head_variables())
+        # 6. scatter through the inverse map: every row of dh written, no atomics
+        inv = ops.inverse_map(flat, self._buf("inv", (B * S,), torch.int32))
+        dh = ops.gather_rows(dhm, inv, self._buf("dh", (B * S, H), dt))
+        # 7. the encoder; its last report (the embeddings) carries both shares of emb.word
+        self.bert.deterministic = self.deterministic
+        return self.bert.backward(dh.view(B, S, H), accumulate=accumulate, word_grad_holds_tied_share=True)
+
+
+@from_config
+def bert_for_masked_lm(**kw):
+    """Builder behind BertForMaskedLM.save / load_model: BertConfig fields + compute_dtype, seed."""
+    cfg = BertConfig(**{k: kw[k] for k in _BERT_CFG_KEYS if k in kw})
+    return BertForMaskedLM(cfg, compute_dtype=kw.get("compute_dtype", "bf16"), seed=kw.get("seed", 1234))
 
 
 class TFBertSplited(PolusModel):

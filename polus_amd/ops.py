@@ -352,6 +352,78 @@ def sigmoid_xent(logits, y_true, class_weights, negative_weight, loss, dlogits):
                                  rows, C, ptr(ws), nb, _st()), "polus_sigmoid_xent")
 
 
+XentWideRoute = collections.namedtuple("XentWideRoute", "path vec16 lds_bytes")
+XENT_WIDE_PATHS = ("staged", "streaming")
+
+
+def _xent_wide_args(logits, dlogits, rows, V):
+    dlogits = logits if dlogits is None else dlogits
+    assert logits.dim() == 2 and dlogits.dim() == 2 and dlogits.dtype == logits.dtype
+    assert (logits.stride(1) == 1 or logits.shape[1] == 1) and (dlogits.stride(1) == 1 or dlogits.shape[1] == 1), \
+        "softmax_xent_wide: the class axis must be contiguous"
+    rows = logits.shape[0] if rows is None else rows
+    V = logits.shape[1] if V is None else V
+    assert dlogits.shape[0] >= rows and dlogits.shape[1] >= V
+    # the stride of a single row is never used: report one that is legal
+    ldl = logits.stride(0) if logits.shape[0] > 1 else max(logits.stride(0), V)
+    lddl = dlogits.stride(0) if dlogits.shape[0] > 1 else max(dlogits.stride(0), V)
+    return dlogits, rows, V, ldl, lddl
+
+
+def softmax_xent_wide_route(logits, dlogits=None, rows=None, V=None):
+    """What `softmax_xent_wide` runs for these tensors (polus_softmax_xent_wide_route): path "staged" or "streaming",
+    whether it moves 16 bytes per lane, and the dynamic LDS bytes; launches nothing and reads no memory, so host
+    tensors do (they count for their address and strides alone)."""
+    dlogits, rows, V, ldl, lddl = _xent_wide_args(logits, dlogits, rows, V)
+    r = (ctypes.c_int * 3)()
+    check(_lib.load().polus_softmax_xent_wide_route(dtype_code(logits.dtype), ptr(logits), ldl, ptr(dlogits), lddl,
+                                                    rows, V, r), "polus_softmax_xent_wide_route")
+    return XentWideRoute(XENT_WIDE_PATHS[r[0]], bool(r[1]), r[2])
+
+
+def softmax_xent_wide(logits, labels, loss, dlogits=None, stats=None, rows=None, V=None):
+    """loss (f32 [1]) = mean over the counted rows of -log softmax(logits)[label]; dlogits (None: in place, into logits)
+    = its gradient.  logits f32 or bf16 [rows, V] with any row stride; labels int32 [rows]: < 0 ignores the row,
+    >= V ignores it and counts it in stats[1]; stats int32 [2] = {counted, rejected} (include/polus_hip.h
+    polus_softmax_xent_wide)."""
+    lib = _lib.load()
+    _req_cuda(logits, labels, loss, dlogits, stats)
+    dlogits, rows, V, ldl, lddl = _xent_wide_args(logits, dlogits, rows, V)
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() >= rows
+    assert loss.dtype == torch.float32 and loss.numel() >= 1
+    assert stats is None or (stats.dtype == torch.int32 and stats.numel() >= 2 and stats.is_contiguous())
+    nb = lib.polus_softmax_xent_wide_workspace_bytes(rows)
+    ws = workspace(logits.device).get(nb)
+    check(lib.polus_softmax_xent_wide(dtype_code(logits.dtype), ptr(logits), ldl, ptr(labels), ptr(loss), ptr(dlogits), lddl,
+                                      ptr(stats), rows, V, ptr(ws), nb, _st()), "polus_softmax_xent_wide")
+    return dlogits
+
+
+def gather_rows(x, idx, y, n=None):
+    """y[i] = x[idx[i]] where 0 <= idx[i] < x.shape[0], a zero row otherwise; x [rows, H], y [n, H] f32 or bf16 with free row
+    strides, idx int32 [n] (include/polus_hip.h polus_gather_rows).  With idx = inverse_map(...) it is the scatter."""
+    _req_cuda(x, idx, y)
+    assert x.dim() == 2 and y.dim() == 2 and y.dtype == x.dtype and y.shape[1] == x.shape[1]
+    assert (x.stride(1) == 1 or x.shape[1] == 1) and (y.stride(1) == 1 or y.shape[1] == 1)
+    n = idx.numel() if n is None else n
+    assert idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() >= n and y.shape[0] >= n
+    rows, H = x.shape
+    ldx = x.stride(0) if rows > 1 else max(x.stride(0), H)
+    ldy = y.stride(0) if y.shape[0] > 1 else max(y.stride(0), H)
+    check(_lib.load().polus_gather_rows(dtype_code(x.dtype), ptr(x), ldx, ptr(idx), ptr(y), ldy, n, rows, H, _st()),
+          "polus_gather_rows")
+    return y
+
+
+def inverse_map(idx, inv):
+    """inv[j] (int32 [rows]) = the last i with idx[i] == j, else -1; entries of idx outside [0, rows) are skipped
+    (include/polus_hip.h polus_inverse_map)."""
+    _req_cuda(idx, inv)
+    assert idx.dtype == torch.int32 and inv.dtype == torch.int32 and idx.is_contiguous() and inv.is_contiguous()
+    check(_lib.load().polus_inverse_map(ptr(idx), idx.numel(), ptr(inv), inv.numel(), _st()), "polus_inverse_map")
+    return inv
+
+
 def _crf_arg(name, t, dtype, shape, optional=False):
     """The CRF kernels index their arguments as dense arrays of one element type: anything else is read as garbage."""
     if t is None:
