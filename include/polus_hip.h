@@ -497,6 +497,72 @@ int polus_centroid_codes(const float* sim, long lds, const int32_t* mask, uint16
 int polus_centroid_update(int dtype, const void* x, const uint16_t* codes, const void* prev, void* out,
                           int32_t* counts, int T, int K, int E, float eps, void* stream);
 
+/* ---- learned sparse retrieval, SPLADE (splade.hip; no counterpart in the reference, whose first stages are dense).
+ * A text becomes one non-negative vector over the vocabulary, rep[v] = max over its valid tokens s of
+ * log(1 + relu(logit[s, v])), from the masked-LM logits of all its tokens.  log1p is monotone: the maximum is taken
+ * over the stored values and log1pf is applied once.
+ *
+ * polus_splade_pool_fwd:
+ *   logits [B*S, V] in `dtype` (f32 or bf16), row stride ldl;  mask int32 [B, S] contiguous, NULL = every token valid
+ *   rep, xmax f32 [B, V] (row strides ldr, ldx);  arg int32 [B, V] (row stride lda)
+ *   per (b, v):  m = the maximum of logits[b*S + s, v] over the s with mask[b, s] != 0, arg = the lowest s attaining m;
+ *                no valid token or m <= 0:  rep = 0, xmax = 0, arg = -1;   otherwise rep = log1pf(m), xmax = m.
+ *   Comparisons are `>`: a NaN never wins (a column of NaN gives (0, 0, -1)).  One read of the valid rows of logits, a
+ *   masked row is not read at all; columns past V of the outputs are not written.
+ * polus_splade_pool_bwd:
+ *   dlogits[b*S + s, v] = (s == arg[b, v]) ? T(drep[b, v] / (1 + xmax[b, v])) : 0 for EVERY s < S, masked rows included:
+ *   IEEE f32 addition and division, rounded once to `dtype`.  Columns past V of a row are not touched.  Nothing of the
+ *   logits is read, so dlogits may be the logits buffer of the forward pass.  Write-only traffic but for the three
+ *   [B, V] inputs.
+ * Both: a lane owns one 16-byte chunk of columns of one sequence and walks its S rows; grid (chunks / 256, B).  16-byte
+ * accesses of logits / dlogits where the pointer and ldl * sizeof(T) are multiples of 16, single elements otherwise and
+ * for the columns behind the last whole chunk; 16-byte accesses of the [B, V] arrays where all three are 16-byte
+ * aligned with strides that are multiples of 4.  The results are the same bits on every access route.  No atomics, no
+ * workspace, no scratch, bitwise reproducible.
+ * Limits (refused before any launch): dtype f32 or bf16; 1 <= B <= 65535; S >= 1; V >= 1; every row stride >= V;
+ * non-null pointers (mask aside), each aligned to its element.
+ *
+ * polus_flops_reg, the FLOPS sparsity regulariser of SPLADE over the rows [0, rows) of rep (f32, row stride ldr):
+ *   colmean[v] = (sum over b of rep[b, v]) / rows;   value = lambda * sum over v of colmean[v]^2
+ *   loss[0] = value, or loss[0] += value with loss_accumulate != 0 (device f32; this is how a trainer adds the
+ *   regulariser to its loss without a host round trip);
+ *   drep != NULL:  drep[b, v] += (lambda * (2 / rows)) * colmean[v]  for b < rows, v < V  (f32, row stride lddr).
+ * Queries and documents take one call each, on their own rows and with their own lambda.  Order: a column is summed in
+ * ascending b by one lane; lane l of workgroup k (one wave) holds columns 256 k + 4 l .. + 3 and adds their four
+ * squares in ascending v, a wave's 64 sums go through one xor-shuffle tree into workspace[k], and a second launch adds
+ * the ceil(V / 256) partials in index order.  The order does not depend on alignment (which only selects 16-byte or
+ * 4-byte accesses).  No atomics, bitwise reproducible.
+ * Limits (refused before any launch): rows >= 1; V >= 1; ldr >= V; lddr >= V with drep; rep, loss non-null;
+ * drep != rep; workspace >= polus_flops_reg_workspace_bytes(V) (host only).
+ *
+ * polus_sparse_scores, sparse documents against dense queries (the search of a SPLADE index):
+ *   q f32 [B, V] (row stride ldq): the queries' representations, dense;
+ *   ids int32 and w f32 [N, M] (row strides ldi, ldw): the M (term, weight) pairs kept per document;
+ *   score[b*lds + n] = sum over m with 0 <= ids[n, m] < V of  w[n, m] * q[b, ids[n, m]]
+ * An id outside [0, V), -1 included, is skipped: its weight is read, nothing of q is dereferenced for it.  A term
+ * that occurs twice counts twice.  One workgroup (16 waves) per (query, contiguous range of documents, sized so that
+ * a launch has about four workgroups per CU and a range at least 8 documents per wave) copies the query row into
+ * dynamic LDS, V * 4 bytes rounded up to 16, which is all the LDS the kernel uses: V * 4 <= 163840 (160 KiB, one CU's
+ * LDS), i.e. V <= 40960; V = 30522 takes 122088 bytes.  A wider vocabulary is refused: there is no global-memory
+ * route.  A wave owns a document (and works on eight of its documents at a time, to have their loads in flight
+ * together; a document's arithmetic does not depend on the others).  Summation order: lane l runs p = fmaf(w[n, m], q[b, ids[n, m]], p) from p = 0 over
+ * m = l, l + 64, l + 128, ... in ascending m (skipped terms leave p as it is), then the 64 lane sums are added by the
+ * xor-shuffle tree with offsets 32, 16, 8, 4, 2, 1.  The bits of an entry therefore depend on the query row, the
+ * document's row and M alone: not on B, N, the range of documents of the launch, the grid or the device.  Columns of
+ * score past N are not written.  No atomics, no workspace, bitwise reproducible.
+ * Limits (refused before any launch): 1 <= M <= 1024 (what polus_topk_merge can keep); B >= 1; N >= 1 (documents are
+ * addressed with 64 bits); V >= 1 and V * 4 <= 163840; ldq >= V; ldi, ldw >= M; lds >= N; B * ceil(N / range) < 2^31;
+ * non-null pointers. */
+int polus_splade_pool_fwd(int dtype, const void* logits, long ldl, const int32_t* mask, float* rep, long ldr,
+                          float* xmax, long ldx, int32_t* arg, long lda, int B, int S, int V, void* stream);
+int polus_splade_pool_bwd(int dtype, const float* drep, long lddr, const float* xmax, long ldx, const int32_t* arg,
+                          long lda, void* dlogits, long lddl, int B, int S, int V, void* stream);
+size_t polus_flops_reg_workspace_bytes(int V);
+int polus_flops_reg(const float* rep, long ldr, int rows, int V, float lambda, float* loss, int loss_accumulate,
+                    float* drep, long lddr, void* workspace, size_t workspace_bytes, void* stream);
+int polus_sparse_scores(const float* q, long ldq, const int32_t* ids, long ldi, const float* w, long ldw,
+                        float* score, long lds, int B, int N, int M, int V, void* stream);
+
 /* ---- argmax over the last axis (PolusClassifier.inference, polus/models.py:148-150) */
 int polus_argmax(const float* x, long ldx, int32_t* out, int rows, int C, void* stream);
 

@@ -85,6 +85,11 @@ SIGNATURES = {
     "polus_centroid_scores": (_i, [_vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _vp]),
     "polus_centroid_codes": (_i, [_vp, _l, _vp, _vp, _i, _i, _vp]),
     "polus_centroid_update": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "polus_splade_pool_fwd": (_i, [_i, _vp, _l, _vp, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _vp]),
+    "polus_splade_pool_bwd": (_i, [_i, _vp, _l, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _vp]),
+    "polus_flops_reg_workspace_bytes": (_sz, [_i]),
+    "polus_flops_reg": (_i, [_vp, _l, _i, _i, _f, _vp, _i, _vp, _l, _vp, _sz, _vp]),
+    "polus_sparse_scores": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i, _vp]),
     "polus_argmax": (_i, [_vp, _l, _vp, _i, _i, _vp]),
     "polus_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64,
                              _f, _f, _f, _f, _f, _f, _f, _vp, _vp]),

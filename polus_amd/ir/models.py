@@ -9,8 +9,10 @@ from collections import namedtuple
 
 import torch
 
+from .. import ops
 from ..layers import Dense
-from ..models import BertModel, PolusModel, COMPUTE_DTYPES
+from ..models import (BertConfig, BertForMaskedLM, BertModel, PolusModel, SavableModel, COMPUTE_DTYPES, from_config,
+                      _BERT_CFG_KEYS)
 from ..tensor import ParamArena, to_device
 
 
@@ -83,3 +85,133 @@ class LateInteractionDualEncoder(DualEncoder):
 
     def document_projection(self, rep, training=False):
         return TokenReps(self.dp.forward(to_device(rep.values, self.compute_dtype, self.arena.device), training), rep.mask)
+
+
+class SpladeEncoder(SavableModel):
+    """Learned sparse retrieval (SPLADE): a text becomes one non-negative f32 vector over the vocabulary,
+    rep[v] = max over its valid tokens s of log(1 + relu(logit[s, v])), from the masked-LM logits of ALL its tokens.
+
+    Built over a BertForMaskedLM and sharing its arena: one bucketed reducer and one fused AdamW cover encoder and head,
+    and the encoder reports its gradient windows as it does under masked-LM training.  `call` runs `mlm.bert`, passes the
+    B S hidden rows through `mlm.head_forward`, pools them (ops.splade_pool_fwd) and returns rep [B, V]; the pooling's
+    maxima and winning tokens are kept for `backward`.  `backward(drep)` writes the pooled gradient in place into the
+    logits buffer (ops.splade_pool_bwd), then follows BertForMaskedLM.backward: head_backward (the decoder's share goes
+    into emb.word's window), the head's windows reported, the encoder's backward with the embedding ADDING its share.
+
+    The logits buffer holds B S ld elements of the compute dtype, ld = V rounded up to whole 16-byte chunks: 1.0 GB in
+    bf16 (2.0 GB in f32) at 64 sequences x 256 tokens x 30522.  The whole batch goes through in one pass: there is no
+    chunking over sequences.  The gradient is dense over [B S, V] although only B V of its entries are non-zero.
+
+    `encode_query` / `encode_document` return a fresh copy of the representations and the projections are the
+    identity, so SparseCorpusIndex and TwoStageSearch drive it like a dual encoder.  Savable: `save` writes the MLM
+    model's config and weights, `load_model(path, external_module=polus_amd.ir.models)` rebuilds it through
+    `splade_encoder`."""
+
+    def __init__(self, mlm, name="splade_encoder"):
+        super().__init__(name)
+        self.mlm = mlm
+        self.arena = mlm.arena
+        self.config = mlm.config
+        self.compute_dtype = mlm.compute_dtype
+        self.savable_config = {"func_name": "splade_encoder", "model": dict(mlm.savable_config["model"])}
+        self.mlm.grad_ready_hook = self.__dict__.get("_hook")
+        self._bufs = {}
+        self._stash = None
+
+    # the trainer sets these on the model it holds; the encoder inside reads them
+    @property
+    def grad_ready_hook(self):
+        return self.__dict__.get("_hook")
+
+    @grad_ready_hook.setter
+    def grad_ready_hook(self, hook):
+        self.__dict__["_hook"] = hook
+        if "mlm" in self.__dict__:
+            self.mlm.grad_ready_hook = hook
+
+    @property
+    def dropout_step(self):
+        return self.mlm.bert.dropout_step
+
+    @dropout_step.setter
+    def dropout_step(self, step):
+        self.mlm.bert.dropout_step = step
+
+    @property
+    def overlap_dw(self):
+        return self.mlm.bert.overlap_dw
+
+    @overlap_dw.setter
+    def overlap_dw(self, on):
+        self.mlm.bert.overlap_dw = on
+
+    @property
+    def graph_seeds(self):
+        return getattr(self.mlm.bert, "graph_seeds", False)
+
+    @graph_seeds.setter
+    def graph_seeds(self, on):
+        self.mlm.bert.graph_seeds = on
+
+    def site_seed(self, layer, site, step=None):
+        return self.mlm.bert.site_seed(layer, site, step)
+
+    def load_numpy_params(self, params):
+        self.mlm.load_numpy_params(params)
+
+    def _buf(self, key, shape, dtype):
+        t = self._bufs.get(key)
+        if t is None or t.shape != tuple(shape) or t.dtype != dtype:
+            t = self._bufs[key] = torch.empty(tuple(shape), dtype=dtype, device=self.arena.device)
+        return t
+
+    def call(self, input_ids=None, attention_mask=None, token_type_ids=None, training=False, **kw):
+        if isinstance(input_ids, dict):
+            d = input_ids
+            input_ids, attention_mask = d.get("input_ids"), d.get("attention_mask", attention_mask)
+            token_type_ids = d.get("token_type_ids", token_type_ids)
+        mlm, V, H = self.mlm, self.config.vocab_size, self.config.hidden_size
+        if attention_mask is not None:
+            attention_mask = to_device(attention_mask, torch.int32, self.arena.device)
+        out = mlm.bert(input_ids=input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids, training=training)
+        B, S = mlm.bert._shape
+        self.tokens_per_step = mlm.bert.tokens_per_step
+        logits = mlm.head_forward(out.last_hidden_state.view(B * S, H), training)
+        rep, xmax = self._buf("rep", (B, V), torch.float32), self._buf("xmax", (B, V), torch.float32)
+        arg = self._buf("arg", (B, V), torch.int32)
+        ops.splade_pool_fwd(logits, None if attention_mask is None else attention_mask.reshape(B, S), rep, xmax, arg, B, S)
+        self._stash = (logits, xmax, arg, B, S) if training else None
+        return rep
+
+    def backward(self, drep, accumulate=False):
+        """drep f32 [B, V]: the gradient wrt the representations of the last training forward pass.  Parameter
+        gradients land in the arena, overwritten or, with `accumulate`, added to."""
+        if self._stash is None:
+            raise RuntimeError("SpladeEncoder.backward: the last forward pass ran with training=False (nothing was kept for backward)")
+        logits, xmax, arg, B, S = self._stash
+        mlm, H = self.mlm, self.config.hidden_size
+        if drep.dtype != torch.float32 or tuple(drep.shape) != tuple(xmax.shape):
+            raise TypeError(f"SpladeEncoder.backward: drep must be float32 {tuple(xmax.shape)}, got {drep.dtype} {tuple(drep.shape)}")
+        ops.splade_pool_bwd(drep, xmax, arg, logits, B, S)            # in place: backward needs nothing of the logits
+        dh = mlm.head_backward(logits, accumulate)
+        self._notify(mlm.head_variables())                            # emb.word still waits for the embedding's share
+        mlm.bert.deterministic = self.deterministic
+        return mlm.bert.backward(dh.view(B, S, H), accumulate=accumulate, word_grad_holds_tied_share=True)
+
+    def encode_query(self, x, training=False):
+        rep = self(**x, training=training) if isinstance(x, dict) else self(x, training=training)
+        return rep if training else rep.clone()                       # a fresh buffer (the encoder reuses its own)
+
+    encode_document = encode_query
+
+    def query_projection(self, rep, training=False):
+        return rep
+
+    document_projection = query_projection
+
+
+@from_config
+def splade_encoder(**kw):
+    """Builder behind SpladeEncoder.save / load_model: the BertForMaskedLM's BertConfig fields + compute_dtype, seed."""
+    cfg = BertConfig(**{k: kw[k] for k in _BERT_CFG_KEYS if k in kw})
+    return SpladeEncoder(BertForMaskedLM(cfg, compute_dtype=kw.get("compute_dtype", "bf16"), seed=kw.get("seed", 1234)))

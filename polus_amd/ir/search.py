@@ -436,6 +436,113 @@ class CorpusIndex:
         return self._rerank_encoded(q, cand_id, k)
 
 
+class SparseCorpusIndex:
+    """A learned sparse (SPLADE) first stage: per document the `terms` best (term id, weight) pairs of its vocabulary
+    representation, int32 ids [N, terms] and f32 weights [N, terms] in growing device buffers; queries stay dense.
+
+    `model` is a SpladeEncoder (anything whose encode_document / encode_query give f32 [n, V]).  The contracts of
+    `add(documents) -> ids` and `search(queries, k) -> (scores, ids)` are CorpusIndex's, so it serves as the first
+    stage of TwoStageSearch and under a validation callback.  `add` keeps a document's terms with ops.topk_merge, each
+    row of the representations one "query" of that kernel: weight descending, ties to the lower term id, and a
+    document with fewer than `terms` entries (V < terms) is padded with (-inf, -1), slots ops.sparse_scores skips by
+    their id.  Zero weights are kept when nothing better is left: they add nothing.
+    `search` scores chunks of documents with ops.sparse_scores and merges them with ops.topk_merge, the loop of
+    CorpusIndex.search.  `scratch_bytes` bounds the [Q, n] f32 score buffer of one chunk.
+    Not measured: retrieval quality and how sparse the representations of a trained model are on a real collection."""
+
+    def __init__(self, model, terms=128, scratch_bytes=256 << 20):
+        if not 1 <= int(terms) <= MAX_K:
+            raise ValueError(f"need 1 <= terms <= {MAX_K}, the limit of ops.topk_merge, which keeps them (got {terms})")
+        self.model, self.terms, self.scratch_bytes = model, int(terms), int(scratch_bytes)
+        self.clear()
+
+    def clear(self):
+        """Empty the index (the storage is released)."""
+        self._ids = self._w = None
+        self._n = 0
+
+    def __len__(self):
+        return self._n
+
+    @property
+    def term_ids(self):
+        """int32 [N, terms]: a view of the stored term ids, -1 in unused slots."""
+        return None if self._ids is None else self._ids[:self._n]
+
+    @property
+    def weights(self):
+        """f32 [N, terms]: a view of the stored weights, -inf in unused slots."""
+        return None if self._w is None else self._w[:self._n]
+
+    @property
+    def nbytes(self):
+        """Bytes of the stored ids and weights of the len(index) documents."""
+        return 0 if self._ids is None else self._n * self.terms * (self._ids.element_size() + self._w.element_size())
+
+    def _grow(self, need, dev):
+        cap = 0 if self._ids is None else self._ids.shape[0]
+        if need <= cap:
+            return
+        cap = max(need, 2 * cap)
+        ids = torch.full((cap, self.terms), -1, dtype=torch.int32, device=dev)
+        w = torch.zeros((cap, self.terms), dtype=torch.float32, device=dev)
+        if self._n:
+            ids[:self._n].copy_(self._ids[:self._n])
+            w[:self._n].copy_(self._w[:self._n])
+        self._ids, self._w = ids, w
+
+    def add(self, documents):
+        """Encode a batch of documents, keep each one's `terms` best entries and append them; returns the batch's ids,
+        the consecutive int32 positions in the index."""
+        model = self.model
+        rep = model.document_projection(model.encode_document(documents, training=False), training=False)
+        if rep.dim() != 2 or rep.dtype != torch.float32:
+            raise ValueError(f"a sparse index holds f32 [n, V] vocabulary representations (got {rep.dtype} {tuple(rep.shape)})")
+        n, V = rep.shape
+        if getattr(self, "_V", V) != V and self._n:
+            raise ValueError(f"the index holds representations over {self._V} terms, the batch has {V}")
+        self._V = V
+        self._grow(self._n + n, rep.device)
+        vals = torch.empty((n, self.terms), dtype=torch.float32, device=rep.device)
+        ids = torch.empty((n, self.terms), dtype=torch.int32, device=rep.device)
+        ops.topk_merge(rep, vals, ids, init=True)
+        self._ids[self._n:self._n + n].copy_(ids)
+        self._w[self._n:self._n + n].copy_(vals)
+        out = torch.arange(self._n, self._n + n, dtype=torch.int32, device=rep.device)
+        self._n += n
+        return out
+
+    def chunks(self, Q):
+        """[(start, stop), ...]: the document ranges a search with Q queries scores, one launch each (CorpusIndex.chunks)."""
+        per = min(MAX_CHUNK, self.scratch_bytes // (4 * int(Q)))
+        if per < 1:
+            raise ValueError(f"scratch_bytes = {self.scratch_bytes} does not hold the scores of one document for "
+                             f"{Q} queries ({4 * int(Q)} bytes)")
+        return [(s, min(s + per, self._n)) for s in range(0, self._n, per)]
+
+    def encode_queries(self, queries):
+        """The queries' dense f32 [Q, V] representations."""
+        model = self.model
+        return model.query_projection(model.encode_query(queries, training=False), training=False).contiguous()
+
+    def search(self, queries, k):
+        """(scores f32 [Q, k], ids int32 [Q, k]) on the device: per query the k best documents, score descending, ties
+        to the lower id; when the corpus holds fewer than k, the tail is (-inf, -1)."""
+        if self._n == 0:
+            raise ValueError("the index is empty: add documents before searching")
+        q = self.encode_queries(queries)
+        Q = q.shape[0]
+        spans = self.chunks(Q)
+        scratch = torch.empty((Q, max(b - a for a, b in spans)), dtype=torch.float32, device=q.device)
+        top_val = torch.empty((Q, int(k)), dtype=torch.float32, device=q.device)
+        top_id = torch.empty((Q, int(k)), dtype=torch.int32, device=q.device)
+        for a, b in spans:
+            s = scratch[:, :b - a]
+            ops.sparse_scores(q, self._ids[a:b], self._w[a:b], s)
+            ops.topk_merge(s, top_val, top_id, id0=a, init=(a == 0))
+        return top_val, top_id
+
+
 class TwoStageSearch:
     """Retrieve with a cheap index, re-rank with the token index: `first` is anything with search(queries, k) ->
     (scores, ids) and add(documents), in practice a [CLS] CorpusIndex over a DualEncoder; `second` is a token

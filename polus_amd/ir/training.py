@@ -12,7 +12,7 @@ Token-level representations (`TokenReps`, from LateInteractionDualEncoder) take 
 are [(k+1)B, Ld, H] in one buffer, and `MaxSimScores` scores them ColBERT-style."""
 import torch
 
-from .. import ops
+from .. import _lib, ops
 from ..tensor import DeviceScalar, to_device
 from ..training import BaseTrainer
 from .models import TokenReps
@@ -273,3 +273,97 @@ class ContrastiveLoss:
         if self.d.shape[1] == self._split:
             return self.d, None
         return self.d[:, :self._split], self.d[:, self._split:]
+
+
+class SparseRetrievalTrainer(BaseTrainer):
+    """Contrastive training of a SpladeEncoder (polus_amd/ir/models.py) with the FLOPS sparsity regulariser.
+
+    Batches have the shape EfficientDenseRetrievalTrainer takes: (question, positive_doc[, negative_doc]), each
+    {"input_ids", "attention_mask"[, "token_type_ids"]}, the negatives [B, k, L].  Unlike there the encoder is trained:
+    the texts of a step go through it as ONE batch of (2 + k) B sequences (queries, positives, then negative i of every
+    query in block i), so all must be padded to one length.  rep[:B] are the queries, the rest the documents;
+    `compute_scores` (default InBatchDotScores, on the f32 representations with K = V) and ContrastiveLoss score them.
+
+    loss = contrastive + lambda_q FLOPS(queries) + lambda_d FLOPS(documents): ops.flops_reg ADDS each regulariser to the
+    contrastive loss's device scalar (no host round trip), and adds its gradient onto the score gradient in one
+    [(2 + k) B, V] buffer, `drep`, which model.backward takes.  The regulariser values are not kept one by one;
+    `ops.flops_reg` on a slice of `reps`, the representations of the last step, gives one again.  Gradient
+    accumulation, the in-backward optimizer update, the bucketed data-parallel exchange and step-graph replay are
+    BaseTrainer's."""
+
+    def __init__(self, model, optimizer, compute_scores=None, lambda_q=0.0, lambda_d=0.0, loss=None, trainable_weights=None,
+                 **kwargs):
+        self.compute_scores = InBatchDotScores() if compute_scores is None else compute_scores
+        self.lambda_q, self.lambda_d = float(lambda_q), float(lambda_d)
+        self.trainable_weights = model.trainable_weights if trainable_weights is None else trainable_weights
+        self.reps, self._widths = None, {}
+        super().__init__(model, optimizer, ContrastiveLoss() if loss is None else loss, **kwargs)
+
+    def __str__(self):
+        return "SparseRetrievalTrainer"
+
+    @staticmethod
+    def _one_batch(question, positive_doc, negative_doc):
+        """The (2 + k) B sequences of a step as one batch; k."""
+        parts = [question, positive_doc]
+        k = 0
+        L = question["input_ids"].shape[-1]
+        if negative_doc is not None:
+            k = negative_doc["input_ids"].shape[1]
+            parts += [{key: v[:, i] for key, v in negative_doc.items()} for i in range(k)]
+        for p in parts[1:]:
+            if p["input_ids"].shape[-1] != L:
+                raise ValueError(f"the documents are padded to {p['input_ids'].shape[-1]} tokens, the questions to {L}: "
+                                 "one pass through the encoder needs one padded length")
+        keys = [key for key in ("input_ids", "attention_mask", "token_type_ids") if all(key in p for p in parts)]
+        dev = None
+        for p in parts:
+            for key in keys:
+                if torch.is_tensor(p[key]) and p[key].is_cuda:
+                    dev = p[key].device
+        batch = {key: torch.cat([to_device(p[key], torch.int32, dev) for p in parts], 0) for key in keys}
+        return batch, k
+
+    def _gemm_width(self, rep):
+        """The row width the score GEMMs run at: V when ops.gemm_route takes the f32 representations as they are, else
+        V rounded up to whole 16-byte chunks (the caller pads with zero columns, which add nothing to a dot product).
+        Asked once per shape."""
+        B, V = self._B, rep.shape[1]
+        key = (tuple(rep.shape), B, rep.data_ptr() % 16)
+        if key not in self._widths:
+            try:
+                ops.gemm_route(rep[:B], rep[B:], torch.empty((B, rep.shape[0] - B), dtype=torch.float32, device=rep.device))
+                self._widths[key] = V
+            except _lib.PolusHipError:
+                self._widths[key] = (V + 3) // 4 * 4
+        return self._widths[key]
+
+    def forward_with_grads(self, question, positive_doc, negative_doc=None):
+        batch, k = self._one_batch(question, positive_doc, negative_doc)
+        B = question["input_ids"].shape[0]
+        self._B, self._n_neg = B, k
+        rep = self.model(**batch, training=True)                   # f32 [(2 + k) B, V]
+        self.reps = rep
+        W = self._gemm_width(rep)
+        self._V = rep.shape[1]
+        if W != rep.shape[1]:
+            wide = torch.zeros((rep.shape[0], W), dtype=rep.dtype, device=rep.device)
+            wide[:, :rep.shape[1]].copy_(rep)
+            rep = wide
+        negs = [rep[B * (2 + i):B * (3 + i)] for i in range(k)]
+        return self.compute_scores(rep[:B], rep[B:2 * B], *negs)
+
+    def backward_from_loss(self, accumulate=False):
+        B, k, V, rep = self._B, self._n_neg, self._V, self.reps
+        total = self.loss.loss                                       # the contrastive loss's device scalar
+        dpos, dneg = self.loss.backward(accumulate)
+        out = self.compute_scores.backward(dpos, dneg)
+        drep = torch.empty_like(rep)
+        drep[:B].copy_(out[0][:, :V])
+        drep[B:2 * B].copy_(out[1][:, :V])
+        if k:
+            dn = out[2] if torch.is_tensor(out[2]) else torch.stack(list(out[2]), 0)
+            drep[2 * B:].copy_(dn.reshape(k * B, -1)[:, :V])
+        ops.flops_reg(rep[:B], self.lambda_q, total, accumulate=True, drep=drep[:B])
+        ops.flops_reg(rep[B:], self.lambda_d, total, accumulate=True, drep=drep[B:])
+        self.model.backward(drep, accumulate=accumulate)

@@ -650,6 +650,71 @@ def centroid_update(x, codes, prev, out, counts, eps=1e-12):
                                             float(eps), _st()), "polus_centroid_update")
 
 
+def _rows2d(t, dtype, rows, cols, name):
+    """t is a [>= rows, >= cols] matrix of `dtype` with contiguous columns; returns a row stride that is legal for one row too."""
+    assert t.dtype == dtype and t.dim() == 2 and t.shape[0] >= rows and t.shape[1] >= cols, f"{name}: need {dtype} [>= {rows}, >= {cols}], got {t.dtype} {tuple(t.shape)}"
+    assert t.stride(1) == 1 or t.shape[1] == 1, f"{name}: the last axis must be contiguous"
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), cols)
+
+
+def splade_pool_fwd(logits, mask, rep, xmax, arg, B, S):
+    """rep[b, v] = log1p(max(0, max over the valid tokens s of logits[b S + s, v])), with xmax (the maximum, 0 where
+    none is positive) and arg (the lowest winning s, -1 where none) kept for backward.  logits f32 or bf16 [B S, V], any
+    row stride; mask int32 [B, S] or None; rep, xmax f32 and arg int32 [B, V] (include/polus_hip.h
+    polus_splade_pool_fwd)."""
+    _req_cuda(logits, mask, rep, xmax, arg)
+    V = logits.shape[1]
+    ldl = _rows2d(logits, logits.dtype, B * S, V, "logits")
+    ldr, ldx, lda = _rows2d(rep, torch.float32, B, V, "rep"), _rows2d(xmax, torch.float32, B, V, "xmax"), _rows2d(arg, torch.int32, B, V, "arg")
+    assert mask is None or (mask.dtype == torch.int32 and mask.is_contiguous() and mask.numel() == B * S)
+    check(_lib.load().polus_splade_pool_fwd(dtype_code(logits.dtype), ptr(logits), ldl, ptr(mask), ptr(rep), ldr, ptr(xmax), ldx,
+                                            ptr(arg), lda, int(B), int(S), V, _st()), "polus_splade_pool_fwd")
+    return rep
+
+
+def splade_pool_bwd(drep, xmax, arg, dlogits, B, S):
+    """dlogits[b S + s, v] = drep[b, v] / (1 + xmax[b, v]) where s == arg[b, v], 0 elsewhere; every row of dlogits (f32 or
+    bf16 [B S, V], any row stride; may be the forward's logits buffer) is written (include/polus_hip.h
+    polus_splade_pool_bwd)."""
+    _req_cuda(drep, xmax, arg, dlogits)
+    V = dlogits.shape[1]
+    lddl = _rows2d(dlogits, dlogits.dtype, B * S, V, "dlogits")
+    lddr, ldx, lda = _rows2d(drep, torch.float32, B, V, "drep"), _rows2d(xmax, torch.float32, B, V, "xmax"), _rows2d(arg, torch.int32, B, V, "arg")
+    check(_lib.load().polus_splade_pool_bwd(dtype_code(dlogits.dtype), ptr(drep), lddr, ptr(xmax), ldx, ptr(arg), lda,
+                                            ptr(dlogits), lddl, int(B), int(S), V, _st()), "polus_splade_pool_bwd")
+    return dlogits
+
+
+def flops_reg(rep, lam, loss, accumulate=False, drep=None):
+    """loss[0] (=, or += with `accumulate`) lam * sum over v of (mean over the rows of rep[:, v])^2, and with drep
+    (f32, rep's shape) drep += its gradient.  rep f32 [rows, V], any row stride (include/polus_hip.h polus_flops_reg)."""
+    lib = _lib.load()
+    _req_cuda(rep, loss, drep)
+    rows, V = rep.shape
+    ldr = _rows2d(rep, torch.float32, rows, V, "rep")
+    lddr = 0 if drep is None else _rows2d(drep, torch.float32, rows, V, "drep")
+    assert loss.dtype == torch.float32 and loss.numel() >= 1
+    nb = lib.polus_flops_reg_workspace_bytes(V)
+    ws = workspace(rep.device).get(nb)
+    check(lib.polus_flops_reg(ptr(rep), ldr, rows, V, float(lam), ptr(loss), 1 if accumulate else 0, ptr(drep), lddr,
+                              ptr(ws), nb, _st()), "polus_flops_reg")
+
+
+def sparse_scores(q, ids, w, score):
+    """score[b, n] (f32, any row stride >= N) = sum over m with 0 <= ids[n, m] < V of w[n, m] * q[b, ids[n, m]]: N sparse
+    documents of M (term, weight) pairs against B dense queries q f32 [B, V]; ids int32 and w f32 [N, M], any row stride
+    (include/polus_hip.h polus_sparse_scores)."""
+    _req_cuda(q, ids, w, score)
+    B, V = q.shape
+    N, M = ids.shape
+    ldq = _rows2d(q, torch.float32, B, V, "q")
+    ldi, ldw = _rows2d(ids, torch.int32, N, M, "ids"), _rows2d(w, torch.float32, N, M, "w")
+    lds = _rows2d(score, torch.float32, B, N, "score")
+    check(_lib.load().polus_sparse_scores(ptr(q), ldq, ptr(ids), ldi, ptr(w), ldw, ptr(score), lds, B, N, M, V, _st()),
+          "polus_sparse_scores")
+    return score
+
+
 def maxsim_bwd(q, d, dscore, argmax, dq, dd):
     """dq [B, Lq, E] and dd [N, Ld, E] from dscore (f32 [B, N], row stride free) and the forward's argmax; every
     element is written."""
