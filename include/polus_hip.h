@@ -406,6 +406,52 @@ int polus_maxsim_scores_fp8(int dtype, const void* Q, const uint8_t* codes, cons
 int polus_maxsim_rerank_fp8(int dtype, const void* Q, const uint8_t* codes, const float* scale, const int32_t* qmask,
                             const int32_t* dmask, const int32_t* cand, long ldc, float* score, long lds,
                             int B, int C, int N, int Lq, int Ld, int E, void* stream);
+/* ---- Residual-compressed token index (residual.hip; ColBERTv2): a document token is stored as the 16-bit id of its
+ * nearest centroid plus nbits = 1, 2 or 4 bits per dimension that name a bucket of its residual: 2 + E*nbits/8 bytes
+ * per token, 38 at E = 128 and nbits = 2 with the int32 mask, against 260 in bf16 and 136 in FP8.
+ * A codec is
+ *   centroids [K, E] in `dtype` (f32 or bf16), 1 <= K <= 65535;   nbits in {1, 2, 4};
+ *   cutoffs f32 [2^nbits - 1], non-decreasing;   weights f32 [2^nbits];
+ * a token is
+ *   code   uint16: its centroid.  Any code >= K means "no token", 0xFFFF among them, as in polus_centroid_scores;
+ *   packed uint8 [E*nbits/8].
+ * Rules, per element k of a row with code < K:
+ *   residual   r_k = f32(x_k) - f32(centroids[code][k]), one f32 subtraction;
+ *   bucket     bucket_k = the number of cutoffs c_j with r_k > c_j (IEEE comparison): a residual equal to a cutoff goes
+ *              to the lower bucket, NaN to bucket 0, +inf to the top bucket (unless a cutoff is +inf itself);
+ *   packing    element k sits in byte k*nbits/8 (integer division) at bits [nbits*(k mod 8/nbits), +nbits), least
+ *              significant first: at nbits = 2 byte 0 holds elements 0..3, element 0 in bits 0-1;
+ *   decode     y_k = T(f32(centroids[code][k]) + weights[bucket_k]): one f32 addition, then one round-to-nearest-even
+ *              conversion to `dtype` (none for f32).
+ * A row with code >= K: its packed bytes are all zero on compress and its y is all (+0) zeros on decode, and nothing of
+ * centroids is dereferenced for it.  Cutoffs and weights are taken as given (the cutoffs' order is not checked here).
+ * x, y [rows, E]; codes uint16 [rows]; packed uint8 [rows, E*nbits/8]; one thread per 8 elements; no workspace, no
+ * atomics, bitwise reproducible.
+ * Limits (refused before any launch): dtype f32 or bf16; nbits 1, 2 or 4; E a multiple of 32 in [32, 256];
+ * 1 <= K <= 65535; rows >= 1; non-null pointers; x / y and centroids 16-byte aligned, packed 4-byte aligned. */
+int polus_residual_compress(int dtype, const void* x, const uint16_t* codes, const void* centroids, int K,
+                            const float* cutoffs, int nbits, uint8_t* packed, int rows, int E, void* stream);
+int polus_residual_decompress(int dtype, const uint16_t* codes, const uint8_t* packed, const void* centroids, int K,
+                              const float* weights, int nbits, void* y, int rows, int E, void* stream);
+/* polus_maxsim_rerank over a residual-compressed corpus: codes uint16 [N,Ld] and packed uint8 [N,Ld,E*nbits/8] with the
+ * codec's centroids [K,E] (in `dtype`, like Q) and weights stand in for D; every other argument and every word of
+ * polus_maxsim_rerank's contract holds (masks, strides, -inf for absent candidates with nothing dereferenced, columns
+ * past C not written, tiles behind a document's last valid token skipped, the resident-query and the rounds route, the
+ * same documents per wave).  A lane reads its row's code (the document's codes are loaded a document ahead, like its
+ * mask), its nbits bytes of residual bits per 32-wide k-step and the matching 8 elements of the centroid row, and forms
+ * T(c + weights[bucket]) in registers with the decoder's own arithmetic; the fragments go to polus_maxsim_rerank's
+ * MFMAs in the same k order and its reduction follows.  So
+ *   polus_maxsim_rerank_res(Q, codes, packed, ...) is bit for bit polus_maxsim_rerank(Q, D) with
+ *   D = polus_residual_decompress(codes, packed, ...),
+ * and the quantiser holds all of the error.  A token with code >= K reads centroid 0 as a stand-in and counts as a row of
+ * zeros, as in D.  The weights stay in registers; no LDS, no barrier, no atomics, no workspace.  The centroid rows
+ * (2E bytes per decoded token in bf16) come through L2 / Infinity Cache.
+ * Limits (refused before any launch): those of polus_maxsim_rerank and of the codec above; Q and centroids 16-byte
+ * aligned, packed 4-byte aligned; codes, packed, centroids, weights non-null. */
+int polus_maxsim_rerank_res(int dtype, const void* Q, const uint16_t* codes, const uint8_t* packed,
+                            const void* centroids, int K, const float* weights, int nbits, const int32_t* qmask,
+                            const int32_t* dmask, const int32_t* cand, long ldc, float* score, long lds,
+                            int B, int C, int N, int Lq, int Ld, int E, void* stream);
 /* Row L2 normalisation, torch.nn.functional.normalize(x, dim=-1, eps) (ColBERT's cosine): x, y [rows,E] in
  * `dtype` (E <= 256), rnorm f32 [rows].  Forward (f32 arithmetic): y = x / max(|x|, eps), rnorm = 1 / max(|x|, eps).
  * Backward: dx = (dy - y <y, dy>) * rnorm where |x| > eps, dy / eps otherwise.  One wave per row. */

@@ -76,6 +76,10 @@ SIGNATURES = {
     "polus_fp8_dequantize_rows": (_i, [_i, _vp, _vp, _vp, _i, _i, _vp]),
     "polus_maxsim_scores_fp8": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _vp]),
     "polus_maxsim_rerank_fp8": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _l, _i, _i, _i, _i, _i, _i, _vp]),
+    "polus_residual_compress": (_i, [_i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp]),
+    "polus_residual_decompress": (_i, [_i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp]),
+    "polus_maxsim_rerank_res": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _l, _vp, _l,
+                                     _i, _i, _i, _i, _i, _i, _vp]),
     "polus_maxsim_bwd": (_i, [_i, _vp, _vp, _vp, _l, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "polus_l2norm_fwd": (_i, [_i, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "polus_l2norm_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),

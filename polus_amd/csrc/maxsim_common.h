@@ -1,7 +1,8 @@
 // Device helpers shared by the MaxSim kernels: maxsim.hip (training forward, corpus scores), rerank.hip (candidate
-// lists) and maxsim_fp8.hip (the same two over an FP8 token index).  What is here is what must be the same in all of
-// them for their scores to agree bit for bit: how many query tiles a wave holds, how a query tile becomes B fragments,
-// and how a document's mask becomes per-tile bit words.
+// lists), maxsim_fp8.hip (the same two over an FP8 token index) and residual.hip (candidate lists over a
+// residual-compressed index).  What is here is what must be the same in all of them for their scores to agree bit for
+// bit: how many query tiles a wave holds, how a query tile becomes B fragments, how a document's mask becomes per-tile
+// bit words, and how a tile's fragments meet the query's (rr_tile_max).
 #pragma once
 #include "common.h"
 
@@ -98,5 +99,23 @@ __device__ __forceinline__ void rr_query_load(Frag<T> (&qf)[UT][KS], bool (&qok)
         for (int ks = 0; ks < KS; ++ks) frag_load_row(qf[u][ks], p + ks * 32 * sizeof(T));
         const bool on = !qm || qm[min(tok, Lq - 1)] != 0;
         qok[u] = tok < Lq && on;
+    }
+}
+
+// one document tile against the wave's nu query tiles: m[u] = max(m[u], products of the valid rows).  bits: the
+// tile's 16 mask bits shifted to this lane's rows 4 g .. 4 g + 3
+template <typename T, int KS, int UT>
+__device__ __forceinline__ void rr_tile_max(float (&m)[UT], const Frag<T> (&df)[KS], const Frag<T> (&qf)[UT][KS],
+                                            unsigned bits, int nu) {
+#pragma unroll
+    for (int u = 0; u < UT; ++u) {
+        if (u < nu) {                                         // uniform
+            f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) mma16(acc, df[ks], qf[u][ks]);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (((bits >> r) & 1u) && acc[r] > m[u]) m[u] = acc[r];
+        }
     }
 }

@@ -30,24 +30,6 @@ __device__ __forceinline__ void rr_tile_load(Frag<T> (&f)[KS], const unsigned ch
     for (int ks = 0; ks < KS; ++ks) frag_load_row(f[ks], p + ks * 32 * sizeof(T));
 }
 
-// one document tile against the wave's nu query tiles: m[u] = max(m[u], products of the valid rows).  bits: the
-// tile's 16 mask bits shifted to this lane's rows 4 g .. 4 g + 3
-template <typename T, int KS, int UT>
-__device__ __forceinline__ void rr_tile_max(float (&m)[UT], const Frag<T> (&df)[KS], const Frag<T> (&qf)[UT][KS],
-                                            unsigned bits, int nu) {
-#pragma unroll
-    for (int u = 0; u < UT; ++u) {
-        if (u < nu) {                                         // uniform
-            f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) mma16(acc, df[ks], qf[u][ks]);
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (((bits >> r) & 1u) && acc[r] > m[u]) m[u] = acc[r];
-        }
-    }
-}
-
 template <typename T, int KS, bool RES>
 __global__ __launch_bounds__(256) void maxsim_rerank_kernel(const T* __restrict__ Q, const T* __restrict__ D,
                                                             const int32_t* __restrict__ qmask,

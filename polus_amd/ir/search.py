@@ -32,9 +32,23 @@ What is approximate: WHICH documents get scored; a document the look-up score ra
 seen, however good its exact score.  How often that happens (recall against `search`) depends on K, `candidates`
 and the data; it has not been measured on a real collection.  With candidates >= len(index) the result is `search`'s.
 
+With centroids a token index can drop the full vectors altogether (ColBERTv2's residual compression): a token is stored
+as its centroid's 16-bit id plus nbits = 1, 2 or 4 bits per dimension naming a bucket of its residual, 2 + E * nbits / 8
+bytes beside the int32 mask: 38 at E = 128 and nbits = 2, against 260 in bf16 and 136 in FP8.
+
+    codec = index.fit_codec(2)                          # on a plain or FP8 "training" index that has centroids
+    small = CorpusIndex(model, compute_scores, storage="residual", codec=codec)
+    for docs in corpus_batches: small.add(docs)         # project, normalise, nearest centroid, compress
+
+`rerank`, `search_pruned` and TwoStageSearch score the compressed tokens directly (ops.maxsim_rerank_res decodes
+centroid + bucket weight in registers), bit for bit what a plain index holding the decoded vectors returns; `search`
+decodes a chunk at a time into scratch and runs ops.maxsim_scores (a pruned search never scans, so there is no
+exhaustive kernel over residual bits).  All of the error is the quantiser's.  Recall and score error of 1-, 2- and 4-bit
+residuals have not been measured on any real collection here.
+
 As in ir/training.py, arithmetic is hand-written HIP (ops.gemm / ops.maxsim_scores / ops.maxsim_rerank,
-ops.l2norm_fwd, ops.topk_merge, ops.centroid_scores / centroid_codes / centroid_update); torch allocates, views and
-copies.  Data parallelism: every rank holds the whole
+ops.l2norm_fwd, ops.topk_merge, ops.centroid_scores / centroid_codes / centroid_update, ops.residual_compress /
+residual_decompress / maxsim_rerank_res); torch allocates, views and copies.  Data parallelism: every rank holds the whole
 index and searches its own shard of the queries; ValidationDataCallback gathers the predictions."""
 import numpy as np
 import torch
@@ -49,6 +63,32 @@ MAX_CENTROIDS = 65535         # codes are 16 bits and 0xFFFF is "no token"
 ASSIGN_ROWS = 16384           # tokens per nearest-centroid GEMM, at most (see CorpusIndex._assign_rows)
 
 
+class ResidualCodec:
+    """What turns a token vector into its centroid id plus `nbits` bits per dimension and back (ColBERTv2; the rules
+    are include/polus_hip.h polus_residual_compress): `centroids` [K, E] (a tensor, 1 <= K <= 65535), `nbits` 1, 2 or
+    4, `cutoffs` f32 [2^nbits - 1], non-decreasing: a residual element's bucket is the number of cutoffs below it, and
+    `weights` f32 [2^nbits], what a bucket decodes to.  CorpusIndex.fit_codec makes one from a sample of a corpus."""
+
+    def __init__(self, centroids, cutoffs, weights, nbits):
+        if nbits not in (1, 2, 4):
+            raise ValueError(f"nbits must be 1, 2 or 4 (got {nbits!r})")
+        c = centroids if isinstance(centroids, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(centroids))
+        if c.dim() != 2 or not 1 <= c.shape[0] <= MAX_CENTROIDS or c.shape[1] % 32 or not 32 <= c.shape[1] <= 256:
+            raise ValueError(f"centroids must be [K, E] with 1 <= K <= {MAX_CENTROIDS} and E a multiple of 32 in "
+                             f"[32, 256] (got {tuple(c.shape)})")
+        cut = torch.as_tensor(np.ascontiguousarray(np.asarray(cutoffs.cpu() if isinstance(cutoffs, torch.Tensor) else cutoffs,
+                                                              dtype=np.float32)))
+        w = torch.as_tensor(np.ascontiguousarray(np.asarray(weights.cpu() if isinstance(weights, torch.Tensor) else weights,
+                                                            dtype=np.float32)))
+        if tuple(cut.shape) != ((1 << nbits) - 1,):
+            raise ValueError(f"cutoffs must be [{(1 << nbits) - 1}] for nbits = {nbits} (got {tuple(cut.shape)})")
+        if tuple(w.shape) != (1 << nbits,):
+            raise ValueError(f"weights must be [{1 << nbits}] for nbits = {nbits} (got {tuple(w.shape)})")
+        if not bool((cut[1:] >= cut[:-1]).all()) or bool(torch.isnan(cut).any()):
+            raise ValueError("cutoffs must be non-decreasing (and not NaN)")
+        self.centroids, self.cutoffs, self.weights, self.nbits = c, cut, w, int(nbits)
+
+
 class CorpusIndex:
     """Projected document representations in one contiguous device buffer, [N, E] ([CLS], DualEncoder) or [N, Ld, E]
     with an int32 mask [N, Ld] (tokens, LateInteractionDualEncoder), in the model's compute dtype.
@@ -57,12 +97,23 @@ class CorpusIndex:
     `post_process_logits` is the trainer's hook for [CLS] vectors, applied to queries and documents as the trainer
     applies it; token representations refuse it, as the trainer does.  `scratch_bytes` bounds the [Q, n] f32 score
     buffer of one chunk.  `storage` is None (the model's compute dtype) or "fp8" (token representations only: e4m3fn
-    codes uint8 [N, Ld, E] and power-of-two scales f32 [N, Ld], include/polus_hip.h polus_fp8_quantize_rows)."""
+    codes uint8 [N, Ld, E] and power-of-two scales f32 [N, Ld], include/polus_hip.h polus_fp8_quantize_rows) or
+    "residual" (token representations under a scorer that normalises: the centroid codes int16 [N, Ld] of `codec`, a
+    ResidualCodec, and uint8 [N, Ld, E * nbits / 8] residual bits, polus_residual_compress; on it `scratch_bytes` also
+    bounds the decoded vectors of one chunk of `search`)."""
 
-    def __init__(self, model, compute_scores, post_process_logits=None, scratch_bytes=256 << 20, storage=None):
-        if storage not in (None, "fp8"):
-            raise ValueError(f"storage must be None or 'fp8' (got {storage!r})")
-        self.storage = storage
+    def __init__(self, model, compute_scores, post_process_logits=None, scratch_bytes=256 << 20, storage=None, codec=None):
+        if storage not in (None, "fp8", "residual"):
+            raise ValueError(f"storage must be None or 'fp8' or 'residual' (got {storage!r})")
+        if (storage == "residual") != (codec is not None):
+            raise ValueError("storage='residual' needs a codec (ResidualCodec, see CorpusIndex.fit_codec), and only "
+                             "that storage takes one")
+        if codec is not None and not isinstance(codec, ResidualCodec):
+            raise ValueError(f"codec must be a ResidualCodec (got {type(codec).__name__})")
+        if storage == "residual" and not bool(getattr(compute_scores, "normalize", False)):
+            raise ValueError("storage='residual' needs a scorer that normalises (MaxSimScores(normalize=True)): the "
+                             "nearest centroid by dot product means something on unit vectors only")
+        self.storage, self.codec = storage, codec
         self.model, self.compute_scores = model, compute_scores
         self.post_process_logits = post_process_logits
         self.scratch_bytes = int(scratch_bytes)
@@ -71,9 +122,11 @@ class CorpusIndex:
         self.clear()
 
     def clear(self):
-        """Empty the index (the storage is released; the next `add` fixes the document length again)."""
+        """Empty the index (the storage is released; the next `add` fixes the document length again).  A residual
+        index keeps its codec."""
         self._reps = self._mask = self._scale = None
         self._codes = self._centroids = None          # centroid codes int16 [cap, Ld] and centroids [K, E]
+        self._cutoffs = self._weights = None          # a residual index: the codec's tables on the device
         self._n = 0
         self.tokens = None            # True: token representations; fixed by the first add
 
@@ -91,7 +144,22 @@ class CorpusIndex:
             if self._n:
                 ops.fp8_dequantize(self._reps[:self._n], self._scale[:self._n], y)
             return y
+        if self.storage == "residual":
+            return self._decoded(0, self._n)
         return self._reps[:self._n]
+
+    def _decoded(self, a, b, out=None):
+        """Documents a .. b of a residual index, decoded into `out` (or a new tensor) [b - a, Ld, E]."""
+        E = self._centroids.shape[1]
+        y = torch.empty((b - a, self._ld, E), dtype=self._dtype, device=self._reps.device) if out is None else out
+        if b > a:
+            ops.residual_decompress(self._codes[a:b], self._reps[a:b], self._centroids, self._weights, self.codec.nbits, y)
+        return y
+
+    @property
+    def residuals(self):
+        """uint8 [N, Ld, E * nbits / 8]: a view of the stored residual bits (a residual index; None otherwise)."""
+        return None if self.storage != "residual" or self._reps is None else self._reps[:self._n]
 
     @property
     def codes(self):
@@ -105,7 +173,10 @@ class CorpusIndex:
 
     @property
     def centroids(self):
-        """[K, E] in the index's dtype: the centroids of set_centroids / fit_centroids (None before)."""
+        """[K, E] in the index's dtype: the centroids of set_centroids / fit_centroids (None before).  A residual
+        index: its codec's (as the codec holds them until the first `add` moves them to the device)."""
+        if self._centroids is None and self.storage == "residual":
+            return self.codec.centroids
         return self._centroids
 
     @property
@@ -137,8 +208,9 @@ class CorpusIndex:
                              "to the scorer (MaxSimScores(normalize=True))")
         if self.tokens is not None and tokens != self.tokens:
             raise ValueError("the index holds " + ("token" if self.tokens else "[CLS]") + " representations")
-        if self.storage == "fp8" and not tokens:
-            raise ValueError("storage='fp8' holds token representations only; a [CLS] index stays in the model's dtype")
+        if self.storage is not None and not tokens:
+            raise ValueError(f"storage={self.storage!r} holds token representations only; a [CLS] index stays in the "
+                             "model's dtype")
         return tokens
 
     def _grow(self, need, like, tail):
@@ -148,8 +220,10 @@ class CorpusIndex:
             return
         cap = max(need, 2 * cap)
         # zeros: the padding of documents shorter than the index's length is never written
-        fp8 = self.storage == "fp8"
-        reps = torch.zeros((cap,) + tail, dtype=torch.uint8 if fp8 else like.dtype, device=like.device)
+        fp8, res = self.storage == "fp8", self.storage == "residual"
+        if res:
+            tail = (tail[0], tail[1] * self.codec.nbits // 8)
+        reps = torch.zeros((cap,) + tail, dtype=torch.uint8 if fp8 or res else like.dtype, device=like.device)
         mask = torch.zeros((cap, tail[0]), dtype=torch.int32, device=like.device) if self.tokens else None
         scale = torch.zeros((cap, tail[0]), dtype=torch.float32, device=like.device) if fp8 else None
         if self._n:
@@ -158,16 +232,18 @@ class CorpusIndex:
                 mask[:self._n].copy_(self._mask[:self._n])
             if scale is not None:
                 scale[:self._n].copy_(self._scale[:self._n])
-        if self._codes is not None:
+        if self._codes is not None or res:
             codes = torch.full((cap, tail[0]), -1, dtype=torch.int16, device=like.device)         # 0xFFFF: no token
-            codes[:self._n].copy_(self._codes[:self._n])
+            if self._codes is not None:
+                codes[:self._n].copy_(self._codes[:self._n])
             self._codes = codes
         self._reps, self._mask, self._scale = reps, mask, scale
 
     def add(self, documents):
         """Encode, project (and normalise) a batch of documents and append it; returns its ids, the consecutive int32
         positions in the index.  Token documents are padded with masked tokens to the length of the first batch;
-        a longer batch raises ValueError.  An FP8 index quantises the projected (and normalised) vectors here."""
+        a longer batch raises ValueError.  An FP8 index quantises the projected (and normalised) vectors here; a
+        residual index gives them their nearest centroid of the codec and compresses them."""
         model = self.model
         rep = model.document_projection(model.encode_document(documents, training=False), training=False)
         tokens = self._check_kind(rep)
@@ -181,6 +257,9 @@ class CorpusIndex:
             if L > self._ld:
                 raise ValueError(f"a document batch of {L} tokens does not fit the index's document length {self._ld} "
                                  "(fixed by the first add)")
+            if self.storage == "residual":
+                self._add_residual(v, m)
+                return self._ids(n, v.device)
             self._grow(self._n + n, v, (self._ld, E))
             if self.storage == "fp8":
                 self._dtype = v.dtype
@@ -200,17 +279,51 @@ class CorpusIndex:
             self.tokens = False
             self._grow(self._n + n, v, (E,))
             self._reps[self._n:self._n + n].copy_(v)
-        ids = torch.arange(self._n, self._n + n, dtype=torch.int32, device=v.device)
+        return self._ids(n, v.device)
+
+    def _ids(self, n, dev):
+        ids = torch.arange(self._n, self._n + n, dtype=torch.int32, device=dev)
         self._n += n
         return ids
 
-    def chunks(self, Q):
+    def _add_residual(self, v, m):
+        """`add` on a residual index: v [n, L, E] projected and normalised, m its mask.  The batch is padded to the
+        index's length, its tokens get their codes by _assign_rows (the rule a plain index with these centroids
+        follows in `add`) and ops.residual_compress writes the bits into the storage."""
+        n, L, E = v.shape
+        codec = self.codec
+        if codec.centroids.shape[1] != E:
+            raise ValueError(f"the codec's centroids have {codec.centroids.shape[1]} features, the model's tokens {E}")
+        if self._centroids is None:
+            self._dtype = v.dtype
+            self._centroids = codec.centroids.to(device=v.device, dtype=v.dtype).contiguous().clone()
+            self._cutoffs, self._weights = codec.cutoffs.to(v.device), codec.weights.to(v.device)
+        self._grow(self._n + n, v, (self._ld, E))
+        a, b = self._n, self._n + n
+        self._mask[a:b, :L].copy_(m)
+        if L < self._ld:
+            x = torch.zeros((n, self._ld, E), dtype=v.dtype, device=v.device)
+            x[:, :L].copy_(v)
+        else:
+            x = v.contiguous()
+        flat = x.view(-1, E)
+        codes = self._codes[a:b].view(-1)
+        self._assign_rows(lambda s, e, dst: dst.copy_(flat[s:e]), n * self._ld, self._mask[a:b].view(-1), codes, self._centroids)
+        ops.residual_compress(x, codes, self._centroids, self._cutoffs, codec.nbits, self._reps[a:b])
+
+    def chunks(self, Q, decode=False):
         """[(start, stop), ...]: the document ranges a search with Q queries scores, one launch each: at most 65535
-        documents, and at most as many as keep the [Q, n] f32 scores within scratch_bytes."""
+        documents, and at most as many as keep the [Q, n] f32 scores within scratch_bytes.  decode=True (the `search` of
+        a residual index): the chunk's decoded vectors [n, Ld, E] stay within scratch_bytes as well."""
         per = min(MAX_CHUNK, self.scratch_bytes // (4 * int(Q)))
         if per < 1:
             raise ValueError(f"scratch_bytes = {self.scratch_bytes} does not hold the scores of one document for "
                              f"{Q} queries ({4 * int(Q)} bytes)")
+        if decode and self._n:
+            doc = self._ld * self._centroids.shape[1] * self._centroids.element_size()
+            if self.scratch_bytes < doc:
+                raise ValueError(f"scratch_bytes = {self.scratch_bytes} does not hold one decoded document ({doc} bytes)")
+            per = min(per, self.scratch_bytes // doc)
         return [(s, min(s + per, self._n)) for s in range(0, self._n, per)]
 
     def encode_queries(self, queries):
@@ -230,13 +343,18 @@ class CorpusIndex:
         q = self.encode_queries(queries)
         qv = q.values if self.tokens else q
         Q = qv.shape[0]
-        spans = self.chunks(Q)
+        res = self.storage == "residual"
+        spans = self.chunks(Q, decode=res)
         scratch = torch.empty((Q, max(b - a for a, b in spans)), dtype=torch.float32, device=qv.device)
         top_val = torch.empty((Q, int(k)), dtype=torch.float32, device=qv.device)
         top_id = torch.empty((Q, int(k)), dtype=torch.int32, device=qv.device)
+        if res:       # no exhaustive kernel over residual bits (a pruned search never scans): decode, then the plain one
+            dec = torch.empty((max(b - a for a, b in spans), self._ld, qv.shape[2]), dtype=self._dtype, device=qv.device)
         for a, b in spans:
             s = scratch[:, :b - a]
-            if self.storage == "fp8":
+            if res:
+                ops.maxsim_scores(qv, self._decoded(a, b, dec[:b - a]), q.mask, self._mask[a:b], s)
+            elif self.storage == "fp8":
                 ops.maxsim_scores_fp8(qv, self._reps[a:b], self._scale[a:b], q.mask, self._mask[a:b], s)
             elif self.tokens:
                 ops.maxsim_scores(qv, self._reps[a:b], q.mask, self._mask[a:b], s)
@@ -299,6 +417,9 @@ class CorpusIndex:
             s, c = scratch[:, :b - a], cand[:, a:b]
             if self.storage == "fp8":
                 ops.maxsim_rerank_fp8(qv, reps, self._scale[:self._n], q.mask, mask, c, s)
+            elif self.storage == "residual":
+                ops.maxsim_rerank_res(qv, self._codes[:self._n], reps, self._centroids, self._weights, self.codec.nbits,
+                                      q.mask, mask, c, s)
             else:
                 ops.maxsim_rerank(qv, reps, q.mask, mask, c, s)
             ops.topk_merge(s, top_val, top_id, init=(a == 0), ids=c)
@@ -306,6 +427,9 @@ class CorpusIndex:
 
     # ------------------------------------------------------------ centroid-pruned search
     def _check_centroid_support(self):
+        if self.storage == "residual":
+            raise ValueError("a residual index takes its centroids from its codec: the stored residuals belong to "
+                             "them, so they cannot be set or fitted again")
         if self._n == 0:
             raise ValueError("the index is empty: add documents before setting or fitting centroids")
         if not self.tokens:
@@ -316,7 +440,7 @@ class CorpusIndex:
                              "centroid by dot product means something on unit vectors only")
 
     def _token_dtype(self):
-        return self._dtype if self.storage == "fp8" else self._reps.dtype
+        return self._dtype if self.storage is not None else self._reps.dtype
 
     def _assign_rows(self, load, T, mask, codes, centroids):
         """codes[t] (int16 [T]) = the nearest row of `centroids` to token t, 0xFFFF where mask[t] == 0 (mask int32 [T]
@@ -406,6 +530,43 @@ class CorpusIndex:
             ops.centroid_update(x, codes, cent, nxt, counts, self.eps)
             cent, nxt = nxt, cent
         self.set_centroids(cent)
+
+    def fit_codec(self, nbits, sample=1 << 16, seed=0):
+        """A ResidualCodec for this index's centroids from a sample of its stored tokens (a plain or FP8 token index
+        that has centroids: the "training" index over a sample of the corpus, as in ColBERTv2).
+
+        The sampled slots are fit_centroids' (seed, N, Ld and the masks only; masked slots dropped).  Every sampled
+        token's residual against the centroid of its stored code is r = f32(x) - f32(centroid), one f32 subtraction
+        (an FP8 index: x is the dequantised vector).  Over all elements of all these residuals, cutoffs[j] is the
+        (j + 1) / 2^nbits quantile and weights[b] the (b + 1/2) / 2^nbits quantile: numpy.quantile in float64 with
+        method="linear", cast to f32.  Host work at build time, deterministic: data-parallel ranks holding the same
+        corpus agree without communication."""
+        if nbits not in (1, 2, 4):
+            raise ValueError(f"nbits must be 1, 2 or 4 (got {nbits!r})")
+        self._check_centroid_support()
+        if self._centroids is None:
+            raise ValueError("fit_codec needs centroids: call fit_centroids or set_centroids first")
+        S, E = self._n * self._ld, self._reps.shape[2]
+        r = np.random.Generator(np.random.PCG64(int(seed)))
+        slots = r.permutation(S) if S <= int(sample) else r.choice(S, size=int(sample), replace=False)
+        slots = slots[self._mask[:self._n].reshape(-1).cpu().numpy()[slots] != 0]
+        if len(slots) == 0:
+            raise ValueError("the sample holds no valid token")
+        at = torch.as_tensor(slots.astype(np.int64)).to(self._reps.device)
+        flat = self._reps[:self._n].view(-1, E)
+        if self.storage == "fp8":
+            x = torch.empty((len(slots), E), dtype=self._dtype, device=self._reps.device)
+            ops.fp8_dequantize(flat[at].contiguous(), self._scale[:self._n].view(-1)[at].contiguous(), x)
+        else:
+            x = flat[at]
+        codes = self._codes[:self._n].view(-1)[at].cpu().numpy().view(np.uint16).astype(np.int64)
+        cent = self._centroids.float().cpu().numpy()
+        res = x.float().cpu().numpy() - cent[codes]
+        n = 1 << nbits
+        flat64 = res.astype(np.float64).ravel()
+        cutoffs = np.quantile(flat64, np.arange(1, n) / n, method="linear").astype(np.float32)
+        weights = np.quantile(flat64, (np.arange(n) + 0.5) / n, method="linear").astype(np.float32)
+        return ResidualCodec(self._centroids.clone(), cutoffs, weights, nbits)
 
     def search_pruned(self, queries, k, candidates):
         """`search` over the `candidates` documents per query that score best under the centroid approximation:

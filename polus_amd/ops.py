@@ -572,6 +572,66 @@ def maxsim_rerank_fp8(q, codes, scale, qmask, dmask, cand, score):
           "polus_maxsim_rerank_fp8")
 
 
+def _residual_codec(centroids, table, nbits, E, name):
+    """Checks of a residual codec's device tensors; `table` is the cutoffs (2^nbits - 1) or the weights (2^nbits)."""
+    assert nbits in (1, 2, 4), f"nbits must be 1, 2 or 4 (got {nbits})"
+    assert centroids.dim() == 2 and centroids.shape[1] == E and centroids.is_contiguous() and 1 <= centroids.shape[0] <= 65535
+    n = (1 << nbits) - (1 if name == "cutoffs" else 0)
+    assert table.dtype == torch.float32 and table.is_contiguous() and table.numel() == n, f"{name}: f32 [{n}] expected"
+    return centroids.shape[0]
+
+
+def residual_compress(x, codes, centroids, cutoffs, nbits, packed):
+    """x [..., E] (f32 or bf16) and its centroid codes int16 [...] (the bits of the unsigned code; >= K: no token) ->
+    packed uint8 [..., E * nbits / 8], the bucket of every residual element x - centroids[code] among the cutoffs
+    f32 [2^nbits - 1] (include/polus_hip.h polus_residual_compress); centroids [K, E] in x's dtype."""
+    _req_cuda(x, codes, centroids, cutoffs, packed)
+    E = x.shape[-1]
+    rows = x.numel() // E
+    K = _residual_codec(centroids, cutoffs, nbits, E, "cutoffs")
+    assert x.is_contiguous() and centroids.dtype == x.dtype
+    assert codes.dtype == torch.int16 and codes.is_contiguous() and codes.numel() == rows
+    assert packed.dtype == torch.uint8 and packed.is_contiguous() and packed.numel() == rows * E * nbits // 8
+    check(_lib.load().polus_residual_compress(dtype_code(x.dtype), ptr(x), ptr(codes), ptr(centroids), K, ptr(cutoffs),
+                                              int(nbits), ptr(packed), rows, E, _st()), "polus_residual_compress")
+
+
+def residual_decompress(codes, packed, centroids, weights, nbits, y):
+    """y [..., E] (f32 or bf16) = centroids[code] + weights[bucket], one f32 addition rounded once to y's dtype; rows
+    whose code is >= K are zeros (codes int16 [...], packed uint8 [..., E * nbits / 8], weights f32 [2^nbits];
+    include/polus_hip.h polus_residual_decompress)."""
+    _req_cuda(codes, packed, centroids, weights, y)
+    E = y.shape[-1]
+    rows = y.numel() // E
+    K = _residual_codec(centroids, weights, nbits, E, "weights")
+    assert y.is_contiguous() and centroids.dtype == y.dtype
+    assert codes.dtype == torch.int16 and codes.is_contiguous() and codes.numel() == rows
+    assert packed.dtype == torch.uint8 and packed.is_contiguous() and packed.numel() == rows * E * nbits // 8
+    check(_lib.load().polus_residual_decompress(dtype_code(y.dtype), ptr(codes), ptr(packed), ptr(centroids), K, ptr(weights),
+                                                int(nbits), ptr(y), rows, E, _st()), "polus_residual_decompress")
+
+
+def maxsim_rerank_res(q, codes, packed, centroids, weights, nbits, qmask, dmask, cand, score):
+    """maxsim_rerank over a residual-compressed corpus (codes int16 [N, Ld], packed uint8 [N, Ld, E * nbits / 8],
+    centroids [K, E] in q's dtype, weights f32 [2^nbits]): score[b, c] is bit for bit what maxsim_rerank gives over the
+    corpus residual_decompress writes; -inf where cand[b, c] is outside [0, N) (include/polus_hip.h
+    polus_maxsim_rerank_res)."""
+    _req_cuda(q, codes, packed, centroids, weights, qmask, dmask, cand, score)
+    B, Lq, E = q.shape
+    K = _residual_codec(centroids, weights, nbits, E, "weights")
+    assert q.is_contiguous() and centroids.dtype == q.dtype
+    assert codes.dim() == 2 and codes.dtype == torch.int16 and codes.is_contiguous()
+    N, Ld = codes.shape
+    assert packed.dtype == torch.uint8 and tuple(packed.shape) == (N, Ld, E * nbits // 8) and packed.is_contiguous()
+    assert cand.dtype == torch.int32 and cand.dim() == 2 and cand.shape[0] == B and (cand.stride(1) == 1 or cand.shape[1] == 1)
+    C = cand.shape[1]
+    assert score.dtype == torch.float32 and tuple(score.shape) == (B, C) and (score.stride(1) == 1 or C == 1)
+    check(_lib.load().polus_maxsim_rerank_res(dtype_code(q.dtype), ptr(q), ptr(codes), ptr(packed), ptr(centroids), K,
+                                              ptr(weights), int(nbits), ptr(_maxsim_mask(qmask, B, Lq, "qmask")),
+                                              ptr(_maxsim_mask(dmask, N, Ld, "dmask")), ptr(cand), cand.stride(0), ptr(score),
+                                              score.stride(0), B, C, N, Lq, Ld, E, _st()), "polus_maxsim_rerank_res")
+
+
 def topk_merge(scores, top_val, top_id, id0=0, init=False, ids=None):
     """Merge scores (f32 [rows, n], any row stride; column c is document id0 + c) into the running top-k state
     top_val f32 / top_id int32 [rows, k]: score descending, ties to the lower id, NaN and -inf dropped, (-inf, -1)
