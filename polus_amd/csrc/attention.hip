@@ -117,7 +117,44 @@ struct AttnArgs {
     float drop_inv;
     const PolusDyn* dyn;               // per-step scalars in device memory (graph replay) or null
     int debug;                         // diagnostics (POLUS_ATTN_DEBUG): parts of the key-resident backward switched off
+    int kskip;                         // POLUS_ATTN_KSKIP: the LDS-DMA forward and the query-resident backwards stop at the last unmasked key block
 };
+
+// ---- Key extent of a sample: kend = 1 + (last key with mask != 0); S without a mask, and S when no key is unmasked (the
+// -10000 scores are then the whole softmax).  A key block that starts at or past kend holds only padded keys: their scores
+// sit ~14 427 base-2 units under the row maximum, v_exp_f32 returns +0 for them, and everything they would add to ctx,
+// lse, dQ, dK and dV is an exact +0 -- the sweeps stop there and results keep every bit (|scaled score| << 10000 assumed,
+// as the additive mask itself assumes).  Left padding and holes end at the last kept key like any other mask.
+// Each wave that converts mask words takes a ballot of "my key is unmasked" (keys base .. base + 63, one per lane) and
+// leaves 1 + its highest such key (0: none) in an LDS word of its own, ahead of a barrier the kernel has anyway ...
+__device__ __forceinline__ int kext_of_ballot(unsigned long long live, int base) {
+    return live ? base + 64 - __builtin_clzll(live) : 0;
+}
+// ... and behind that barrier every wave folds the NWORDS words (a multiple of 4): a scalar, so that loop bounds and the
+// barriers inside the loops stay workgroup-uniform.  (Inline-asm reads: ahead of a read it can see, the compiler lets every
+// LDS-DMA in flight land -- in the forward kernel that would be blocks 0-2, the whole prefetch.)
+template <int NWORDS>
+__device__ __forceinline__ int kext_fold(const int* words, bool masked, int S) {
+    typedef int kx4_t __attribute__((ext_vector_type(4)));
+    const unsigned addr = (unsigned)(unsigned long)(const __attribute__((address_space(3))) int*)words;
+    int k = 0;
+#pragma unroll
+    for (int w = 0; w < NWORDS; w += 4) {
+        kx4_t v;
+        asm volatile("ds_read_b128 %0, %1 offset:%2\n\ts_waitcnt lgkmcnt(0)" : "=&v"(v) : "v"(addr), "n"(w * 4));
+        k = max(k, max(max(v[0], v[1]), max(v[2], v[3])));
+    }
+    return __builtin_amdgcn_readfirstlane(masked && k > 0 ? k : S);
+}
+// +0 into the dK and dV rows row0 .. S - 1 of head h (the key blocks a one-pass backward skipped): whole 128-byte rows as
+// 16-byte stores, by all NT threads of the workgroup
+template <int NT>
+__device__ __forceinline__ void zero_dkv_rows(bf16_t* __restrict__ dqkv, long ld, int row0, int S, int H, int h, int tid) {
+    for (int c = tid; c < (S - row0) * 16; c += NT) {
+        const int r = row0 + (c >> 4), which = (c >> 3) & 1, ch = c & 7;
+        *reinterpret_cast<uint4*>(dqkv + (long)r * ld + (1 + which) * H + h * D + ch * 8) = make_uint4(0, 0, 0, 0);
+    }
+}
 
 __device__ __forceinline__ float key_bias(const int32_t* mask, int b, int S, int key) {
     if (key >= S) return -INFINITY;
@@ -242,6 +279,8 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_kernel(AttnArgs p) {
 // refilled once the fragments are in registers); the output goes back through LDS so that HBM sees whole 128-byte rows.
 // Same arithmetic per score as attn_fwd_kernel (scale, additive -10000 mask, base-2 exponentials, dropout after the
 // row sum); the sums are taken in a different order, so results agree to rounding, not bit for bit.
+// The sweep ends at the block of the sample's last unmasked key (POLUS_ATTN_KSKIP, kext_of_ballot above): blocks 0-2 are
+// on their way before the mask has landed, block 3 and every refill are fetched only if they will be computed.
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void* gptr_t;
 __device__ __forceinline__ void dma16(const void* g, unsigned char* lds) {
@@ -321,15 +360,24 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void attn_fwd_dma_kernel(
         for (int sub = 0; sub < 2; ++sub)
             qf[sub].v = *reinterpret_cast<const bf16x8*>(ring + 3 * FWD_STAGE + row * 128 + (((sub * 4 + g) ^ (row & 7)) * 16));
     }
+    int* kext = reinterpret_cast<int*>(kbc) + (S + NT - 1) / NT * NT;   // [NW] key extent seen by each wave
+    int kw = 0;
     for (int t = tid; t < nblk * BLK; t += NT) {                  // mask -> additive bias, in place (same thread reads and writes a word)
         float bias = 0.0f;
-        if (p.mask) bias = (1.0f - (float)reinterpret_cast<const int*>(kbc)[t]) * MASK_NEG;
+        int mk = 0;
+        if (p.mask) { mk = reinterpret_cast<const int*>(kbc)[t]; bias = (1.0f - (float)mk) * MASK_NEG; }
         kbc[t] = t < S ? bias * LOG2E : -INFINITY;
+        const unsigned long long live = __ballot(t < S && mk != 0);      // a wave's 64 t are consecutive, t - lane its first
+        if (live) kw = kext_of_ballot(live, t - lane);
     }
+    if (lane == 0) kext[wid] = kw;
     wait_lgkm();
     __builtin_amdgcn_s_barrier();                                 // Q fragments in registers everywhere: slot 3 is free
-    if (nblk > 3) issue_block(3);
-    int issued = min(nblk, 4);
+    // blocks from nblk_eff on hold padded keys only (see kext_of_ballot): neither computed nor, from block 3 on, fetched
+    const int kend = kext_fold<NW>(kext, p.mask != nullptr, S);
+    const int nblk_eff = p.kskip ? (kend + BLK - 1) / BLK : nblk;
+    if (nblk_eff > 3) issue_block(3);
+    int issued = min(nblk, 3) + (nblk_eff > 3);                   // what was really issued: the counted waits go by it
 
     const float scale2 = p.scale * LOG2E;
     float m = -1e30f, l = 0.f;                                    // l: this lane's share of the row sum (4 lanes per query)
@@ -342,8 +390,8 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void attn_fwd_dma_kernel(
     const int vrow = 4 * g + (i >> 2), vx = vrow & 7;
     const int v_base = vrow * 128 + (i & 1) * 8, v_c = (i & 3) >> 1;
 
-    for (int j0 = 0; j0 < nblk; j0 += 2) {
-        const bool two = j0 + 1 < nblk;
+    for (int j0 = 0; j0 < nblk_eff; j0 += 2) {
+        const bool two = j0 + 1 < nblk_eff;
         // ---- scores of the pass: S^T tiles [64 keys x 16 queries] per block, each behind its counted wait
         f32x4 s[2][4];
 #pragma unroll
@@ -361,9 +409,6 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void attn_fwd_dma_kernel(
                     mma16(s[jj][kt], a0, qf[0]);                  // D[key 4g+r][query i]
                     mma16(s[jj][kt], a1, qf[1]);
                 }
-            } else {
-#pragma unroll
-                for (int kt = 0; kt < 4; ++kt) s[jj][kt] = (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
             }
         }
         // ---- softmax step over the (up to) 32 scores of this lane; 4 lanes (g) share a query
@@ -387,6 +432,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void attn_fwd_dma_kernel(
         Frag<T> pf[2][2];
 #pragma unroll
         for (int jj = 0; jj < 2; ++jj) {
+            // a missing second block (odd block count) would add 64 exact zeros to the row sum and feeds no MFMA below:
+            // neither its exponentials nor its dropout hashes are evaluated
+            if (jj == 1 && !two) continue;
 #pragma unroll
             for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
@@ -428,18 +476,19 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void attn_fwd_dma_kernel(
             }
         }
         // ---- longer sequences: both slots of this pass are free once every wave is past its reads; refill them
-        if (j0 + 4 < nblk) {
+        if (j0 + 4 < nblk_eff) {
             wait_lgkm();
             __builtin_amdgcn_s_barrier();
             issue_block(j0 + 4);
             ++issued;
-            if (j0 + 5 < nblk) { issue_block(j0 + 5); ++issued; }
+            if (j0 + 5 < nblk_eff) { issue_block(j0 + 5); ++issued; }
         }
     }
     // ---- output: normalise, stage this wave's 16 x 64 tile in LDS (ring slot 0, wave-private 2 KiB, same chunk swizzle),
     // store whole 128-byte rows
     l = col_sum2(l);
     const float inv_l = 1.0f / l;
+    wait_vm<0>();                                                 // a block issued ahead of kend and then skipped may still be landing
     wait_lgkm();
     __builtin_amdgcn_s_barrier();                                 // every wave is done reading K / V (and no DMA is in flight)
     unsigned char* ot = ring + wid * 2048;
@@ -718,6 +767,11 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_fused_kernel(AttnArgs p) {
     tile_load<T, NT>(Oc, dctx, H, 0, S, h * D, tid);
     load_kv(0, 0);
     if (tid < S) kbc[tid] = key_bias(p.mask, b, S, tid) * LOG2E;
+    int* kext = reinterpret_cast<int*>(kbc + S);     // [4] key extent seen by each of the first four waves
+    if (wid < 4) {                                   // (see kext_of_ballot): the waves that read mask words, 0 from the rest
+        const unsigned long long live = __ballot(tid < S && p.mask && p.mask[(long)b * S + tid] != 0);
+        if (lane == 0) kext[wid] = kext_of_ballot(live, wid * 64);
+    }
 
     Frag<T> qf[2], dof[2];
 #pragma unroll
@@ -744,12 +798,15 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_fused_kernel(AttnArgs p) {
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) dq[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     __syncthreads();
+    // key blocks from nkb_eff on hold padded keys only: P' = dS = 0, nothing for dQ, zero dK / dV rows (written behind the loop)
+    const int kend = kext_fold<4>(kext, p.mask != nullptr, S);
+    const int nkb_eff = p.kskip ? (kend + KBLK - 1) / KBLK : NKB;
 
-    for (int kb = 0; kb < NKB; ++kb) {
+    for (int kb = 0; kb < nkb_eff; ++kb) {
         const int cur = kb & 1;
         const unsigned char* Kt = Kc + cur * KBLK * RS;
         const unsigned char* Vt = Vc + cur * KBLK * RS;
-        if (kb + 1 < NKB) load_kv(kb + 1, cur ^ 1);      // the other buffer was last read before the previous barrier
+        if (kb + 1 < nkb_eff) load_kv(kb + 1, cur ^ 1);  // the other buffer was last read before the previous barrier
         // ---- phase 1
         f32x4 s[2], dp[2];
 #pragma unroll
@@ -823,6 +880,7 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_fused_kernel(AttnArgs p) {
         }
         __syncthreads();
     }
+    zero_dkv_rows<NT>(dqkv, ld, nkb_eff * KBLK, S, H, h, tid);
     store_acc_T<T>(dqkv, ld, q, h * D, dq, 1.0f, g, true);
 }
 
@@ -877,7 +935,7 @@ constexpr int Q64_KB = 64;
 template <int NW> struct Q64Cfg {
     static constexpr int S = 16 * NW;
     static constexpr int OFF_O = S * 128, OFF_K = 2 * S * 128, OFF_V = OFF_K + Q64_KB * 128, OFF_P = OFF_V + Q64_KB * 128,
-                         OFF_D = OFF_P + 4 * S * 32, OFF_B = OFF_D + 4 * S * 32, SMEM = OFF_B + S * 4;
+                         OFF_D = OFF_P + 4 * S * 32, OFF_B = OFF_D + 4 * S * 32, OFF_X = OFF_B + S * 4, SMEM = OFF_X + 16;
 };
 
 template <int NW>
@@ -897,6 +955,7 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_bwd_q64_kernel(AttnArgs p) {
     unsigned char* Ps = smem + C::OFF_P;               // [4][S][32]
     unsigned char* Ds = smem + C::OFF_D;
     float* kbc = reinterpret_cast<float*>(smem + C::OFF_B);
+    int* kext = reinterpret_cast<int*>(smem + C::OFF_X);   // [4] key extent seen by each of the first four waves
     const int tid = threadIdx.x, lane = tid & 63, i = lane & 15, g = lane >> 4;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = blockIdx.x, b = blockIdx.y;
@@ -924,6 +983,10 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_bwd_q64_kernel(AttnArgs p) {
     }
     issue_kv(0);
     if (tid < S) kbc[tid] = key_bias(p.mask, b, S, tid) * LOG2E;
+    if (wid < 4) {                                     // key extent (see kext_of_ballot): the waves that read mask words, 0 from the rest
+        const unsigned long long live = __ballot(tid < S && p.mask && p.mask[(long)b * S + tid] != 0);
+        if (lane == 0) kext[wid] = kext_of_ballot(live, wid * 64);
+    }
     const long stat = ((long)b * p.A + h) * S + q;
     const float lse2 = p.lse[stat] * LOG2E;
     const float scale2 = p.scale * LOG2E;
@@ -958,8 +1021,11 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_bwd_q64_kernel(AttnArgs p) {
     const int trow = 4 * g + (i >> 2), tx = trow & 7, thalf = (i & 1) * 8, tc = (i & 3) >> 1;    // transposing reads
     const int st_w = q * 32 + ((g ^ ((q >> 2) & 3)) * 8);                                        // staging write: image kt, row q
     const int st_r = trow * 32 + (((i & 3) ^ g) * 8);                                            // staging read: rows 32 qs + trow (+16)
+    // key blocks from nkb_eff on hold padded keys only: P' = dS = 0, nothing for dQ, zero dK / dV rows (written behind the loop)
+    const int kend = kext_fold<4>(kext, p.mask != nullptr, S);
+    const int nkb_eff = p.kskip ? (kend + Q64_KB - 1) / Q64_KB : NKB;
 
-    for (int kb = 0; kb < NKB; ++kb) {
+    for (int kb = 0; kb < nkb_eff; ++kb) {
         // ---- phase 1: my 16 queries x the 64 keys of the block (the query-side fragments are re-read from the resident images
         // every block: 16 registers that need not stay live across phase 2)
         f32x4 s[4];
@@ -1018,7 +1084,7 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_bwd_q64_kernel(AttnArgs p) {
         wait_lgkm();
         __builtin_amdgcn_s_barrier();
         // ---- the next block's K / V land under phase 2 (which reads neither)
-        if (kb + 1 < NKB) issue_kv(kb + 1);
+        if (kb + 1 < nkb_eff) issue_kv(kb + 1);
         // ---- phase 2: this block's dK^T / dV^T tiles over ALL queries; a wave's tiles share the A operand (Q^T or dO^T)
 #pragma unroll
         for (int c = 0; c < COMBOS; ++c) {
@@ -1054,10 +1120,11 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_bwd_q64_kernel(AttnArgs p) {
             }
         }
         // ---- block kb + 1 has landed (younger: this phase's COMBOS x KTW tile stores), every wave is done with the staging images
-        if (kb + 1 < NKB) wait_vm<COMBOS * KTW>();
+        if (kb + 1 < nkb_eff) wait_vm<COMBOS * KTW>();
         wait_lgkm();
         __builtin_amdgcn_s_barrier();
     }
+    zero_dkv_rows<NT>(dqkv, ld, nkb_eff * Q64_KB, S, H, h, tid);   // behind the loop: its counted waits see only their tile stores
     store_acc_T<T>(dqkv, ld, q, h * D, dq, 1.0f, g, true);
 }
 
@@ -1427,6 +1494,7 @@ int attn_args(const char* who, AttnArgs& a, int B, int S, int n_heads, float dro
     POLUS_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (long)B * n_heads * S * S < (1LL << 32), "%s: bad dropout arguments", who);
     a.B = B; a.S = S; a.A = n_heads; a.H = n_heads * D; a.scale = 0.125f;
     a.drop_thresh = drop_p > 0.f ? polus_drop_thresh(drop_p) : 0u; a.drop_seed = seed; a.drop_inv = 1.0f / (1.0f - drop_p); a.dyn = polus_dyn();
+    a.kskip = polus_cfg().attn_kskip != 0;
     return POLUS_OK;
 }
 
@@ -1441,8 +1509,9 @@ int launch_wide(const char* who, const AttnArgs& a, hipStream_t st) {
 template <int NW>
 int launch_fwd_dma(const AttnArgs& a, hipStream_t st) {
     // the key-bias block grows with S: the limit is raised once, for the longest sequence the kernel takes
-    const size_t lds_max = FWD_RING * FWD_STAGE + (FWD_MAX_S + 64 * NW) * 4;
-    const size_t lds = FWD_RING * FWD_STAGE + (size_t)((a.S + 64 * NW - 1) / (64 * NW)) * 64 * NW * 4;
+    // (+ one key-extent word per wave behind it)
+    const size_t lds_max = FWD_RING * FWD_STAGE + (FWD_MAX_S + 64 * NW) * 4 + NW * 4;
+    const size_t lds = FWD_RING * FWD_STAGE + (size_t)((a.S + 64 * NW - 1) / (64 * NW)) * 64 * NW * 4 + NW * 4;
     return polus_launch_lds<attn_fwd_dma_kernel<NW>>("polus_attention_fwd", dim3((a.S + 16 * NW - 1) / (16 * NW), a.A, a.B), dim3(64 * NW), lds_max, lds, st, a);
 }
 // one pass, one workgroup per (batch, head), 64-key blocks by LDS-DMA
@@ -1453,7 +1522,7 @@ int launch_q64(const AttnArgs& a, hipStream_t st) {
 // one pass, one workgroup per (batch, head), 32-key blocks; S = 16 * NW
 template <int NW>
 int launch_fused(const AttnArgs& a, hipStream_t st) {
-    const size_t lds = 2 * (size_t)a.S * TileCfg<bf16_t>::RS + 4 * (size_t)KBLK * TileCfg<bf16_t>::RS + 2 * (size_t)a.S * RSS + (size_t)a.S * 4;
+    const size_t lds = 2 * (size_t)a.S * TileCfg<bf16_t>::RS + 4 * (size_t)KBLK * TileCfg<bf16_t>::RS + 2 * (size_t)a.S * RSS + (size_t)a.S * 4 + 16;   // ... key bias, four key-extent words
     return polus_launch_lds<attn_bwd_fused_kernel<NW>>("polus_attention_bwd(fused)", dim3(a.A, a.B), dim3(64 * NW), lds, lds, st, a);
 }
 // key-resident one-pass backward: one workgroup per (256-key block, head, batch); with `slabs` (several blocks) each block
