@@ -459,6 +459,67 @@ int polus_l2norm_fwd(int dtype, const void* x, void* y, float* rnorm, int rows, 
 int polus_l2norm_bwd(int dtype, const void* y, const float* rnorm, const void* dy, void* dx, int rows, int E,
                      float eps, void* stream);
 
+/* ---- tuple scoring for retrieval distillation (tuples.hip): query b is scored against its OWN n documents only (an
+ * n-way tuple: the positive and n - 1 negatives, with a teacher's scores for them), not against all N = B n of the step.
+ * The N documents sit in one contiguous buffer; `layout` names the row of document (b, j):
+ *   0, slot-major:  j*B + b  (what the retrieval trainers build: positives first, then negative block i);
+ *   1, query-major: b*n + j.
+ * MaxSim tuples.  Q [B,Lq,E], D [B*n,Ld,E] in `dtype`, contiguous, 16-byte aligned; qmask int32 [B,Lq], dmask int32
+ * [B*n,Ld], NULL = all ones.
+ *   score[b*lds + j] = MaxSim(Q[b], D[doc(b,j)])  (f32, lds >= n);
+ *   argmax int32 [B,n,Lq]: the winning document token, lowest j on ties, -1 for an invalid query token or a document
+ *   without a valid token.
+ * score and argmax are bit for bit what polus_maxsim_fwd writes for the pair (b, doc(b,j)): the same fragments, MFMAs in
+ * ascending k, the same running (value, j) pick, the same xor-shuffle sum of a tile's 16 maxima, tiles added in ascending
+ * order.  One wave per pair keeps the query's tiles in registers and streams the document from global memory (no LDS,
+ * no barrier), skipping the tiles behind its last valid token; queries of more tiles than a wave holds take rounds.
+ * Backward, from dscore f32 [B,n] (row stride lds) and the forward's argmax:
+ *   dQ[b,i]         = sum over j ascending of dscore[b,j] * D[doc(b,j), argmax[b,j,i]]
+ *   dD[doc(b,j), t] = sum over i ascending with argmax[b,j,i] == t of dscore[b,j] * Q[b,i]
+ * f32 fmaf chains in that order from +0, rounded once to `dtype`; every element of dQ and dD is written (0 where nothing
+ * lands); no atomics, no workspace, bitwise reproducible.  Order and arithmetic are polus_maxsim_bwd's, so the results
+ * equal what it gives for a B x N dscore that is zero outside the tuple entries and the all-pairs argmax.
+ * Limits (refused before any launch): dtype f32 or bf16; E a multiple of 32 in [32, 256]; 1 <= Lq, Ld <= 512;
+ * 1 <= B <= 65535; 1 <= n <= 65535; B*n <= 2^31 - 1; B*n*Lq < 2^31; lds >= n; layout 0 or 1; forward: Q and D 16-byte
+ * aligned; no null pointer but the masks. */
+int polus_maxsim_tuples_fwd(int dtype, const void* Q, const void* D, const int32_t* qmask, const int32_t* dmask,
+                            float* score, long lds, int32_t* argmax, int B, int n, int layout, int Lq, int Ld, int E,
+                            void* stream);
+int polus_maxsim_tuples_bwd(int dtype, const void* Q, const void* D, const float* dscore, long lds,
+                            const int32_t* argmax, void* dQ, void* dD, int B, int n, int layout, int Lq, int Ld, int E,
+                            void* stream);
+/* Dot tuples, for single vectors ([CLS] embeddings, SPLADE representations over the vocabulary): q [B,W] (row stride
+ * ldq) and d [B*n,W] (row stride ldd) in `dtype`, the same `layout`.
+ *   score[b*lds + j] = sum_w q[b,w] * d[doc(b,j),w], f32.  Order: a row is cut into chunks of 16 / sizeof(dtype)
+ *   elements; one wave per pair, lane l takes chunks l, l + 64, ... and adds their elements in ascending w to one fmaf
+ *   chain from +0; the 64 lane sums meet in the xor-shuffle tree 32, 16, .., 1.
+ *   dq[b]        = sum over j ascending of dscore[b,j] * d[doc(b,j)]   (fmaf chain from +0, rounded once; stride lddq)
+ *   dd[doc(b,j)] = dscore[b,j] * q[b]                                  (one product, rounded once; stride lddd)
+ * Every element of dq and dd is written.  Whole chunks move as 16-byte accesses when every row pointer involved and
+ * every row stride in bytes is a multiple of 16, element by element otherwise: the same bits either way.
+ * Limits: W >= 1; 1 <= B, n <= 65535; B*n <= 2^31 - 1; lds >= n; row strides >= W; layout 0 or 1. */
+int polus_dot_tuples_fwd(int dtype, const void* q, long ldq, const void* d, long ldd, float* score, long lds,
+                         int B, int n, int layout, int W, void* stream);
+int polus_dot_tuples_bwd(int dtype, const void* q, long ldq, const void* d, long ldd, const float* dscore, long lds,
+                         void* dq, long lddq, void* dd, long lddd, int B, int n, int layout, int W, void* stream);
+/* Distillation losses over tuple scores: student and teacher f32 [rows,n] (row strides lds, ldt), loss f32 [1],
+ * dstudent f32 [rows,n] (row stride ldd), every element written.  A column whose teacher score is -inf (what
+ * polus_maxsim_rerank writes for a missing candidate) is absent: left out of every sum, gradient 0, its student value
+ * never used.  f32 arithmetic, one wave per row, per-row results added in index order by a second kernel: no atomics,
+ * bitwise reproducible.
+ * polus_distill_kl, over the present columns of a row: p = softmax(teacher), s = log_softmax(student), each with its
+ *   own maximum subtracted; loss = sum over rows of sum_j p_j (log p_j - s_j) / rows; dstudent = (softmax(student) - p)
+ *   / rows; a row without a present column adds 0 and gets a zero row.
+ * polus_margin_mse: column 0 is the positive; with m present negatives j >= 1 in a row whose column 0 is present and
+ *   M = the sum of m over those rows, loss = sum over them of ((s_0 - s_j) - (t_0 - t_j))^2 / max(M, 1) and dstudent its
+ *   exact gradient; a row whose column 0 is absent contributes nothing and gets a zero row.
+ * Limits: rows >= 1; 1 <= n <= 1024; row strides >= n; workspace >= polus_distill_workspace_bytes(rows) (host only). */
+size_t polus_distill_workspace_bytes(int rows);
+int polus_distill_kl(const float* student, long lds, const float* teacher, long ldt, float* loss, float* dstudent,
+                     long ldd, int rows, int n, void* workspace, size_t workspace_bytes, void* stream);
+int polus_margin_mse(const float* student, long lds, const float* teacher, long ldt, float* loss, float* dstudent,
+                     long ldd, int rows, int n, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- exact running top-k of score rows, for corpus search (topk.hip).  scores f32 [rows, n], row stride lds >= n;
  * column c is the document with id id0 + c.  top_val f32 and top_id int32, contiguous [rows, k], hold the running
  * state and are rewritten.  Per row:

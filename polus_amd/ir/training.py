@@ -9,7 +9,13 @@ backward: `InBatchDotScores` + `ContrastiveLoss` below are the stock pair.  With
 `compute_scores.backward` returns (dq, dd, dnegs).
 
 Token-level representations (`TokenReps`, from LateInteractionDualEncoder) take the same path: the documents
-are [(k+1)B, Ld, H] in one buffer, and `MaxSimScores` scores them ColBERT-style."""
+are [(k+1)B, Ld, H] in one buffer, and `MaxSimScores` scores them ColBERT-style.
+
+Distillation: `TupleMaxSimScores` / `TupleDotScores` score every query against its own positive and k negatives only
+([B, 1+k] scores), and `DistillKLLoss` / `MarginMSELoss` fit them to a teacher's scores of the same tuples, which reach
+the loss as an optional last element `teacher_scores` [B, 1+k] of the batch of both trainers; `TupleContrastiveLoss` is
+the contrastive objective over the same tuples without a teacher."""
+import numpy as np
 import torch
 
 from .. import _lib, ops
@@ -34,9 +40,19 @@ class EfficientDenseRetrievalTrainer(BaseTrainer):
     def __str__(self):
         return "SimilarityTrainer"
 
-    def forward_without_grads(self, question, positive_doc, negative_doc=None):
+    def forward_without_grads(self, question, positive_doc, negative_doc=None, teacher_scores=None):
         """polus/ir/training.py:47-75.  The document representations land in one [(1+k)B, H] buffer
-        (positives first) so that forward_with_grads can project them in one call without a copy."""
+        (positives first) so that forward_with_grads can project them in one call without a copy.
+        `teacher_scores` ([B, 1+k], positive first, host or device), the optional last element of a distillation
+        batch, is checked before anything is launched and travels on to the loss as f32 on the device."""
+        if teacher_scores is None:
+            return self._encode(question, positive_doc, negative_doc)
+        if negative_doc is None:
+            raise ValueError("teacher_scores need explicit negatives: a one-column tuple has nothing to contrast")
+        t = _teacher_scores(teacher_scores, question["input_ids"].shape[0], negative_doc["input_ids"].shape[1])
+        return self._encode(question, positive_doc, negative_doc) + (t,)
+
+    def _encode(self, question, positive_doc, negative_doc=None):
         q = self.model.encode_query(question, training=True)
         if negative_doc is None:
             return q, self.model.encode_document(positive_doc, training=True)
@@ -97,8 +113,12 @@ class EfficientDenseRetrievalTrainer(BaseTrainer):
         negs = [TokenReps(dall[B * (i + 1):B * (i + 2)], dmask[B * (i + 1):B * (i + 2)]) for i in range(k)]
         return self.compute_scores(q, d, *negs)
 
-    def forward_with_grads(self, question, positive_doc, negative_doc=None):
-        """polus/ir/training.py:77-117."""
+    def forward_with_grads(self, question, positive_doc, negative_doc=None, teacher_scores=None):
+        """polus/ir/training.py:77-117; with `teacher_scores` the loss gets them as a third argument."""
+        scores = self._scores(question, positive_doc, negative_doc)
+        return scores if teacher_scores is None else tuple(scores) + (teacher_scores,)
+
+    def _scores(self, question, positive_doc, negative_doc=None):
         if isinstance(question, TokenReps):
             return self._token_forward_with_grads(question, positive_doc, negative_doc)
         q = self.model.query_projection(question, training=True)
@@ -208,15 +228,7 @@ class MaxSimScores:
         if any(n.values.shape[1] != Ld for n in negs):
             raise ValueError("token-level scoring needs the positives and negatives padded to one length")
         if k:
-            parts = (d,) + negs
-            if all(_adjacent_rows(a.values.reshape(-1, E), b.values.reshape(-1, E)) for a, b in zip(parts[:-1], parts[1:])):
-                dv = torch.as_strided(d.values, ((k + 1) * B, Ld, E), (Ld * E, E, 1))
-            else:
-                dv = torch.cat([p.values.reshape(-1, Ld, E) for p in parts], 0)
-            if all(_adjacent_rows(a.mask.reshape(-1, Ld), b.mask.reshape(-1, Ld)) for a, b in zip(parts[:-1], parts[1:])):
-                dm = torch.as_strided(d.mask, ((k + 1) * B, Ld), (Ld, 1))
-            else:
-                dm = torch.cat([p.mask.reshape(-1, Ld) for p in parts], 0)
+            dv, dm = _token_parts((d,) + negs, B, Ld, E)
         else:
             dv, dm = d.values.contiguous(), d.mask.contiguous()
         self.k, self.B = k, B
@@ -273,6 +285,147 @@ class ContrastiveLoss:
         if self.d.shape[1] == self._split:
             return self.d, None
         return self.d[:, :self._split], self.d[:, self._split:]
+
+
+def _token_parts(parts, B, Ld, E):
+    """The token vectors [len(parts) B, Ld, E] and masks [len(parts) B, Ld] of `parts` (TokenReps of B documents
+    each, slot-major): views where the parts are adjacent rows of one buffer, concatenations otherwise."""
+    n = len(parts)
+    if all(_adjacent_rows(a.values.reshape(-1, E), b.values.reshape(-1, E)) for a, b in zip(parts[:-1], parts[1:])):
+        dv = torch.as_strided(parts[0].values, (n * B, Ld, E), (Ld * E, E, 1))
+    else:
+        dv = torch.cat([p.values.reshape(-1, Ld, E) for p in parts], 0)
+    if all(_adjacent_rows(a.mask.reshape(-1, Ld), b.mask.reshape(-1, Ld)) for a, b in zip(parts[:-1], parts[1:])):
+        dm = torch.as_strided(parts[0].mask, (n * B, Ld), (Ld, 1))
+    else:
+        dm = torch.cat([p.mask.reshape(-1, Ld) for p in parts], 0)
+    return dv, dm
+
+
+def _teacher_scores(t, B, k, dev=None):
+    """A batch's teacher scores as f32 [B, 1+k] on the device; ValueError (before anything is launched) for another
+    shape."""
+    shape = tuple(t.shape) if hasattr(t, "shape") else tuple(np.shape(t))
+    if shape != (B, 1 + k):
+        raise ValueError(f"teacher_scores must be [B, 1+k] = [{B}, {1 + k}], positive first (got {list(shape)})")
+    return to_device(t, torch.float32, dev)
+
+
+class TupleMaxSimScores(MaxSimScores):
+    """MaxSim of every query against its OWN documents only (n-way tuples: the positive and the k explicit negatives
+    of the query), for distillation from a teacher's scores of the same tuples and for contrastive training without
+    in-batch negatives.  The call contract of MaxSimScores: called with TokenReps q [B, Lq, E], d [B, Ld, E] and k >= 1
+    negatives [B, Ld, E] each, it returns the column blocks (pos [B, 1], neg [B, k]) of one f32 [B, 1+k] matrix;
+    `backward` returns (dq, dd, dnegs [k, B, Ld, E]).  `argmax` is int32 [B, 1+k, Lq].  1/B of MaxSimScores' pairs are
+    scored, with the bits MaxSimScores gives those pairs (ops.maxsim_tuples_fwd)."""
+
+    def __call__(self, q, d, *negs):
+        if not negs:
+            raise ValueError("TupleMaxSimScores needs explicit negatives: a one-column tuple has nothing to contrast")
+        qv, qm = q.values.contiguous(), q.mask.contiguous()
+        B, Lq, E = qv.shape
+        k = len(negs)
+        Ld = d.values.shape[1]
+        if any(n.values.shape[1] != Ld for n in negs):
+            raise ValueError("token-level scoring needs the positives and negatives padded to one length")
+        dv, dm = _token_parts((d,) + negs, B, Ld, E)               # slot-major either way
+        self.k, self.B = k, B
+        if self.normalize:
+            (self.q, self._rq), (self.docs, self._rd) = self._norm(qv), self._norm(dv)
+        else:
+            self.q, self.docs = qv, dv
+        self.scores = torch.empty((B, 1 + k), dtype=torch.float32, device=qv.device)
+        self.argmax = torch.empty((B, 1 + k, Lq), dtype=torch.int32, device=qv.device)
+        ops.maxsim_tuples_fwd(self.q, self.docs, qm, dm, self.scores, self.argmax, ops.SLOT_MAJOR)
+        return self.scores[:, :1], self.scores[:, 1:]
+
+    def backward(self, dpos, dneg):
+        B, k = self.B, self.k
+        ds = _whole(dpos, dneg)
+        dq, dd = torch.empty_like(self.q), torch.empty_like(self.docs)
+        ops.maxsim_tuples_bwd(self.q, self.docs, ds, self.argmax, dq, dd, ops.SLOT_MAJOR)
+        if self.normalize:
+            gq, gd = torch.empty_like(dq), torch.empty_like(dd)
+            ops.l2norm_bwd(self.q, self._rq, dq, gq, self.eps)
+            ops.l2norm_bwd(self.docs, self._rd, dd, gd, self.eps)
+            dq, dd = gq, gd
+        return dq, dd[:B], dd[B:].view(k, B, *dd.shape[1:])
+
+
+class TupleDotScores:
+    """Dot products of every query with its own documents only: InBatchDotScores' call contract over single vectors
+    q [B, W], d [B, W] and k >= 1 negatives [B, W] each (f32 or bf16, any W: [CLS] embeddings, SPLADE representations
+    over the vocabulary), returning the column blocks (pos [B, 1], neg [B, k]) of one f32 [B, 1+k] matrix; `backward`
+    returns (dq, dd, dnegs [k, B, W])."""
+    any_width = True               # no GEMM behind it: SparseRetrievalTrainer need not pad the rows to 16 bytes
+
+    def __call__(self, q, d, *negs):
+        if not negs:
+            raise ValueError("TupleDotScores needs explicit negatives: a one-column tuple has nothing to contrast")
+        self.q = q if q.stride(-1) == 1 else q.contiguous()
+        B, W = self.q.shape
+        k = len(negs)
+        if all(_adjacent_rows(a.reshape(-1, W), b.reshape(-1, W)) for a, b in zip((d,) + negs[:-1], negs)):
+            docs = torch.as_strided(d, ((k + 1) * B, W), (W, 1))
+        else:
+            docs = torch.cat([d] + [n.reshape(-1, W) for n in negs], 0)
+        self.docs, self.k = docs, k
+        self.scores = torch.empty((B, 1 + k), dtype=torch.float32, device=q.device)
+        ops.dot_tuples_fwd(self.q, docs, self.scores, ops.SLOT_MAJOR)
+        return self.scores[:, :1], self.scores[:, 1:]
+
+    def backward(self, dpos, dneg):
+        B, W = self.q.shape
+        ds = _whole(dpos, dneg)
+        dq, ddocs = torch.empty_like(self.q), torch.empty_like(self.docs)
+        ops.dot_tuples_bwd(self.q, self.docs, ds, dq, ddocs, ops.SLOT_MAJOR)
+        return dq, ddocs[:B], ddocs[B:].view(self.k, B, W)
+
+
+class TupleContrastiveLoss:
+    """softmax cross-entropy over each query's own tuple of scores [positive | explicit negatives], column 0 the
+    label: contrastive training without in-batch negatives."""
+
+    def __call__(self, pos_scores, neg_scores):
+        s = _whole(pos_scores, neg_scores)
+        labels = torch.zeros(s.shape[0], dtype=torch.int32, device=s.device)
+        self.loss = torch.empty(1, dtype=torch.float32, device=s.device)
+        self.d = torch.empty_like(s)
+        ops.softmax_xent(s, labels, self.loss, self.d)
+        return DeviceScalar(self.loss)
+
+    def backward(self, accumulate=False):
+        return self.d[:, :1], self.d[:, 1:]
+
+
+class _DistillLoss:
+    """A loss of the student's tuple scores [positive | negatives] against a teacher's scores of the same tuples
+    (f32 [B, 1+k], host or device; -inf marks a column the teacher has no score for, which is left out).  The device
+    scalar stays in `.loss` (SparseRetrievalTrainer adds its FLOPS terms to it)."""
+    _op = None
+
+    def __call__(self, pos_scores, neg_scores, teacher_scores):
+        s = _whole(pos_scores, neg_scores)
+        t = _teacher_scores(teacher_scores, s.shape[0], s.shape[1] - 1, s.device)
+        self.loss = torch.empty(1, dtype=torch.float32, device=s.device)
+        self.d = torch.empty_like(s)
+        self._op(s, t, self.loss, self.d)
+        return DeviceScalar(self.loss)
+
+    def backward(self, accumulate=False):
+        return self.d[:, :1], self.d[:, 1:]
+
+
+class DistillKLLoss(_DistillLoss):
+    """ColBERTv2's distillation objective: the mean over the queries of KL(softmax(teacher) || softmax(student)) over
+    each query's own tuple (ops.distill_kl)."""
+    _op = staticmethod(ops.distill_kl)
+
+
+class MarginMSELoss(_DistillLoss):
+    """MarginMSE (Hofstaetter et al.): the mean over every (query, negative) pair of the squared difference between
+    the student's margin s_pos - s_neg and the teacher's (ops.margin_mse)."""
+    _op = staticmethod(ops.margin_mse)
 
 
 class SparseRetrievalTrainer(BaseTrainer):
@@ -338,20 +491,25 @@ class SparseRetrievalTrainer(BaseTrainer):
                 self._widths[key] = (V + 3) // 4 * 4
         return self._widths[key]
 
-    def forward_with_grads(self, question, positive_doc, negative_doc=None):
-        batch, k = self._one_batch(question, positive_doc, negative_doc)
+    def forward_with_grads(self, question, positive_doc, negative_doc=None, teacher_scores=None):
         B = question["input_ids"].shape[0]
+        if teacher_scores is not None:                              # checked before anything is launched
+            if negative_doc is None:
+                raise ValueError("teacher_scores need explicit negatives: a one-column tuple has nothing to contrast")
+            teacher_scores = _teacher_scores(teacher_scores, B, negative_doc["input_ids"].shape[1])
+        batch, k = self._one_batch(question, positive_doc, negative_doc)
         self._B, self._n_neg = B, k
         rep = self.model(**batch, training=True)                   # f32 [(2 + k) B, V]
         self.reps = rep
-        W = self._gemm_width(rep)
+        W = rep.shape[1] if getattr(self.compute_scores, "any_width", False) else self._gemm_width(rep)
         self._V = rep.shape[1]
         if W != rep.shape[1]:
             wide = torch.zeros((rep.shape[0], W), dtype=rep.dtype, device=rep.device)
             wide[:, :rep.shape[1]].copy_(rep)
             rep = wide
         negs = [rep[B * (2 + i):B * (3 + i)] for i in range(k)]
-        return self.compute_scores(rep[:B], rep[B:2 * B], *negs)
+        scores = self.compute_scores(rep[:B], rep[B:2 * B], *negs)
+        return scores if teacher_scores is None else tuple(scores) + (teacher_scores,)
 
     def backward_from_loss(self, accumulate=False):
         B, k, V, rep = self._B, self._n_neg, self._V, self.reps

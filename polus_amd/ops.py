@@ -813,6 +813,106 @@ def l2norm_bwd(y, rnorm, dy, dx, eps=1e-12):
           "polus_l2norm_bwd")
 
 
+SLOT_MAJOR, QUERY_MAJOR = 0, 1          # tuple layouts: document (b, j) at row j*B + b / b*n + j
+
+
+def _tuple_shapes(q, d, name):
+    B, Lq, E = q.shape
+    assert d.dim() == 3 and d.shape[2] == E and d.dtype == q.dtype and q.is_contiguous() and d.is_contiguous()
+    assert d.shape[0] % B == 0, f"{name}: {d.shape[0]} documents are not n per query for {B} queries"
+    return B, d.shape[0] // B, Lq, d.shape[1], E
+
+
+def maxsim_tuples_fwd(q, d, qmask, dmask, score, argmax, layout=SLOT_MAJOR):
+    """score[b, j] (f32, any row stride >= n) = MaxSim(q[b], d[doc(b, j)]) of query b and its own n documents, and
+    argmax[b, j, i] (int32 [B, n, Lq]) the winning document token: bit for bit what maxsim_fwd gives that pair.
+    q [B, Lq, E], d [B n, Ld, E]; document (b, j) is row j*B + b (layout SLOT_MAJOR) or b*n + j (QUERY_MAJOR)
+    (include/polus_hip.h polus_maxsim_tuples_fwd)."""
+    _req_cuda(q, d, qmask, dmask, score, argmax)
+    B, n, Lq, Ld, E = _tuple_shapes(q, d, "maxsim_tuples_fwd")
+    assert score.dtype == torch.float32 and score.dim() == 2 and score.shape[0] >= B and score.shape[1] >= n
+    assert score.stride(1) == 1 or score.shape[1] == 1
+    assert argmax.dtype == torch.int32 and argmax.is_contiguous() and argmax.numel() == B * n * Lq
+    lds = score.stride(0) if score.shape[0] > 1 else max(score.stride(0), n)
+    check(_lib.load().polus_maxsim_tuples_fwd(dtype_code(q.dtype), ptr(q), ptr(d), ptr(_maxsim_mask(qmask, B, Lq, "qmask")),
+                                              ptr(_maxsim_mask(dmask, B * n, Ld, "dmask")), ptr(score), lds, ptr(argmax),
+                                              B, n, int(layout), Lq, Ld, E, _st()), "polus_maxsim_tuples_fwd")
+
+
+def maxsim_tuples_bwd(q, d, dscore, argmax, dq, dd, layout=SLOT_MAJOR):
+    """dq [B, Lq, E] and dd [B n, Ld, E] from dscore (f32 [B, n], row stride free) and the forward's argmax; every
+    element is written, with the bits maxsim_bwd gives for the dscore scattered into a zero [B, B n] matrix."""
+    _req_cuda(q, d, dscore, argmax, dq, dd)
+    B, n, Lq, Ld, E = _tuple_shapes(q, d, "maxsim_tuples_bwd")
+    assert dscore.dtype == torch.float32 and dscore.dim() == 2 and dscore.shape[0] >= B and dscore.shape[1] >= n
+    assert dscore.stride(1) == 1 or dscore.shape[1] == 1
+    assert argmax.dtype == torch.int32 and argmax.is_contiguous() and argmax.numel() == B * n * Lq
+    assert dq.shape == q.shape and dd.shape == d.shape and dq.dtype == q.dtype and dd.dtype == d.dtype
+    assert dq.is_contiguous() and dd.is_contiguous()
+    lds = dscore.stride(0) if dscore.shape[0] > 1 else max(dscore.stride(0), n)
+    check(_lib.load().polus_maxsim_tuples_bwd(dtype_code(q.dtype), ptr(q), ptr(d), ptr(dscore), lds, ptr(argmax),
+                                              ptr(dq), ptr(dd), B, n, int(layout), Lq, Ld, E, _st()),
+          "polus_maxsim_tuples_bwd")
+
+
+def _dot_tuple_shapes(q, d, name):
+    assert q.dim() == 2 and d.dim() == 2 and d.dtype == q.dtype and d.shape[1] == q.shape[1], f"{name}: q [B, W], d [B n, W]"
+    B, W = q.shape
+    assert d.shape[0] % B == 0, f"{name}: {d.shape[0]} documents are not n per query for {B} queries"
+    return B, d.shape[0] // B, W
+
+
+def dot_tuples_fwd(q, d, score, layout=SLOT_MAJOR):
+    """score[b, j] (f32, any row stride >= n) = <q[b], d[doc(b, j)]>, accumulated in f32 in a fixed order; q [B, W] and
+    d [B n, W] f32 or bf16 with free row strides (include/polus_hip.h polus_dot_tuples_fwd)."""
+    _req_cuda(q, d, score)
+    B, n, W = _dot_tuple_shapes(q, d, "dot_tuples_fwd")
+    ldq, ldd = _rows2d(q, q.dtype, B, W, "q"), _rows2d(d, q.dtype, B * n, W, "d")
+    lds = _rows2d(score, torch.float32, B, n, "score")
+    check(_lib.load().polus_dot_tuples_fwd(dtype_code(q.dtype), ptr(q), ldq, ptr(d), ldd, ptr(score), lds, B, n, int(layout),
+                                           W, _st()), "polus_dot_tuples_fwd")
+    return score
+
+
+def dot_tuples_bwd(q, d, dscore, dq, dd, layout=SLOT_MAJOR):
+    """dq[b] = sum over j ascending of dscore[b, j] d[doc(b, j)] and dd[doc(b, j)] = dscore[b, j] q[b], f32 arithmetic
+    rounded once; dscore f32 [B, n]; every element of dq and dd (free row strides) is written."""
+    _req_cuda(q, d, dscore, dq, dd)
+    B, n, W = _dot_tuple_shapes(q, d, "dot_tuples_bwd")
+    ldq, ldd = _rows2d(q, q.dtype, B, W, "q"), _rows2d(d, q.dtype, B * n, W, "d")
+    lddq, lddd = _rows2d(dq, q.dtype, B, W, "dq"), _rows2d(dd, q.dtype, B * n, W, "dd")
+    lds = _rows2d(dscore, torch.float32, B, n, "dscore")
+    check(_lib.load().polus_dot_tuples_bwd(dtype_code(q.dtype), ptr(q), ldq, ptr(d), ldd, ptr(dscore), lds, ptr(dq), lddq,
+                                           ptr(dd), lddd, B, n, int(layout), W, _st()), "polus_dot_tuples_bwd")
+
+
+def _distill(fn, student, teacher, loss, dstudent):
+    lib = _lib.load()
+    _req_cuda(student, teacher, loss, dstudent)
+    rows, n = student.shape
+    lds, ldt = _rows2d(student, torch.float32, rows, n, "student"), _rows2d(teacher, torch.float32, rows, n, "teacher")
+    ldd = _rows2d(dstudent, torch.float32, rows, n, "dstudent")
+    assert teacher.shape == student.shape and dstudent.shape == student.shape
+    assert loss.dtype == torch.float32 and loss.numel() >= 1
+    nb = lib.polus_distill_workspace_bytes(rows)
+    ws = workspace(student.device).get(nb)
+    check(getattr(lib, fn)(ptr(student), lds, ptr(teacher), ldt, ptr(loss), ptr(dstudent), ldd, rows, n, ptr(ws), nb, _st()),
+          fn)
+
+
+def distill_kl(student, teacher, loss, dstudent):
+    """loss (f32 [1]) = mean over the rows of KL(softmax(teacher) || softmax(student)) over the present columns, and
+    dstudent its gradient; student, teacher, dstudent f32 [rows, n] with free row strides; a column whose teacher score
+    is -inf is absent (include/polus_hip.h polus_distill_kl)."""
+    _distill("polus_distill_kl", student, teacher, loss, dstudent)
+
+
+def margin_mse(student, teacher, loss, dstudent):
+    """loss (f32 [1]) = mean over the present negatives j >= 1 of every row of ((s_0 - s_j) - (t_0 - t_j))^2, column 0
+    the positive, and dstudent its gradient; same arguments as distill_kl (include/polus_hip.h polus_margin_mse)."""
+    _distill("polus_margin_mse", student, teacher, loss, dstudent)
+
+
 def argmax(x, out, rows=None, C=None):
     lib = _lib.load()
     _req_cuda(x, out)
