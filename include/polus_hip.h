@@ -520,6 +520,46 @@ int polus_distill_kl(const float* student, long lds, const float* teacher, long 
 int polus_margin_mse(const float* student, long lds, const float* teacher, long ldt, float* loss, float* dstudent,
                      long ldd, int rows, int n, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- cross-encoder pair rows (pairs.hip; HF BertTokenizer(q, d, truncation="only_second", padding="max_length")
+ * restated over token ids): a reranker scores pairs `[CLS] query [SEP] document [SEP]`, built here on the device from
+ * query rows, document rows and a candidate table.  Integers only: every result is exact.
+ * Inputs.  q_ids, qmask int32 [B, Lq] (row strides ldq, ldqm); d_ids, dmask int32 [N, Ld] (row strides ldd, lddm); a
+ *   NULL mask is all ones.  cand int32 [B, n], row stride ldc.
+ * Valid tokens.  The valid tokens of a row are those whose mask is non-zero, in order: holes and left padding are
+ *   compacted away.
+ * Stripping.  Of a query's valid tokens the first q_head and the last q_tail are dropped, of a document's the first
+ *   d_head and the last d_tail; each count is in 0..8, and dropping more than there are leaves none.  1/1 takes the
+ *   [CLS] and [SEP] off HF-tokenised inputs, 0/0 uses raw ids as they are.  nq, nd = what is left.
+ * Truncation.  nq' = min(nq, max_q), nd' = min(nd, S - 3 - nq'), the FIRST tokens of each (HF's only_second).
+ *   S >= max_q + 3 is required.
+ * Pair index.  Pair p has query b = p / n and document cand[b*ldc + p % n].  Output row r is pair rows[r] (int32 [R]),
+ *   or pair r when rows is NULL; the same p may appear more than once in rows.  A value of rows outside [0, B*n) is
+ *   the caller's error: it is not detected and reads out of bounds.
+ * Output row.  cls, q'.., sep, d'.., sep, then pad up to S.  token_type_ids is 0 through the first sep, 1 through the
+ *   second and 0 on padding; attention_mask is 1 on the length = nq' + nd' + 3 real tokens and 0 behind them.
+ * Missing candidates.  A candidate id outside [0, N) gives the empty-document pair `cls q' sep sep` (length nq' + 3); no
+ *   document memory is read for it.  No row comes out fully masked: length >= 3.
+ * Writes.  Every element of the S columns of input_ids, token_type_ids and attention_mask (int32 [R, S], one row
+ *   stride ldo >= S) is written, and nothing beyond column S - 1.
+ * polus_pair_lengths writes only length int32 [R], from the same arguments (the host plans buckets from it).
+ * polus_pair_pack writes the three outputs and length (NULL: not written).  One wave per output row; compaction by
+ *   __ballot and a popcount prefix over 64-token steps; plain stores, no LDS, no atomics, no workspace.
+ * polus_pair_scatter_scores, for DISTINCT rows: out[b*ldo + j] = s[r] when the candidate of pair rows[r] = b*n + j
+ *   exists and -inf when it does not (what polus_maxsim_rerank writes and polus_distill_kl reads as "absent"); s f32
+ *   [R]; entries of out (f32 [B, n], row stride ldo) that rows does not name are left alone.
+ * Limits (refused before any launch): no null pointer but the masks, rows and polus_pair_pack's length; R, B, n, N,
+ *   Lq, Ld >= 1; B*n <= 2^31 - 1; row strides >= the widths; strips in 0..8; max_q >= 0; S >= max_q + 3. */
+int polus_pair_lengths(const int32_t* qmask, long ldqm, const int32_t* dmask, long lddm, const int32_t* cand, long ldc,
+                       const int32_t* rows, int R, int B, int n, int N, int Lq, int Ld, int q_head, int q_tail,
+                       int d_head, int d_tail, int max_q, int S, int32_t* length, void* stream);
+int polus_pair_pack(const int32_t* q_ids, long ldq, const int32_t* qmask, long ldqm, const int32_t* d_ids, long ldd,
+                    const int32_t* dmask, long lddm, const int32_t* cand, long ldc, const int32_t* rows, int R, int B,
+                    int n, int N, int Lq, int Ld, int q_head, int q_tail, int d_head, int d_tail, int max_q, int S,
+                    int cls, int sep, int pad, int32_t* input_ids, int32_t* token_type_ids, int32_t* attention_mask,
+                    long ldo, int32_t* length, void* stream);
+int polus_pair_scatter_scores(const float* s, const int32_t* rows, const int32_t* cand, long ldc, int R, int B, int n,
+                              int N, float* out, long ldo, void* stream);
+
 /* ---- exact running top-k of score rows, for corpus search (topk.hip).  scores f32 [rows, n], row stride lds >= n;
  * column c is the document with id id0 + c.  top_val f32 and top_id int32, contiguous [rows, k], hold the running
  * state and are rewritten.  Per row:

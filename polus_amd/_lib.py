@@ -90,6 +90,10 @@ SIGNATURES = {
     "polus_distill_workspace_bytes": (_sz, [_i]),
     "polus_distill_kl": (_i, [_vp, _l, _vp, _l, _vp, _vp, _l, _i, _i, _vp, _sz, _vp]),
     "polus_margin_mse": (_i, [_vp, _l, _vp, _l, _vp, _vp, _l, _i, _i, _vp, _sz, _vp]),
+    "polus_pair_lengths": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "polus_pair_pack": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
+                             _i, _i, _i, _vp, _vp, _vp, _l, _vp, _vp]),
+    "polus_pair_scatter_scores": (_i, [_vp, _vp, _vp, _l, _i, _i, _i, _i, _vp, _l, _vp]),
     "polus_topk_merge": (_i, [_vp, _l, _i, _i, _c.c_int32, _vp, _vp, _i, _i, _vp]),
     "polus_topk_merge_ids": (_i, [_vp, _l, _vp, _l, _i, _i, _vp, _vp, _i, _i, _vp]),
     "polus_centroid_scores_route": (_i, [_i, _i, _i, _i, _i, _c.POINTER(_i)]),

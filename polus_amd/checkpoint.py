@@ -105,6 +105,40 @@ def load_bert_for_masked_lm_from_local(path, compute_dtype="bf16"):
     return model
 
 
+def read_local_cross_encoder(path):
+    """(config dict, params dict) of a local HF BertForSequenceClassification(num_labels=1) directory in CrossEncoder's
+    naming: bert.* as hf_state_to_params maps it (emb.*, layer{i}.*, pooler.*) and classifier.{weight,bias} as
+    classifier.{w,b}.  Host only.  A checkpoint without the pooler or with another number of labels is an error."""
+    if not os.path.isdir(path):
+        raise FileNotFoundError(f"'{path}' is not a local directory: checkpoints cannot be fetched by name (no network)")
+    c, params = read_local_hf_checkpoint(path)
+    if "pooler.w" not in params:
+        raise ValueError(f"{path}: no bert.pooler.dense.* (a cross-encoder scores the pooled [CLS] state)")
+    if "head.w" not in params:
+        raise ValueError(f"{path}: no classifier.* (not a BertForSequenceClassification checkpoint)")
+    w, b = params.pop("head.w"), params.pop("head.b")
+    if w.shape != (1, c["hidden_size"]) or b.shape != (1,):
+        raise ValueError(f"{path}: classifier.weight is {list(w.shape)}: a cross-encoder has num_labels = 1")
+    params["classifier.w"], params["classifier.b"] = w, b
+    return c, params
+
+
+def load_cross_encoder_from_local(path, compute_dtype="bf16"):
+    """A local HF BertForSequenceClassification(num_labels=1) directory -> polus_amd.ir.models.CrossEncoder."""
+    from .ir.models import CrossEncoder
+    from .models import BertConfig
+    c, params = read_local_cross_encoder(path)
+    cfg = BertConfig(vocab_size=c["vocab_size"], hidden_size=c["hidden_size"], num_hidden_layers=c["num_hidden_layers"],
+                     num_attention_heads=c["num_attention_heads"], intermediate_size=c["intermediate_size"],
+                     max_position_embeddings=c["max_position_embeddings"], type_vocab_size=c.get("type_vocab_size", 2),
+                     layer_norm_eps=c.get("layer_norm_eps", 1e-12),
+                     hidden_dropout_prob=c.get("hidden_dropout_prob", 0.1),
+                     attention_probs_dropout_prob=c.get("attention_probs_dropout_prob", 0.1), _name_or_path=path)
+    model = CrossEncoder(cfg, compute_dtype=compute_dtype)
+    model.load_numpy_params(params)
+    return model
+
+
 def load_weights(model, path):
     """Inverse of SavableModel.save: <path>.npz -> model.set_weights (weight{i} order = get_weights())."""
     z = np.load(path if path.endswith(".npz") else path + ".npz", allow_pickle=False)

@@ -210,6 +210,125 @@ class SpladeEncoder(SavableModel):
     document_projection = query_projection
 
 
+CROSS_DROPOUT_SITE = 3        # BertModel's own sites are 0..2 of layers -1..L-1; the head's dropout is site 3 of layer L-1
+
+
+class CrossEncoder(SavableModel):
+    """A cross-encoder reranker, HF BertForSequenceClassification(num_labels=1): the pair row `[CLS] query [SEP]
+    document [SEP]` goes through BERT as ONE sequence and score = classifier(dropout(pooler_output)), one f32 number
+    per pair.  The teacher the distillation losses of polus_amd/ir/training.py fit a retriever to, and the last stage
+    behind TwoStageSearch (polus_amd/ir/cross.py CrossEncoderIndex).
+
+    One arena: BertModel(add_pooling_layer=True)'s variables, then classifier.{w,b} (Dense(1), f32 out, the
+    polus_dense_thin kernels) with the highest offsets, reported final first.  The dropout between pooler and
+    classifier is hidden_dropout_prob in training only (polus_dropout, regenerated in backward), seeded by
+    `site_seed(last layer, 3)`, which no site of the encoder uses.
+
+    `call(input_ids, attention_mask, token_type_ids, training)` returns f32 [P]; `backward(dscore)` takes f32 [P] (or
+    [P, 1]).  Savable through `cross_encoder`."""
+
+    def __init__(self, cfg, compute_dtype="bf16", seed=1234, name="cross_encoder"):
+        super().__init__(name)
+        self.config = cfg
+        self.compute_dtype = COMPUTE_DTYPES[compute_dtype]
+        mode = "bf16" if self.compute_dtype == torch.bfloat16 else "f32"
+        self.savable_config = {"func_name": "cross_encoder", "model": dict(cfg.to_dict(), compute_dtype=mode, seed=seed)}
+        self.arena = ParamArena(self.compute_dtype)
+        self.bert = BertModel(cfg, compute_dtype=mode, seed=seed, arena=self.arena, add_pooling_layer=True)
+        self.bert.grad_ready_hook = self.__dict__.get("_hook")
+        self.classifier = Dense(1, out_dtype=torch.float32, name="classifier")
+        self.classifier.build(self.arena, cfg.hidden_size, "classifier")
+        self.arena.finalize()
+        self._bufs = {}
+        self._stash = None
+
+    # the trainer sets these on the model it holds; the encoder inside reads them
+    @property
+    def grad_ready_hook(self):
+        return self.__dict__.get("_hook")
+
+    @grad_ready_hook.setter
+    def grad_ready_hook(self, hook):
+        self.__dict__["_hook"] = hook
+        if "bert" in self.__dict__:
+            self.bert.grad_ready_hook = hook
+
+    @property
+    def dropout_step(self):
+        return self.bert.dropout_step
+
+    @dropout_step.setter
+    def dropout_step(self, step):
+        self.bert.dropout_step = step
+
+    @property
+    def overlap_dw(self):
+        return self.bert.overlap_dw
+
+    @overlap_dw.setter
+    def overlap_dw(self, on):
+        self.bert.overlap_dw = on
+
+    def site_seed(self, layer, site, step=None):
+        return self.bert.site_seed(layer, site, step)
+
+    def load_numpy_params(self, params):
+        """params: dict in the emb.* / layer{i}.* / pooler.* / classifier.* naming; names it lacks keep their values."""
+        for v in self.arena.vars:
+            if v.name in params:
+                v.assign(params[v.name])
+
+    def _buf(self, key, shape, dtype):
+        t = self._bufs.get(key)
+        if t is None or t.shape != tuple(shape) or t.dtype != dtype:
+            t = self._bufs[key] = torch.empty(tuple(shape), dtype=dtype, device=self.arena.device)
+        return t
+
+    def call(self, input_ids=None, attention_mask=None, token_type_ids=None, training=False, **kw):
+        if isinstance(input_ids, dict):
+            d = input_ids
+            input_ids, attention_mask = d.get("input_ids"), d.get("attention_mask", attention_mask)
+            token_type_ids = d.get("token_type_ids", token_type_ids)
+        L =self.config.num_hidden_layers - 1
+        seed = self.site_seed(L, CROSS_DROPOUT_SITE) if training else 0      # before the encoder advances dropout_step
+        out = self.bert(input_ids=input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids, training=training)
+        self.tokens_per_step = self.bert.tokens_per_step
+        pooled = out.pooler_output
+        p = self.config.hidden_dropout_prob if training else 0.0
+        if p > 0.0:
+            dropped = self._buf("dropped", pooled.shape, pooled.dtype)
+            ops.dropout(pooled, dropped, p, seed)
+            pooled = dropped
+        score = self.classifier.forward(pooled, training)                   # f32 [P, 1]
+        self._stash = (p, seed) if training else None
+        return score.view(-1)
+
+    def backward(self, dscore, accumulate=False):
+        """dscore f32 [P] or [P, 1]: the gradient wrt the scores of the last training forward pass.  Parameter gradients
+        land in the arena, overwritten or, with `accumulate`, added to."""
+        if self._stash is None:
+            raise RuntimeError("CrossEncoder.backward: the last forward pass ran with training=False (nothing was kept for backward)")
+        p, seed = self._stash
+        P = self.bert._shape[0]
+        if dscore.dtype != torch.float32 or dscore.numel() != P:
+            raise TypeError(f"CrossEncoder.backward: dscore must be float32 with {P} elements, got {dscore.dtype} {tuple(dscore.shape)}")
+        dpooled = self.classifier.backward(dscore.reshape(P, 1), accumulate)
+        self._notify(self.classifier.variables())
+        if p > 0.0:
+            d = self._buf("ddropped", dpooled.shape, dpooled.dtype)
+            ops.dropout(dpooled, d, p, seed)
+            dpooled = d
+        self.bert.deterministic = self.deterministic
+        return self.bert.backward(None, accumulate=accumulate, dpooled=dpooled)
+
+
+@from_config
+def cross_encoder(**kw):
+    """Builder behind CrossEncoder.save / load_model: the BertConfig fields + compute_dtype, seed."""
+    cfg = BertConfig(**{k: kw[k] for k in _BERT_CFG_KEYS if k in kw})
+    return CrossEncoder(cfg, compute_dtype=kw.get("compute_dtype", "bf16"), seed=kw.get("seed", 1234))
+
+
 @from_config
 def splade_encoder(**kw):
     """Builder behind SpladeEncoder.save / load_model: the BertForMaskedLM's BertConfig fields + compute_dtype, seed."""

@@ -14,7 +14,11 @@ are [(k+1)B, Ld, H] in one buffer, and `MaxSimScores` scores them ColBERT-style.
 Distillation: `TupleMaxSimScores` / `TupleDotScores` score every query against its own positive and k negatives only
 ([B, 1+k] scores), and `DistillKLLoss` / `MarginMSELoss` fit them to a teacher's scores of the same tuples, which reach
 the loss as an optional last element `teacher_scores` [B, 1+k] of the batch of both trainers; `TupleContrastiveLoss` is
-the contrastive objective over the same tuples without a teacher."""
+the contrastive objective over the same tuples without a teacher.
+
+Cross-encoder: `CrossEncoderTrainer` takes the same batches, builds the (1+k)B pair rows `cls q sep d sep` on the device
+(ops.pair_pack) and trains a CrossEncoder end to end; its [B, 1+k] scores go to the tuple losses above or to
+`PointwiseBCELoss`."""
 import numpy as np
 import torch
 
@@ -426,6 +430,124 @@ class MarginMSELoss(_DistillLoss):
     """MarginMSE (Hofstaetter et al.): the mean over every (query, negative) pair of the squared difference between
     the student's margin s_pos - s_neg and the teacher's (ops.margin_mse)."""
     _op = staticmethod(ops.margin_mse)
+
+
+class PointwiseBCELoss:
+    """monoBERT's pointwise objective over tuple scores [positive | explicit negatives]: binary cross-entropy of every
+    score against label 1 in column 0 and 0 elsewhere, summed over a query's 1+k columns and averaged over the queries
+    (ops.sigmoid_xent with unit weights).  Takes (pos [B, 1], neg [B, k] or None) like TupleContrastiveLoss."""
+
+    def __call__(self, pos_scores, neg_scores=None):
+        s = _whole(pos_scores, neg_scores)
+        B, n = s.shape
+        y = torch.zeros((B, n), dtype=torch.float32, device=s.device)
+        y[:, 0] = 1.0
+        self.loss = torch.empty(1, dtype=torch.float32, device=s.device)
+        self.d = torch.empty_like(s)
+        ops.sigmoid_xent(s, y, torch.ones(n, dtype=torch.float32, device=s.device), 1.0, self.loss, self.d)
+        return DeviceScalar(self.loss)
+
+    def backward(self, accumulate=False):
+        return self.d[:, :1], (self.d[:, 1:] if self.d.shape[1] > 1 else None)
+
+
+class CrossEncoderTrainer(BaseTrainer):
+    """Training of a CrossEncoder (polus_amd/ir/models.py) on the batches the other retrieval trainers take:
+    (question, positive_doc[, negative_doc[, teacher_scores]]), each {"input_ids", "attention_mask"}, the negatives
+    [B, k, L].  Nothing is encoded on its own: the positives and negatives go into one [(1+k)B, Ld] id buffer and mask
+    buffer, slot-major (cand[b, j] = j B + b), and ops.pair_pack builds the (1+k)B pair rows `cls q sep d sep` at the
+    fixed S = max_length on the device, with no host synchronisation.  `strip` = (head, tail) tokens taken off every
+    valid query and document row first: (1, 1) removes the [CLS] and [SEP] of HF-tokenised inputs, (0, 0) takes raw ids.
+    A query keeps at most `max_query_tokens`; the document gets the rest of the row.
+
+    The model's scores, reshaped to [B, 1+k], reach the loss as (pos [B, 1], neg [B, k]) (+ teacher_scores), so
+    TupleContrastiveLoss (the default), PointwiseBCELoss, DistillKLLoss and MarginMSELoss work as they are.  Gradient
+    accumulation, the in-backward optimizer update and the data-parallel exchange are BaseTrainer's.  Step-graph
+    replay is not supported."""
+
+    def __init__(self, model, optimizer, loss=None, strip=(1, 1), max_query_tokens=64, max_length=256, cls_token_id=101,
+                 sep_token_id=102, pad_token_id=0, trainable_weights=None, **kwargs):
+        self.strip = (int(strip[0]), int(strip[1]))
+        self.max_query_tokens, self.max_length = int(max_query_tokens), int(max_length)
+        self.special = (int(cls_token_id), int(sep_token_id), int(pad_token_id))
+        if not all(0 <= s <= 8 for s in self.strip):
+            raise ValueError(f"strip counts must be in 0..8, got {strip}")
+        if self.max_query_tokens < 0 or self.max_length < self.max_query_tokens + 3:
+            raise ValueError(f"max_length ({max_length}) must be at least max_query_tokens ({max_query_tokens}) + 3")
+        cfg = model.config
+        if self.max_length > cfg.max_position_embeddings:
+            raise ValueError(f"max_length {max_length} exceeds the model's {cfg.max_position_embeddings} positions")
+        if not all(0 <= t < cfg.vocab_size for t in self.special):
+            raise ValueError(f"special token ids {self.special} must lie in the vocabulary [0, {cfg.vocab_size})")
+        self.trainable_weights = model.trainable_weights if trainable_weights is None else trainable_weights
+        self.scores, self._cand = None, {}
+        super().__init__(model, optimizer, TupleContrastiveLoss() if loss is None else loss, **kwargs)
+
+    def __str__(self):
+        return "CrossEncoderTrainer"
+
+    def enable_step_graph(self, warmup=3):
+        raise NotImplementedError("CrossEncoderTrainer does not support step-graph replay")
+
+    def _documents(self, positive_doc, negative_doc, dev):
+        """ids and mask int32 [(1+k)B, Ld] of the positives, then negative i of every query in block i; k."""
+        pi = to_device(positive_doc["input_ids"], torch.int32, dev)
+        B, Lp = pi.shape
+        pm = positive_doc.get("attention_mask")
+        pm = None if pm is None else to_device(pm, torch.int32, dev)
+        if negative_doc is None:
+            return pi, pm, 0
+        ni = to_device(negative_doc["input_ids"], torch.int32, dev)
+        if ni.dim() != 3 or ni.shape[0] != B:
+            raise ValueError(f"negative documents must be [B, k, L] with B = {B}, got {list(ni.shape)}")
+        k, Ln = ni.shape[1], ni.shape[2]
+        nm = negative_doc.get("attention_mask")
+        nm = None if nm is None else to_device(nm, torch.int32, dev)
+        Ld = max(Lp, Ln)
+        ids = torch.zeros(((1 + k) * B, Ld), dtype=torch.int32, device=dev)
+        mask = torch.zeros(((1 + k) * B, Ld), dtype=torch.int32, device=dev)
+        ids[:B, :Lp].copy_(pi)
+        ids[B:].view(k, B, Ld)[:, :, :Ln].copy_(ni.permute(1, 0, 2))
+        if pm is None:
+            mask[:B, :Lp].fill_(1)
+        else:
+            mask[:B, :Lp].copy_(pm)
+        if nm is None:
+            mask[B:].view(k, B, Ld)[:, :, :Ln].fill_(1)
+        else:
+            mask[B:].view(k, B, Ld)[:, :, :Ln].copy_(nm.permute(1, 0, 2))
+        return ids, mask, k
+
+    def forward_with_grads(self, question, positive_doc, negative_doc=None, teacher_scores=None):
+        dev = self.model.arena.device
+        q_ids = to_device(question["input_ids"], torch.int32, dev)
+        B = q_ids.shape[0]
+        if teacher_scores is not None:                              # checked before anything is launched
+            if negative_doc is None:
+                raise ValueError("teacher_scores need explicit negatives: a one-column tuple has nothing to contrast")
+            teacher_scores = _teacher_scores(teacher_scores, B, negative_doc["input_ids"].shape[1], dev)
+        qm = question.get("attention_mask")
+        qm = None if qm is None else to_device(qm, torch.int32, dev)
+        d_ids, dm, k = self._documents(positive_doc, negative_doc, dev)
+        self._B, self._n_neg = B, k
+        cand = self._cand.get((B, k))
+        if cand is None:                                            # cand[b, j] = j B + b
+            cand = self._cand[(B, k)] = (torch.arange(1 + k, dtype=torch.int32, device=dev)[None, :] * B +
+                                         torch.arange(B, dtype=torch.int32, device=dev)[:, None]).contiguous()
+        P, S = (1 + k) * B, self.max_length
+        rows = torch.empty((3, P, S), dtype=torch.int32, device=dev)
+        ops.pair_pack(q_ids, qm, d_ids, dm, cand, rows[0], rows[1], rows[2], self.strip + self.strip, self.max_query_tokens,
+                      self.special)
+        self.pairs = rows
+        s = self.model(input_ids=rows[0], attention_mask=rows[2], token_type_ids=rows[1], training=True).view(B, 1 + k)
+        self.scores = s
+        out = (s[:, :1], s[:, 1:] if k else None)
+        return out if teacher_scores is None else out + (teacher_scores,)
+
+    def backward_from_loss(self, accumulate=False):
+        dpos, dneg = self.loss.backward(accumulate)
+        ds = _whole(dpos, dneg)
+        self.model.backward(ds.contiguous().reshape(-1), accumulate=accumulate)
 
 
 class SparseRetrievalTrainer(BaseTrainer):

@@ -913,6 +913,96 @@ def margin_mse(student, teacher, loss, dstudent):
     _distill("polus_margin_mse", student, teacher, loss, dstudent)
 
 
+def _pair_rows(rows, B, n, distinct=False):
+    """`rows` (None, a host array or an int32 device tensor [R]) -> (device tensor or None, R).  A host array is checked
+    (values in [0, B n), distinct where the caller needs that) and copied over; a device tensor is taken as it is."""
+    if rows is None:
+        return None, B * n
+    if not (isinstance(rows, torch.Tensor) and rows.is_cuda):
+        import numpy as np
+        h = rows.numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+        if h.ndim != 1 or h.size < 1 or not np.issubdtype(h.dtype, np.integer):
+            raise ValueError(f"rows must be a non-empty 1-d integer array, got {h.dtype} {h.shape}")
+        if h.min() < 0 or h.max() >= B * n:
+            raise ValueError(f"rows holds a pair index outside [0, B n) = [0, {B * n})")
+        if distinct and np.unique(h).size != h.size:
+            raise ValueError("rows repeats a pair index: the scattered scores need distinct rows")
+        rows = torch.as_tensor(np.ascontiguousarray(h.astype(np.int32))).cuda()
+    assert rows.dtype == torch.int32 and rows.dim() == 1 and rows.is_contiguous() and rows.numel() >= 1
+    return rows, rows.numel()
+
+
+def _pair_mask(mask, rows, L, name):
+    if mask is None:
+        return None, 0
+    return ptr(mask), _rows2d(mask, torch.int32, rows, L, name)
+
+
+def _pair_cand(cand):
+    assert cand.dtype == torch.int32 and cand.dim() == 2 and (cand.stride(1) == 1 or cand.shape[1] == 1), "cand: need int32 [B, n]"
+    B, n = cand.shape
+    return B, n, cand.stride(0) if B > 1 else max(cand.stride(0), n)
+
+
+def pair_lengths(q_shape, qmask, d_shape, dmask, cand, length, strips, max_q, S, rows=None):
+    """length[r] (int32 [R]) = the real tokens of the pair row `cls q' sep d' sep` that pair_pack would build for pair
+    rows[r] (None: pair r) of cand (int32 [B, n]): q_shape = (B, Lq) and d_shape = (N, Ld) with their int32 masks (None:
+    all ones), strips = (q_head, q_tail, d_head, d_tail) (include/polus_hip.h polus_pair_lengths)."""
+    _req_cuda(qmask, dmask, cand, length)
+    B, n, ldc = _pair_cand(cand)
+    (Bq, Lq), (N, Ld) = q_shape, d_shape
+    assert Bq == B, f"cand has {B} rows for {Bq} queries"
+    rows, R = _pair_rows(rows, B, n)
+    pq, ldqm = _pair_mask(qmask, B, Lq, "qmask")
+    pd, lddm = _pair_mask(dmask, N, Ld, "dmask")
+    assert length.dtype == torch.int32 and length.is_contiguous() and length.numel() >= R
+    qh, qt, dh, dt = (int(s) for s in strips)
+    check(_lib.load().polus_pair_lengths(pq, ldqm, pd, lddm, ptr(cand), ldc, ptr(rows), R, B, n, int(N), int(Lq), int(Ld),
+                                         qh, qt, dh, dt, int(max_q), int(S), ptr(length), _st()), "polus_pair_lengths")
+
+
+def pair_pack(q_ids, qmask, d_ids, dmask, cand, input_ids, token_type_ids, attention_mask, strips, max_q, special,
+              rows=None, length=None):
+    """The pair rows `cls q' sep d' sep pad..` of pairs rows[r] (None: every pair of cand, in order) into input_ids,
+    token_type_ids and attention_mask (int32 [R, S], one common row stride; S is their width) and, when given, their
+    real lengths into length (int32 [R]).  q_ids int32 [B, Lq], d_ids int32 [N, Ld], the masks int32 or None, cand int32
+    [B, n] (an id outside [0, N) is the empty document), strips = (q_head, q_tail, d_head, d_tail), special = (cls, sep,
+    pad) (include/polus_hip.h polus_pair_pack)."""
+    _req_cuda(q_ids, qmask, d_ids, dmask, cand, input_ids, token_type_ids, attention_mask, length)
+    B, n, ldc = _pair_cand(cand)
+    assert q_ids.dim() == 2 and d_ids.dim() == 2 and q_ids.shape[0] == B, f"cand has {B} rows for {tuple(q_ids.shape)} query ids"
+    (Lq, (N, Ld)) = q_ids.shape[1], d_ids.shape
+    rows, R = _pair_rows(rows, B, n)
+    ldq, ldd = _rows2d(q_ids, torch.int32, B, Lq, "q_ids"), _rows2d(d_ids, torch.int32, N, Ld, "d_ids")
+    pq, ldqm = _pair_mask(qmask, B, Lq, "qmask")
+    pd, lddm = _pair_mask(dmask, N, Ld, "dmask")
+    S = input_ids.shape[1]
+    ldo = _rows2d(input_ids, torch.int32, R, S, "input_ids")
+    for t, name in ((token_type_ids, "token_type_ids"), (attention_mask, "attention_mask")):
+        assert tuple(t.shape) == tuple(input_ids.shape) and _rows2d(t, torch.int32, R, S, name) == ldo, \
+            f"{name}: the three outputs share one shape and row stride"
+    assert input_ids.shape[0] == R, f"the outputs have {input_ids.shape[0]} rows for {R} pairs"
+    assert length is None or (length.dtype == torch.int32 and length.is_contiguous() and length.numel() >= R)
+    qh, qt, dh, dt = (int(s) for s in strips)
+    cls, sep, pad = (int(s) for s in special)
+    check(_lib.load().polus_pair_pack(ptr(q_ids), ldq, pq, ldqm, ptr(d_ids), ldd, pd, lddm, ptr(cand), ldc, ptr(rows), R, B, n,
+                                      N, Lq, Ld, qh, qt, dh, dt, int(max_q), S, cls, sep, pad, ptr(input_ids),
+                                      ptr(token_type_ids), ptr(attention_mask), ldo, ptr(length), _st()), "polus_pair_pack")
+
+
+def pair_scatter_scores(s, cand, N, out, rows=None):
+    """out[b, j] = s[r] for pair rows[r] = b n + j (None: pair r) whose candidate cand[b, j] lies in [0, N), -inf for one
+    that does not; s f32 [R], out f32 [B, n] (any row stride), entries that `rows` does not name left alone; `rows` must
+    be distinct (include/polus_hip.h polus_pair_scatter_scores)."""
+    _req_cuda(s, cand, out)
+    B, n, ldc = _pair_cand(cand)
+    rows, R = _pair_rows(rows, B, n, distinct=True)
+    assert s.dtype == torch.float32 and s.is_contiguous() and s.numel() >= R
+    ldo = _rows2d(out, torch.float32, B, n, "out")
+    check(_lib.load().polus_pair_scatter_scores(ptr(s), ptr(rows), ptr(cand), ldc, R, B, n, int(N), ptr(out), ldo, _st()),
+          "polus_pair_scatter_scores")
+
+
 def argmax(x, out, rows=None, C=None):
     lib = _lib.load()
     _req_cuda(x, out)
