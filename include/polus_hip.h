@@ -710,6 +710,77 @@ int polus_flops_reg(const float* rep, long ldr, int rows, int V, float lambda, f
 int polus_sparse_scores(const float* q, long ldq, const int32_t* ids, long ldi, const float* w, long ldw,
                         float* score, long lds, int B, int N, int M, int V, void* stream);
 
+/* ---- lexical retrieval, BM25 over token ids (bm25.hip; no counterpart in the reference, which has no lexical stage).
+ * A document is the bag of its token ids; the index keeps per document M (term, count) pairs, the document length and
+ * the corpus statistics, and derives f32 weights from them, so that polus_sparse_scores over (q, terms, w) is the BM25
+ * score.  Integers only in polus_bm25_term_counts: every result is exact.
+ *
+ * polus_bm25_term_counts:
+ *   ids int32 [n, L] (row stride ldi);  mask int32 [n, L] (row stride ldm) or NULL = every token valid
+ *   terms, tf int32 [n, M] (row strides ldt, ldf);  doc_len int32 [n]
+ *   df int32 [V] or NULL, ACCUMULATED;  stats int64 [3] or NULL, ACCUMULATED (zero both to start)
+ *   Valid tokens.  The valid tokens of a row are those whose mask is non-zero, in order.
+ *   Stripping.  A row with at most head + tail valid tokens is empty; otherwise its first `head` and last `tail` valid
+ *     tokens are dropped (polus_pair_pack's rule: 1/1 takes the [CLS] and [SEP] off HF-tokenised rows).
+ *   Rejection.  A remaining token whose id lies outside [0, V) is dropped and adds 1 to stats[1].
+ *   doc_len[r] = the number of tokens that remain; it is also added to stats[2].
+ *   Terms.  Let u be the number of distinct remaining ids, ordered by (count descending, id ascending).  Slot s <
+ *     min(u, M) holds the s-th of them: terms[r, s] = the id, tf[r, s] = its count.  Every further slot s < M is written
+ *     as (-1, 0).  u > M adds 1 to stats[0] (a truncated document).  Nothing beyond column M - 1 is written.
+ *   df[t] += 1 for every distinct remaining id t of the row, kept in a slot or not (int32 atomics); with df == NULL
+ *     (queries) that step is skipped.
+ *   One workgroup per document (grid-stride): ids into LDS as 64-bit keys, bitonic sort, run heads by neighbour
+ *   compares, run lengths by a binary search, a second sort of (count, id) keys; 16 KiB of LDS for every V.  stats
+ *   receives three int64 atomic adds per workgroup.  Sums of integers are exact in any order: bitwise reproducible.  No
+ *   float atomics, no workspace.
+ *   Limits (refused before any launch): 1 <= L <= 2048; 1 <= M <= 1024; n >= 1; V >= 1; 0 <= head, tail <= 8; ldi >= L;
+ *     ldm >= L with a mask; ldt, ldf >= M; ids, terms, tf, doc_len non-null.
+ *
+ * polus_bm25_weights:  w f32 [n, M] (row stride ldw) from tf int32 [n, M] (row stride ldf), doc_len int32 [n] and three
+ *   f32 constants (BM25Index.refresh: c0 = k1 (1 - b), c1 = k1 b / avgdl, k1p1 = k1 + 1):
+ *     K_r     = fl(fl(c1 * f32(doc_len[r])) + c0)
+ *     w[r, m] = tf[r, m] > 0 ? fl(fl(f32(tf[r, m]) * k1p1) / fl(f32(tf[r, m]) + K_r)) : +0.0f
+ *   Every fl is one IEEE f32 rounding to nearest even, the division is correctly rounded and nothing is contracted into
+ *   an fma: NumPy float32 arithmetic gives the same bits.  Nothing beyond column M - 1 is written.  One wave per row.
+ *   Limits (refused before any launch): n >= 1; 1 <= M <= 1024; ldf, ldw >= M; non-null pointers.
+ *
+ * polus_bm25_query:  the dense query rows polus_sparse_scores reads.  q f32 [B, V] (row stride ldq), EVERY element of
+ *   the V columns written; terms, tf int32 [B, M] (row strides ldt, ldf) as polus_bm25_term_counts leaves them; idf f32 [V]:
+ *     q[b, terms[b, m]] = fl(f32(tf[b, m]) * idf[terms[b, m]])  for the slots with 0 <= terms[b, m] < V;  0.0 elsewhere.
+ *   The terms of a row must be distinct (plain stores; of a repeated term one slot's value remains).  One workgroup per
+ *   row: fill, barrier, scatter.
+ *   Limits (refused before any launch): B >= 1; 1 <= M <= 1024; V >= 1 and V * 4 <= 163840 (polus_sparse_scores' limit
+ *     on the row); ldt, ldf >= M; ldq >= V; non-null pointers. */
+int polus_bm25_term_counts(const int32_t* ids, long ldi, const int32_t* mask, long ldm, int n, int L, int V, int head,
+                           int tail, int32_t* terms, long ldt, int32_t* tf, long ldf, int M, int32_t* doc_len,
+                           int32_t* df, int64_t* stats, void* stream);
+int polus_bm25_weights(const int32_t* tf, long ldf, const int32_t* doc_len, float* w, long ldw, int n, int M, float c0,
+                       float c1, float k1p1, void* stream);
+int polus_bm25_query(const int32_t* terms, long ldt, const int32_t* tf, long ldf, const float* idf, float* q, long ldq,
+                     int B, int M, int V, void* stream);
+
+/* ---- hard-negative mining (mine.hip): k negatives per query sampled from a ranked candidate list, the step between a
+ * first-stage search and the (question, positive, negatives) tuples of the trainers.  Integers only: exact.
+ *   cand int32 [Q, C] (row stride ldc), in rank order, ids distinct within a row (as a search returns them)
+ *   score f32 [Q, C] (row stride lds) or NULL;  exclude int32 [Q, P] (row stride lde), NULL allowed when P == 0
+ *   neg int32 [Q, k] contiguous;  neg_col int32 [Q, k] contiguous or NULL;  n_pool int32 [Q]
+ * Pool.  The pool of row r is the columns c >= skip_top, in column order, with cand[r, c] >= 0, cand[r, c] not equal to
+ *   any non-negative entry of exclude[r, :], and, when score is given, score[r, c] > min_score (a NaN fails;
+ *   min_score = 0 removes the documents that share no term with a BM25 query).  R = the pool's size; n_pool[r] = R.
+ * R <= k.  neg[r, j] = the id of pool position j for j < R and -1 for R <= j < k.
+ * R > k.   With lo_j = floor(j R / k) and hi_j = floor((j + 1) R / k) in 64-bit integers, neg[r, j] = the id at pool
+ *   position lo_j + polus_hash32(seed, r k + j) mod (hi_j - lo_j), where polus_hash32(seed, idx) is the murmur3
+ *   finaliser of idx * 0x9E3779B1 + seed (uint32 arithmetic; the dropout mask's hash) and r k + j is taken mod 2^32.
+ *   One draw per rank stratum: the negatives come out in rank order, are distinct and span the whole depth.
+ * neg_col[r, j] = the column neg[r, j] came from, -1 where neg is -1.
+ * One wave per query, two sweeps over the columns in 64-column steps (count, then place by __ballot and popcount);
+ * plain stores to distinct addresses, no LDS, no atomics, no workspace, bitwise reproducible.
+ * Limits (refused before any launch): Q, C >= 1; 1 <= k <= 1024; 0 <= P <= 1024; skip_top >= 0; Q k < 2^32; ldc >= C;
+ *   lds >= C with scores; lde >= P and exclude non-null when P > 0; cand, neg, n_pool non-null. */
+int polus_mine_negatives(const int32_t* cand, long ldc, const float* score, long lds, const int32_t* exclude, long lde,
+                         int Q, int C, int P, int skip_top, float min_score, int k, uint32_t seed, int32_t* neg,
+                         int32_t* neg_col, int32_t* n_pool, void* stream);
+
 /* ---- argmax over the last axis (PolusClassifier.inference, polus/models.py:148-150) */
 int polus_argmax(const float* x, long ldx, int32_t* out, int rows, int C, void* stream);
 

@@ -1,0 +1,4 @@
+"""polus.ir.lexical -> polus_amd.ir.lexical (re-export; no counterpart module in the reference, which has no lexical stage)."""
+from polus_amd.ir import lexical as _impl
+
+globals().update({k: v for k, v in vars(_impl).items() if not k.startswith("__")})

@@ -775,6 +775,78 @@ def sparse_scores(q, ids, w, score):
     return score
 
 
+def bm25_term_counts(ids, mask, terms, tf, doc_len, V, strip=(0, 0), df=None, stats=None):
+    """Per row of ids (int32 [n, L], any row stride; mask int32 [n, L] or None) the distinct token ids that remain after
+    the strip (head, tail) and their counts, ordered by (count descending, id ascending), into terms / tf (int32 [n, M],
+    any row stride, unused slots (-1, 0)) and the number of remaining tokens into doc_len (int32 [n]).  df (int32 [V])
+    and stats (int64 [3]: truncated documents, rejected tokens, tokens) are accumulated into when given
+    (include/polus_hip.h polus_bm25_term_counts)."""
+    _req_cuda(ids, mask, terms, tf, doc_len, df, stats)
+    assert ids.dim() == 2 and terms.dim() == 2, "ids: need int32 [n, L]; terms: need int32 [n, M]"
+    (n, L), M = ids.shape, terms.shape[1]
+    ldi = _rows2d(ids, torch.int32, n, L, "ids")
+    pm, ldm = _pair_mask(mask, n, L, "mask")
+    ldt, ldf = _rows2d(terms, torch.int32, n, M, "terms"), _rows2d(tf, torch.int32, n, M, "tf")
+    assert tf.shape[1] == M, f"terms has {M} slots, tf {tf.shape[1]}"
+    assert doc_len.dtype == torch.int32 and doc_len.is_contiguous() and doc_len.numel() >= n
+    assert df is None or (df.dtype == torch.int32 and df.is_contiguous() and df.numel() >= int(V))
+    assert stats is None or (stats.dtype == torch.int64 and stats.is_contiguous() and stats.numel() >= 3)
+    check(_lib.load().polus_bm25_term_counts(ptr(ids), ldi, pm, ldm, n, L, int(V), int(strip[0]), int(strip[1]), ptr(terms),
+                                             ldt, ptr(tf), ldf, M, ptr(doc_len), ptr(df), ptr(stats), _st()),
+          "polus_bm25_term_counts")
+
+
+def bm25_weights(tf, doc_len, w, c0, c1, k1p1):
+    """w[r, m] (f32 [n, M], any row stride) = tf (k1 + 1) / (tf + c1 doc_len[r] + c0) where tf[r, m] > 0, else 0; every
+    operation rounded once to f32 (include/polus_hip.h polus_bm25_weights)."""
+    _req_cuda(tf, doc_len, w)
+    n, M = tf.shape
+    ldf, ldw = _rows2d(tf, torch.int32, n, M, "tf"), _rows2d(w, torch.float32, n, M, "w")
+    assert w.shape[1] == M, f"tf has {M} slots, w {w.shape[1]}"
+    assert doc_len.dtype == torch.int32 and doc_len.is_contiguous() and doc_len.numel() >= n
+    check(_lib.load().polus_bm25_weights(ptr(tf), ldf, ptr(doc_len), ptr(w), ldw, n, M, float(c0), float(c1), float(k1p1),
+                                         _st()), "polus_bm25_weights")
+    return w
+
+
+def bm25_query(terms, tf, idf, q):
+    """q (f32 [B, V], any row stride, every element written) = tf[b, m] * idf[terms[b, m]] at column terms[b, m] for
+    the used slots of terms / tf (int32 [B, M]), 0 elsewhere; idf f32 [V] (include/polus_hip.h polus_bm25_query)."""
+    _req_cuda(terms, tf, idf, q)
+    B, M = terms.shape
+    V = q.shape[1]
+    ldt, ldf = _rows2d(terms, torch.int32, B, M, "terms"), _rows2d(tf, torch.int32, B, M, "tf")
+    ldq = _rows2d(q, torch.float32, B, V, "q")
+    assert tf.shape[1] == M and q.shape[0] == B
+    assert idf.dtype == torch.float32 and idf.is_contiguous() and idf.numel() >= V
+    check(_lib.load().polus_bm25_query(ptr(terms), ldt, ptr(tf), ldf, ptr(idf), ptr(q), ldq, B, M, V, _st()), "polus_bm25_query")
+    return q
+
+
+def mine_negatives(cand, neg, n_pool, score=None, exclude=None, skip_top=0, min_score=0.0, seed=0, neg_col=None):
+    """k = neg.shape[1] negatives per row of cand (int32 [Q, C] in rank order, any row stride) into neg (int32 [Q, k]),
+    their columns into neg_col (int32 [Q, k] or None) and the pool size into n_pool (int32 [Q]).  The pool of a row:
+    columns >= skip_top with a non-negative id that is not in exclude (int32 [Q, P] or None) and, with score (f32
+    [Q, C]), a score above min_score.  A pool of at most k goes out whole, padded with -1; a larger one gives one seeded
+    draw per rank stratum (include/polus_hip.h polus_mine_negatives)."""
+    _req_cuda(cand, neg, n_pool, score, exclude, neg_col)
+    Q, C, ldc = _pair_cand(cand)
+    assert neg.dim() == 2 and neg.dtype == torch.int32 and neg.is_contiguous() and neg.shape[0] == Q, "neg: need contiguous int32 [Q, k]"
+    k = neg.shape[1]
+    assert neg_col is None or (neg_col.dtype == torch.int32 and neg_col.is_contiguous() and tuple(neg_col.shape) == (Q, k))
+    assert n_pool.dtype == torch.int32 and n_pool.is_contiguous() and n_pool.numel() >= Q
+    lds = 0 if score is None else _rows2d(score, torch.float32, Q, C, "score")
+    assert score is None or score.shape[1] == C
+    P, lde = 0, 0
+    if exclude is not None and exclude.shape[1] > 0:
+        P = exclude.shape[1]
+        lde = _rows2d(exclude, torch.int32, Q, P, "exclude")
+        assert exclude.shape[0] == Q
+    check(_lib.load().polus_mine_negatives(ptr(cand), ldc, ptr(score), lds, ptr(exclude) if P else None, lde, Q, C, P,
+                                           int(skip_top), float(min_score), k, int(seed) & 0xFFFFFFFF, ptr(neg), ptr(neg_col),
+                                           ptr(n_pool), _st()), "polus_mine_negatives")
+
+
 def maxsim_bwd(q, d, dscore, argmax, dq, dd):
     """dq [B, Lq, E] and dd [N, Ld, E] from dscore (f32 [B, N], row stride free) and the forward's argmax; every
     element is written."""
