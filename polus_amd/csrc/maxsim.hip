@@ -17,8 +17,6 @@
 
 namespace {
 
-constexpr int MS_NOJ = 0x7fffffff;      // "no valid j yet" while reducing
-
 __device__ __forceinline__ void ms_pick(float& m, int& j, float m2, int j2) {
     if (m2 > m || (m2 == m && j2 < j)) { m = m2; j = j2; }
 }
@@ -335,12 +333,8 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const T* __restrict__ y
 }
 
 int ms_check(const char* what, int dtype, int B, int N, int Lq, int Ld, int E, long lds, bool with_argmax = true) {
-    POLUS_REQUIRE(dtype == POLUS_F32 || dtype == POLUS_BF16, "%s: unknown dtype %d", what, dtype);
-    POLUS_REQUIRE(E >= 32 && E <= MS_EMAX && E % 32 == 0, "%s: E must be a multiple of 32 in [32, %d] (got %d)", what,
-                  MS_EMAX, E);
-    POLUS_REQUIRE(Lq >= 1 && Lq <= MS_LMAX, "%s: need 1 <= Lq <= %d (got %d)", what, MS_LMAX, Lq);
-    POLUS_REQUIRE(Ld >= 1 && Ld <= MS_LMAX, "%s: need 1 <= Ld <= %d (got %d)", what, MS_LMAX, Ld);
-    POLUS_REQUIRE(B >= 1 && B <= 65535, "%s: need 1 <= B <= 65535 (got %d)", what, B);
+    int rc = ms_shape_check(what, dtype, B, Lq, Ld, E);
+    if (rc != POLUS_OK) return rc;
     POLUS_REQUIRE(N >= 1 && N <= 65535, "%s: need 1 <= N <= 65535 (got %d)", what, N);
     POLUS_REQUIRE(!with_argmax || (long long)B * N * Lq < (1LL << 31), "%s: B*N*Lq must be < 2^31 (got %lld)", what,
                   (long long)B * N * Lq);
@@ -348,37 +342,21 @@ int ms_check(const char* what, int dtype, int B, int N, int Lq, int Ld, int E, l
     return POLUS_OK;
 }
 
-template <typename T, int KS>
-void fwd_launch(const void* Q, const void* D, const int32_t* qm, const int32_t* dm, float* score, long lds,
-                int32_t* am, int B, int N, int Lq, int Ld, hipStream_t st) {
-    // queries per workgroup: one round of 4 x UT query tiles where the queries are short (at most 16 queries),
-    // halved while that leaves fewer than 512 workgroups
-    const int nut = (Lq + 15) / 16;
-    const int per = 4 * MsTiles<T, KS>::UT;
-    int qpb = nut >= per ? 1 : min(16, per / nut);
-    while (qpb > 1 && (long)N * ((B + qpb - 1) / qpb) < 512) qpb >>= 1;
-    dim3 grid(N, (B + qpb - 1) / qpb);
-    if (am)
-        hipLaunchKernelGGL((maxsim_fwd_kernel<T, KS>), grid, dim3(256), 0, st, static_cast<const T*>(Q),
-                           static_cast<const T*>(D), qm, dm, score, lds, am, B, N, Lq, Ld, qpb);
-    else                                              // polus_maxsim_scores (polus_maxsim_fwd refuses a null argmax)
-        hipLaunchKernelGGL((maxsim_scores_kernel<T, KS>), grid, dim3(256), 0, st, static_cast<const T*>(Q),
-                           static_cast<const T*>(D), qm, dm, score, lds, B, N, Lq, Ld, qpb);
-}
-
-template <typename T>
-void fwd_dispatch(int E, const void* Q, const void* D, const int32_t* qm, const int32_t* dm, float* score, long lds,
-                  int32_t* am, int B, int N, int Lq, int Ld, hipStream_t st) {
-    switch (E / 32) {
-    case 1: fwd_launch<T, 1>(Q, D, qm, dm, score, lds, am, B, N, Lq, Ld, st); break;
-    case 2: fwd_launch<T, 2>(Q, D, qm, dm, score, lds, am, B, N, Lq, Ld, st); break;
-    case 3: fwd_launch<T, 3>(Q, D, qm, dm, score, lds, am, B, N, Lq, Ld, st); break;
-    case 4: fwd_launch<T, 4>(Q, D, qm, dm, score, lds, am, B, N, Lq, Ld, st); break;
-    case 5: fwd_launch<T, 5>(Q, D, qm, dm, score, lds, am, B, N, Lq, Ld, st); break;
-    case 6: fwd_launch<T, 6>(Q, D, qm, dm, score, lds, am, B, N, Lq, Ld, st); break;
-    case 7: fwd_launch<T, 7>(Q, D, qm, dm, score, lds, am, B, N, Lq, Ld, st); break;
-    default: fwd_launch<T, 8>(Q, D, qm, dm, score, lds, am, B, N, Lq, Ld, st); break;
-    }
+// am == nullptr: polus_maxsim_scores (polus_maxsim_fwd refuses a null argmax)
+void fwd_dispatch(int dtype, int E, const void* Q, const void* D, const int32_t* qm, const int32_t* dm, float* score,
+                  long lds, int32_t* am, int B, int N, int Lq, int Ld, hipStream_t st) {
+    ms_dispatch(dtype, E, [&](auto t, auto ks) {
+        using T = typename decltype(t)::type;
+        constexpr int KS = decltype(ks)::value;
+        const int qpb = ms_queries_per_block<T, KS>(B, N, Lq);
+        dim3 grid(N, (B + qpb - 1) / qpb);
+        if (am)
+            hipLaunchKernelGGL((maxsim_fwd_kernel<T, KS>), grid, dim3(256), 0, st, static_cast<const T*>(Q),
+                               static_cast<const T*>(D), qm, dm, score, lds, am, B, N, Lq, Ld, qpb);
+        else
+            hipLaunchKernelGGL((maxsim_scores_kernel<T, KS>), grid, dim3(256), 0, st, static_cast<const T*>(Q),
+                               static_cast<const T*>(D), qm, dm, score, lds, B, N, Lq, Ld, qpb);
+    });
 }
 
 template <typename T>
@@ -401,11 +379,7 @@ extern "C" int polus_maxsim_fwd(int dtype, const void* Q, const void* D, const i
     if (rc != POLUS_OK) return rc;
     POLUS_REQUIRE(Q && D && score && argmax, "polus_maxsim_fwd: null pointer");
     POLUS_REQUIRE(polus_aligned16(Q) && polus_aligned16(D), "polus_maxsim_fwd: Q and D must be 16-byte aligned");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == POLUS_BF16)
-        fwd_dispatch<bf16_t>(E, Q, D, qmask, dmask, score, lds, argmax, B, N, Lq, Ld, st);
-    else
-        fwd_dispatch<float>(E, Q, D, qmask, dmask, score, lds, argmax, B, N, Lq, Ld, st);
+    fwd_dispatch(dtype, E, Q, D, qmask, dmask, score, lds, argmax, B, N, Lq, Ld, static_cast<hipStream_t>(stream));
     POLUS_CHECK_LAUNCH("polus_maxsim_fwd");
     return POLUS_OK;
 }
@@ -416,11 +390,7 @@ extern "C" int polus_maxsim_scores(int dtype, const void* Q, const void* D, cons
     if (rc != POLUS_OK) return rc;
     POLUS_REQUIRE(Q && D && score, "polus_maxsim_scores: null pointer");
     POLUS_REQUIRE(polus_aligned16(Q) && polus_aligned16(D), "polus_maxsim_scores: Q and D must be 16-byte aligned");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == POLUS_BF16)
-        fwd_dispatch<bf16_t>(E, Q, D, qmask, dmask, score, lds, nullptr, B, N, Lq, Ld, st);
-    else
-        fwd_dispatch<float>(E, Q, D, qmask, dmask, score, lds, nullptr, B, N, Lq, Ld, st);
+    fwd_dispatch(dtype, E, Q, D, qmask, dmask, score, lds, nullptr, B, N, Lq, Ld, static_cast<hipStream_t>(stream));
     POLUS_CHECK_LAUNCH("polus_maxsim_scores");
     return POLUS_OK;
 }

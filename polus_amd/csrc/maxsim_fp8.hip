@@ -363,67 +363,11 @@ int f8_rows_check(const char* what, int dtype, const void* a, const void* b, con
 
 int f8_check(const char* what, int dtype, int B, int Lq, int Ld, int E, const void* Q, const void* codes,
              const void* scale, const void* score) {
-    POLUS_REQUIRE(dtype == POLUS_F32 || dtype == POLUS_BF16, "%s: unknown dtype %d", what, dtype);
-    POLUS_REQUIRE(E >= 32 && E <= MS_EMAX && E % 32 == 0, "%s: E must be a multiple of 32 in [32, %d] (got %d)", what,
-                  MS_EMAX, E);
-    POLUS_REQUIRE(Lq >= 1 && Lq <= MS_LMAX, "%s: need 1 <= Lq <= %d (got %d)", what, MS_LMAX, Lq);
-    POLUS_REQUIRE(Ld >= 1 && Ld <= MS_LMAX, "%s: need 1 <= Ld <= %d (got %d)", what, MS_LMAX, Ld);
-    POLUS_REQUIRE(B >= 1 && B <= 65535, "%s: need 1 <= B <= 65535 (got %d)", what, B);
+    int rc = ms_shape_check(what, dtype, B, Lq, Ld, E);
+    if (rc != POLUS_OK) return rc;
     POLUS_REQUIRE(Q && codes && scale && score, "%s: null pointer", what);
     POLUS_REQUIRE(polus_aligned16(Q) && polus_aligned16(codes), "%s: Q and codes must be 16-byte aligned", what);
     return POLUS_OK;
-}
-
-template <typename T, int KS>
-void f8_scores_launch(const void* Q, const unsigned char* codes, const float* scale, const int32_t* qm,
-                      const int32_t* dm, float* score, long lds, int B, int N, int Lq, int Ld, hipStream_t st) {
-    // queries per workgroup: the rule of maxsim.hip fwd_launch
-    const int nut = (Lq + 15) / 16;
-    const int per = 4 * MsTiles<T, KS>::UT;
-    int qpb = nut >= per ? 1 : min(16, per / nut);
-    while (qpb > 1 && (long)N * ((B + qpb - 1) / qpb) < 512) qpb >>= 1;
-    dim3 grid(N, (B + qpb - 1) / qpb);
-    hipLaunchKernelGGL((maxsim_scores_fp8_kernel<T, KS>), grid, dim3(256), 0, st, static_cast<const T*>(Q), codes,
-                       scale, qm, dm, score, lds, B, N, Lq, Ld, qpb);
-}
-
-template <typename T, int KS>
-void f8_rerank_launch(const void* Q, const unsigned char* codes, const float* scale, const int32_t* qm,
-                      const int32_t* dm, const int32_t* cand, long ldc, float* score, long lds, int B, int C, int N,
-                      int Lq, int Ld, hipStream_t st) {
-    const int dpw = rr_docs_per_wave(B, C);
-    dim3 grid((unsigned)((C + 4 * dpw - 1) / (4 * dpw)), (unsigned)B);
-    if ((Lq + 15) / 16 <= MsTiles<T, KS>::UT)
-        hipLaunchKernelGGL((maxsim_rerank_fp8_kernel<T, KS, true>), grid, dim3(256), 0, st, static_cast<const T*>(Q),
-                           codes, scale, qm, dm, cand, ldc, score, lds, C, N, Lq, Ld, dpw);
-    else
-        hipLaunchKernelGGL((maxsim_rerank_fp8_kernel<T, KS, false>), grid, dim3(256), 0, st, static_cast<const T*>(Q),
-                           codes, scale, qm, dm, cand, ldc, score, lds, C, N, Lq, Ld, dpw);
-}
-
-#define F8_BY_KS(LAUNCH, ...)                                  \
-    switch (E / 32) {                                          \
-    case 1: LAUNCH<T, 1>(__VA_ARGS__); break;                  \
-    case 2: LAUNCH<T, 2>(__VA_ARGS__); break;                  \
-    case 3: LAUNCH<T, 3>(__VA_ARGS__); break;                  \
-    case 4: LAUNCH<T, 4>(__VA_ARGS__); break;                  \
-    case 5: LAUNCH<T, 5>(__VA_ARGS__); break;                  \
-    case 6: LAUNCH<T, 6>(__VA_ARGS__); break;                  \
-    case 7: LAUNCH<T, 7>(__VA_ARGS__); break;                  \
-    default: LAUNCH<T, 8>(__VA_ARGS__); break;                 \
-    }
-
-template <typename T>
-void f8_scores_dispatch(int E, const void* Q, const unsigned char* codes, const float* scale, const int32_t* qm,
-                        const int32_t* dm, float* score, long lds, int B, int N, int Lq, int Ld, hipStream_t st) {
-    F8_BY_KS(f8_scores_launch, Q, codes, scale, qm, dm, score, lds, B, N, Lq, Ld, st)
-}
-
-template <typename T>
-void f8_rerank_dispatch(int E, const void* Q, const unsigned char* codes, const float* scale, const int32_t* qm,
-                        const int32_t* dm, const int32_t* cand, long ldc, float* score, long lds, int B, int C, int N,
-                        int Lq, int Ld, hipStream_t st) {
-    F8_BY_KS(f8_rerank_launch, Q, codes, scale, qm, dm, cand, ldc, score, lds, B, C, N, Lq, Ld, st)
 }
 
 }  // namespace
@@ -472,11 +416,14 @@ extern "C" int polus_maxsim_scores_fp8(int dtype, const void* Q, const uint8_t* 
     if (rc != POLUS_OK) return rc;
     POLUS_REQUIRE(N >= 1 && N <= 65535, "%s: need 1 <= N <= 65535 (got %d)", what, N);
     POLUS_REQUIRE(lds >= N, "%s: score row stride lds must be >= N (got %ld < %d)", what, lds, N);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == POLUS_BF16)
-        f8_scores_dispatch<bf16_t>(E, Q, codes, scale, qmask, dmask, score, lds, B, N, Lq, Ld, st);
-    else
-        f8_scores_dispatch<float>(E, Q, codes, scale, qmask, dmask, score, lds, B, N, Lq, Ld, st);
+    ms_dispatch(dtype, E, [&](auto t, auto ks) {
+        using T = typename decltype(t)::type;
+        constexpr int KS = decltype(ks)::value;
+        const int qpb = ms_queries_per_block<T, KS>(B, N, Lq);
+        hipLaunchKernelGGL((maxsim_scores_fp8_kernel<T, KS>), dim3(N, (B + qpb - 1) / qpb), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), static_cast<const T*>(Q), codes, scale, qmask, dmask,
+                           score, lds, B, N, Lq, Ld, qpb);
+    });
     POLUS_CHECK_LAUNCH(what);
     return POLUS_OK;
 }
@@ -487,17 +434,16 @@ extern "C" int polus_maxsim_rerank_fp8(int dtype, const void* Q, const uint8_t* 
                                        void* stream) {
     const char* what = "polus_maxsim_rerank_fp8";
     int rc = f8_check(what, dtype, B, Lq, Ld, E, Q, codes, scale, score);
+    if (rc == POLUS_OK) rc = rr_args_check(what, C, N, ldc, lds);
     if (rc != POLUS_OK) return rc;
-    POLUS_REQUIRE(C >= 1 && C <= 65535, "%s: need 1 <= C <= 65535 (got %d)", what, C);
-    POLUS_REQUIRE(N >= 1, "%s: need 1 <= N <= 2^31 - 1 (got %d)", what, N);
-    POLUS_REQUIRE(ldc >= C, "%s: candidate row stride ldc must be >= C (got %ld < %d)", what, ldc, C);
-    POLUS_REQUIRE(lds >= C, "%s: score row stride lds must be >= C (got %ld < %d)", what, lds, C);
     POLUS_REQUIRE(cand, "%s: null pointer", what);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == POLUS_BF16)
-        f8_rerank_dispatch<bf16_t>(E, Q, codes, scale, qmask, dmask, cand, ldc, score, lds, B, C, N, Lq, Ld, st);
-    else
-        f8_rerank_dispatch<float>(E, Q, codes, scale, qmask, dmask, cand, ldc, score, lds, B, C, N, Lq, Ld, st);
+    ms_dispatch(dtype, E, [&](auto t, auto ks) {
+        using T = typename decltype(t)::type;
+        constexpr int KS = decltype(ks)::value;
+        rr_launch<T, KS>(maxsim_rerank_fp8_kernel<T, KS, true>, maxsim_rerank_fp8_kernel<T, KS, false>, B, C, Lq,
+                         static_cast<hipStream_t>(stream), static_cast<const T*>(Q), codes, scale, qmask, dmask, cand,
+                         ldc, score, lds, C, N, Lq, Ld);
+    });
     POLUS_CHECK_LAUNCH(what);
     return POLUS_OK;
 }

@@ -21,15 +21,6 @@
 
 namespace {
 
-// A fragments of document tile t: lane (i, g) takes row 16 t + i (rows past Ld re-read row Ld - 1), k = 8 g .. 8 g + 7
-// of every 32-wide k-step.  `base` is the document's first row plus this lane's 8 g elements.
-template <typename T, int KS>
-__device__ __forceinline__ void rr_tile_load(Frag<T> (&f)[KS], const unsigned char* base, int t, int i, int Ld) {
-    const unsigned char* p = base + (size_t)min(16 * t + i, Ld - 1) * (32 * KS * sizeof(T));
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) frag_load_row(f[ks], p + ks * 32 * sizeof(T));
-}
-
 template <typename T, int KS, bool RES>
 __global__ __launch_bounds__(256) void maxsim_rerank_kernel(const T* __restrict__ Q, const T* __restrict__ D,
                                                             const int32_t* __restrict__ qmask,
@@ -129,57 +120,24 @@ __global__ __launch_bounds__(256) void maxsim_rerank_kernel(const T* __restrict_
     }
 }
 
-template <typename T, int KS>
-void rr_launch(const void* Q, const void* D, const int32_t* qm, const int32_t* dm, const int32_t* cand, long ldc,
-               float* score, long lds, int B, int C, int N, int Lq, int Ld, hipStream_t st) {
-    const int dpw = rr_docs_per_wave(B, C);
-    dim3 grid((unsigned)((C + 4 * dpw - 1) / (4 * dpw)), (unsigned)B);
-    if ((Lq + 15) / 16 <= MsTiles<T, KS>::UT)
-        hipLaunchKernelGGL((maxsim_rerank_kernel<T, KS, true>), grid, dim3(256), 0, st, static_cast<const T*>(Q),
-                           static_cast<const T*>(D), qm, dm, cand, ldc, score, lds, C, N, Lq, Ld, dpw);
-    else
-        hipLaunchKernelGGL((maxsim_rerank_kernel<T, KS, false>), grid, dim3(256), 0, st, static_cast<const T*>(Q),
-                           static_cast<const T*>(D), qm, dm, cand, ldc, score, lds, C, N, Lq, Ld, dpw);
-}
-
-template <typename T>
-void rr_dispatch(int E, const void* Q, const void* D, const int32_t* qm, const int32_t* dm, const int32_t* cand,
-                 long ldc, float* score, long lds, int B, int C, int N, int Lq, int Ld, hipStream_t st) {
-    switch (E / 32) {
-    case 1: rr_launch<T, 1>(Q, D, qm, dm, cand, ldc, score, lds, B, C, N, Lq, Ld, st); break;
-    case 2: rr_launch<T, 2>(Q, D, qm, dm, cand, ldc, score, lds, B, C, N, Lq, Ld, st); break;
-    case 3: rr_launch<T, 3>(Q, D, qm, dm, cand, ldc, score, lds, B, C, N, Lq, Ld, st); break;
-    case 4: rr_launch<T, 4>(Q, D, qm, dm, cand, ldc, score, lds, B, C, N, Lq, Ld, st); break;
-    case 5: rr_launch<T, 5>(Q, D, qm, dm, cand, ldc, score, lds, B, C, N, Lq, Ld, st); break;
-    case 6: rr_launch<T, 6>(Q, D, qm, dm, cand, ldc, score, lds, B, C, N, Lq, Ld, st); break;
-    case 7: rr_launch<T, 7>(Q, D, qm, dm, cand, ldc, score, lds, B, C, N, Lq, Ld, st); break;
-    default: rr_launch<T, 8>(Q, D, qm, dm, cand, ldc, score, lds, B, C, N, Lq, Ld, st); break;
-    }
-}
-
 }  // namespace
 
 extern "C" int polus_maxsim_rerank(int dtype, const void* Q, const void* D, const int32_t* qmask, const int32_t* dmask,
                                    const int32_t* cand, long ldc, float* score, long lds, int B, int C, int N, int Lq,
                                    int Ld, int E, void* stream) {
     const char* what = "polus_maxsim_rerank";
-    POLUS_REQUIRE(dtype == POLUS_F32 || dtype == POLUS_BF16, "%s: unknown dtype %d", what, dtype);
-    POLUS_REQUIRE(E >= 32 && E <= MS_EMAX && E % 32 == 0, "%s: E must be a multiple of 32 in [32, %d] (got %d)", what,
-                  MS_EMAX, E);
-    POLUS_REQUIRE(Lq >= 1 && Lq <= MS_LMAX, "%s: need 1 <= Lq <= %d (got %d)", what, MS_LMAX, Lq);
-    POLUS_REQUIRE(Ld >= 1 && Ld <= MS_LMAX, "%s: need 1 <= Ld <= %d (got %d)", what, MS_LMAX, Ld);
-    POLUS_REQUIRE(B >= 1 && B <= 65535, "%s: need 1 <= B <= 65535 (got %d)", what, B);
-    POLUS_REQUIRE(C >= 1 && C <= 65535, "%s: need 1 <= C <= 65535 (got %d)", what, C);
-    POLUS_REQUIRE(N >= 1, "%s: need 1 <= N <= 2^31 - 1 (got %d)", what, N);
-    POLUS_REQUIRE(ldc >= C, "%s: candidate row stride ldc must be >= C (got %ld < %d)", what, ldc, C);
-    POLUS_REQUIRE(lds >= C, "%s: score row stride lds must be >= C (got %ld < %d)", what, lds, C);
+    int rc = ms_shape_check(what, dtype, B, Lq, Ld, E);
+    if (rc == POLUS_OK) rc = rr_args_check(what, C, N, ldc, lds);
+    if (rc != POLUS_OK) return rc;
     POLUS_REQUIRE(Q && D && cand && score, "%s: null pointer", what);
     POLUS_REQUIRE(polus_aligned16(Q) && polus_aligned16(D), "%s: Q and D must be 16-byte aligned", what);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == POLUS_BF16)
-        rr_dispatch<bf16_t>(E, Q, D, qmask, dmask, cand, ldc, score, lds, B, C, N, Lq, Ld, st);
-    else
-        rr_dispatch<float>(E, Q, D, qmask, dmask, cand, ldc, score, lds, B, C, N, Lq, Ld, st);
+    ms_dispatch(dtype, E, [&](auto t, auto ks) {
+        using T = typename decltype(t)::type;
+        constexpr int KS = decltype(ks)::value;
+        rr_launch<T, KS>(maxsim_rerank_kernel<T, KS, true>, maxsim_rerank_kernel<T, KS, false>, B, C, Lq,
+                         static_cast<hipStream_t>(stream), static_cast<const T*>(Q), static_cast<const T*>(D), qmask,
+                         dmask, cand, ldc, score, lds, C, N, Lq, Ld);
+    });
     POLUS_CHECK_LAUNCH(what);
     return POLUS_OK;
 }

@@ -302,40 +302,6 @@ int res_codec_check(const char* what, int dtype, int K, int nbits, int E) {
     default: CALL(4); break;                                   \
     }
 
-template <typename T, int KS, int NB>
-void res_rerank_launch(const void* Q, const uint16_t* codes, const uint8_t* packed, const void* cent, int K,
-                       const float* weights, const int32_t* qm, const int32_t* dm, const int32_t* cand, long ldc,
-                       float* score, long lds, int B, int C, int N, int Lq, int Ld, hipStream_t st) {
-    const int dpw = rr_docs_per_wave(B, C);
-    dim3 grid((unsigned)((C + 4 * dpw - 1) / (4 * dpw)), (unsigned)B);
-    if ((Lq + 15) / 16 <= MsTiles<T, KS>::UT)
-        hipLaunchKernelGGL((maxsim_rerank_res_kernel<T, KS, NB, true>), grid, dim3(256), 0, st,
-                           static_cast<const T*>(Q), codes, packed, static_cast<const T*>(cent), K, weights, qm, dm,
-                           cand, ldc, score, lds, C, N, Lq, Ld, dpw);
-    else
-        hipLaunchKernelGGL((maxsim_rerank_res_kernel<T, KS, NB, false>), grid, dim3(256), 0, st,
-                           static_cast<const T*>(Q), codes, packed, static_cast<const T*>(cent), K, weights, qm, dm,
-                           cand, ldc, score, lds, C, N, Lq, Ld, dpw);
-}
-
-template <typename T, int NB>
-void res_rerank_by_ks(int E, const void* Q, const uint16_t* codes, const uint8_t* packed, const void* cent, int K,
-                      const float* weights, const int32_t* qm, const int32_t* dm, const int32_t* cand, long ldc,
-                      float* score, long lds, int B, int C, int N, int Lq, int Ld, hipStream_t st) {
-#define RES_KS(KS_) res_rerank_launch<T, KS_, NB>(Q, codes, packed, cent, K, weights, qm, dm, cand, ldc, score, lds, B, C, N, Lq, Ld, st)
-    switch (E / 32) {
-    case 1: RES_KS(1); break;
-    case 2: RES_KS(2); break;
-    case 3: RES_KS(3); break;
-    case 4: RES_KS(4); break;
-    case 5: RES_KS(5); break;
-    case 6: RES_KS(6); break;
-    case 7: RES_KS(7); break;
-    default: RES_KS(8); break;
-    }
-#undef RES_KS
-}
-
 }  // namespace
 
 extern "C" int polus_residual_compress(int dtype, const void* x, const uint16_t* codes, const void* centroids, int K,
@@ -400,26 +366,23 @@ extern "C" int polus_maxsim_rerank_res(int dtype, const void* Q, const uint16_t*
     const char* what = "polus_maxsim_rerank_res";
     int rc = res_codec_check(what, dtype, K, nbits, E);
     if (rc != POLUS_OK) return rc;
-    POLUS_REQUIRE(Lq >= 1 && Lq <= MS_LMAX, "%s: need 1 <= Lq <= %d (got %d)", what, MS_LMAX, Lq);
-    POLUS_REQUIRE(Ld >= 1 && Ld <= MS_LMAX, "%s: need 1 <= Ld <= %d (got %d)", what, MS_LMAX, Ld);
-    POLUS_REQUIRE(B >= 1 && B <= 65535, "%s: need 1 <= B <= 65535 (got %d)", what, B);
-    POLUS_REQUIRE(C >= 1 && C <= 65535, "%s: need 1 <= C <= 65535 (got %d)", what, C);
-    POLUS_REQUIRE(N >= 1, "%s: need 1 <= N <= 2^31 - 1 (got %d)", what, N);
-    POLUS_REQUIRE(ldc >= C, "%s: candidate row stride ldc must be >= C (got %ld < %d)", what, ldc, C);
-    POLUS_REQUIRE(lds >= C, "%s: score row stride lds must be >= C (got %ld < %d)", what, lds, C);
+    // (dtype and E have passed above: from here on the order is Lq, Ld, B, then the candidate lists)
+    rc = ms_shape_check(what, dtype, B, Lq, Ld, E);
+    if (rc == POLUS_OK) rc = rr_args_check(what, C, N, ldc, lds);
+    if (rc != POLUS_OK) return rc;
     POLUS_REQUIRE(Q && codes && packed && centroids && weights && cand && score, "%s: null pointer", what);
     POLUS_REQUIRE(polus_aligned16(Q) && polus_aligned16(centroids), "%s: Q and centroids must be 16-byte aligned", what);
     POLUS_REQUIRE((((uintptr_t)packed) & 3) == 0, "%s: packed must be 4-byte aligned", what);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    ms_dispatch(dtype, E, [&](auto t, auto ks) {
+        using T = typename decltype(t)::type;
+        constexpr int KS = decltype(ks)::value;
 #define RES_CALL(NB_)                                                                                                  \
-    if (dtype == POLUS_BF16)                                                                                           \
-        res_rerank_by_ks<bf16_t, NB_>(E, Q, codes, packed, centroids, K, weights, qmask, dmask, cand, ldc, score, lds, \
-                                      B, C, N, Lq, Ld, st);                                                            \
-    else                                                                                                               \
-        res_rerank_by_ks<float, NB_>(E, Q, codes, packed, centroids, K, weights, qmask, dmask, cand, ldc, score, lds,  \
-                                     B, C, N, Lq, Ld, st)
-    RES_BY_NB(RES_CALL)
+    rr_launch<T, KS>(maxsim_rerank_res_kernel<T, KS, NB_, true>, maxsim_rerank_res_kernel<T, KS, NB_, false>, B, C, Lq, \
+                     static_cast<hipStream_t>(stream), static_cast<const T*>(Q), codes, packed,                        \
+                     static_cast<const T*>(centroids), K, weights, qmask, dmask, cand, ldc, score, lds, C, N, Lq, Ld)
+        RES_BY_NB(RES_CALL)
 #undef RES_CALL
+    });
     POLUS_CHECK_LAUNCH(what);
     return POLUS_OK;
 }

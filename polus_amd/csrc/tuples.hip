@@ -24,18 +24,8 @@
 
 namespace {
 
-constexpr int TP_NOJ = 0x7fffffff;      // "no valid j yet" (maxsim.hip's MS_NOJ)
-
 __device__ __forceinline__ long tp_doc(int b, int j, int B, int n, int layout) {
     return layout ? (long)b * n + j : (long)j * B + b;
-}
-
-// rerank.hip's rr_tile_load: A fragments of document tile t (rows past Ld re-read row Ld - 1)
-template <typename T, int KS>
-__device__ __forceinline__ void tp_tile_load(Frag<T> (&f)[KS], const unsigned char* base, int t, int i, int Ld) {
-    const unsigned char* p = base + (size_t)min(16 * t + i, Ld - 1) * (32 * KS * sizeof(T));
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) frag_load_row(f[ks], p + ks * 32 * sizeof(T));
 }
 
 // rr_tile_max with the winning row: ascending rows per lane, a strict > keeps the lowest j of equal values
@@ -92,7 +82,7 @@ __global__ __launch_bounds__(256) void maxsim_tuples_fwd_kernel(const T* __restr
     }
     // two tile buffers used in turn, two tiles per trip (rerank.hip): at the top of a round ta = tile 0
     Frag<T> ta[KS], tb[KS];
-    tp_tile_load<T, KS>(ta, Dc, 0, i, Ld);
+    rr_tile_load<T, KS>(ta, Dc, 0, i, Ld);
     Frag<T> qf[UT][KS];
     bool qok[UT];
     if constexpr (RES) rr_query_load<T, KS, UT>(qf, qok, Qb, qm, 0, nut, Lq, i, g);
@@ -104,13 +94,13 @@ __global__ __launch_bounds__(256) void maxsim_tuples_fwd_kernel(const T* __restr
         float m[UT];
         int jb[UT];
 #pragma unroll
-        for (int u = 0; u < UT; ++u) { m[u] = -INFINITY; jb[u] = TP_NOJ; }
+        for (int u = 0; u < UT; ++u) { m[u] = -INFINITY; jb[u] = MS_NOJ; }
         for (int t = 0; t < nvt; t += 2) {
             const int t1 = min(t + 1, nvt - 1);
             const bool last = t + 2 >= nvt;
-            tp_tile_load<T, KS>(tb, Dc, t1, i, Ld);
+            rr_tile_load<T, KS>(tb, Dc, t1, i, Ld);
             tp_tile_pick<T, KS, UT>(m, jb, ta, qf, __builtin_amdgcn_readlane(tm, t) >> (4 * g), 16 * t + 4 * g, nu);
-            tp_tile_load<T, KS>(ta, Dc, last ? 0 : t + 2, i, Ld);   // the next round starts at tile 0 again
+            rr_tile_load<T, KS>(ta, Dc, last ? 0 : t + 2, i, Ld);   // the next round starts at tile 0 again
             tp_tile_pick<T, KS, UT>(m, jb, tb, qf, __builtin_amdgcn_readlane(tm, t1) >> (4 * g), 16 * t1 + 4 * g, nu);
         }
 #pragma unroll
@@ -125,7 +115,7 @@ __global__ __launch_bounds__(256) void maxsim_tuples_fwd_kernel(const T* __restr
                     if (m2 > mu || (m2 == mu && j2 < ju)) { mu = m2; ju = j2; }
                 }
                 const int tok = 16 * (r0 + u) + i;
-                const bool hit = qok[u] && ju != TP_NOJ;
+                const bool hit = qok[u] && ju != MS_NOJ;
                 if (g == 0 && tok < Lq) am[tok] = hit ? ju : -1;
                 float contrib = hit ? mu : 0.f;
 #pragma unroll
@@ -478,12 +468,8 @@ __global__ __launch_bounds__(256) void distill_finalize_kernel(const float* __re
 
 // ---------------------------------------------------------------- host
 int tp_check(const char* what, int dtype, int B, int n, int layout, int Lq, int Ld, int E, long lds) {
-    POLUS_REQUIRE(dtype == POLUS_F32 || dtype == POLUS_BF16, "%s: unknown dtype %d", what, dtype);
-    POLUS_REQUIRE(E >= 32 && E <= MS_EMAX && E % 32 == 0, "%s: E must be a multiple of 32 in [32, %d] (got %d)", what,
-                  MS_EMAX, E);
-    POLUS_REQUIRE(Lq >= 1 && Lq <= MS_LMAX, "%s: need 1 <= Lq <= %d (got %d)", what, MS_LMAX, Lq);
-    POLUS_REQUIRE(Ld >= 1 && Ld <= MS_LMAX, "%s: need 1 <= Ld <= %d (got %d)", what, MS_LMAX, Ld);
-    POLUS_REQUIRE(B >= 1 && B <= 65535, "%s: need 1 <= B <= 65535 (got %d)", what, B);
+    int rc = ms_shape_check(what, dtype, B, Lq, Ld, E);
+    if (rc != POLUS_OK) return rc;
     POLUS_REQUIRE(n >= 1 && n <= 65535, "%s: need 1 <= n <= 65535 (got %d)", what, n);
     POLUS_REQUIRE((long long)B * n <= 0x7fffffffLL, "%s: B*n must be <= 2^31 - 1 (got %lld)", what, (long long)B * n);
     POLUS_REQUIRE((long long)B * n * Lq < (1LL << 31), "%s: B*n*Lq must be < 2^31 (got %lld)", what,
@@ -492,33 +478,6 @@ int tp_check(const char* what, int dtype, int B, int n, int layout, int Lq, int 
     POLUS_REQUIRE(layout == 0 || layout == 1, "%s: layout must be 0 (slot-major) or 1 (query-major) (got %d)", what,
                   layout);
     return POLUS_OK;
-}
-
-template <typename T, int KS>
-void tp_fwd_launch(const void* Q, const void* D, const int32_t* qm, const int32_t* dm, float* score, long lds,
-                   int32_t* am, int B, int n, int layout, int Lq, int Ld, hipStream_t st) {
-    dim3 grid((unsigned)((n + 3) / 4), (unsigned)B);
-    if ((Lq + 15) / 16 <= MsTiles<T, KS>::UT)
-        hipLaunchKernelGGL((maxsim_tuples_fwd_kernel<T, KS, true>), grid, dim3(256), 0, st, static_cast<const T*>(Q),
-                           static_cast<const T*>(D), qm, dm, score, lds, am, B, n, layout, Lq, Ld);
-    else
-        hipLaunchKernelGGL((maxsim_tuples_fwd_kernel<T, KS, false>), grid, dim3(256), 0, st, static_cast<const T*>(Q),
-                           static_cast<const T*>(D), qm, dm, score, lds, am, B, n, layout, Lq, Ld);
-}
-
-template <typename T>
-void tp_fwd_dispatch(int E, const void* Q, const void* D, const int32_t* qm, const int32_t* dm, float* score, long lds,
-                     int32_t* am, int B, int n, int layout, int Lq, int Ld, hipStream_t st) {
-    switch (E / 32) {
-    case 1: tp_fwd_launch<T, 1>(Q, D, qm, dm, score, lds, am, B, n, layout, Lq, Ld, st); break;
-    case 2: tp_fwd_launch<T, 2>(Q, D, qm, dm, score, lds, am, B, n, layout, Lq, Ld, st); break;
-    case 3: tp_fwd_launch<T, 3>(Q, D, qm, dm, score, lds, am, B, n, layout, Lq, Ld, st); break;
-    case 4: tp_fwd_launch<T, 4>(Q, D, qm, dm, score, lds, am, B, n, layout, Lq, Ld, st); break;
-    case 5: tp_fwd_launch<T, 5>(Q, D, qm, dm, score, lds, am, B, n, layout, Lq, Ld, st); break;
-    case 6: tp_fwd_launch<T, 6>(Q, D, qm, dm, score, lds, am, B, n, layout, Lq, Ld, st); break;
-    case 7: tp_fwd_launch<T, 7>(Q, D, qm, dm, score, lds, am, B, n, layout, Lq, Ld, st); break;
-    default: tp_fwd_launch<T, 8>(Q, D, qm, dm, score, lds, am, B, n, layout, Lq, Ld, st); break;
-    }
 }
 
 template <typename T>
@@ -604,11 +563,15 @@ extern "C" int polus_maxsim_tuples_fwd(int dtype, const void* Q, const void* D, 
     if (rc != POLUS_OK) return rc;
     POLUS_REQUIRE(Q && D && score && argmax, "%s: null pointer", what);
     POLUS_REQUIRE(polus_aligned16(Q) && polus_aligned16(D), "%s: Q and D must be 16-byte aligned", what);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == POLUS_BF16)
-        tp_fwd_dispatch<bf16_t>(E, Q, D, qmask, dmask, score, lds, argmax, B, n, layout, Lq, Ld, st);
-    else
-        tp_fwd_dispatch<float>(E, Q, D, qmask, dmask, score, lds, argmax, B, n, layout, Lq, Ld, st);
+    ms_dispatch(dtype, E, [&](auto t, auto ks) {
+        using T = typename decltype(t)::type;
+        constexpr int KS = decltype(ks)::value;
+        const auto kern = ms_query_fits<T, KS>(Lq) ? maxsim_tuples_fwd_kernel<T, KS, true>
+                                                   : maxsim_tuples_fwd_kernel<T, KS, false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((n + 3) / 4), (unsigned)B), dim3(256), 0,
+                           static_cast<hipStream_t>(stream), static_cast<const T*>(Q), static_cast<const T*>(D), qmask,
+                           dmask, score, lds, argmax, B, n, layout, Lq, Ld);
+    });
     POLUS_CHECK_LAUNCH(what);
     return POLUS_OK;
 }

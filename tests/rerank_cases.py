@@ -68,7 +68,7 @@ def present(cand, N):
 
 
 # Several documents per wave.  A wave of the rerank kernel takes candidates c, c + 4, ... of its workgroup's block of
-# 4 * dpw columns, and the launch (rerank.hip rr_launch) halves dpw from 8 while fewer than 1024 workgroups result, so
+# 4 * dpw columns, and the launch (maxsim_common.h rr_launch) halves dpw from 8 while fewer than 1024 workgroups result, so
 # dpw exceeds 1 only from Q * ceil(C / 8) >= 1024 on.  (Q, N, Lq, Ld, E), [(C, dpw), ...]: every C leaves a partial
 # last block, where waves hold fewer documents than dpw.  Ld = 70 is five tiles, an odd number.
 WAVE_SHAPES = [((16, 48, 20, 70, 64), [(507, 2), (1011, 4), (2021, 8)]),       # the query stays in registers
