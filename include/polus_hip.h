@@ -163,8 +163,9 @@ int polus_dense_bwd_params_grouped(int dtype, int n, const polus_dw_problem* pro
  * out[2 + k] = K slices of problem k (stream-K: its slots per tile).  out holds 2 + n ints. */
 int polus_dense_bwd_params_grouped_route(int dtype, int n, const polus_dw_problem* problems, int T, int split_k, int* out);
 
-/* ---- Dense layers with at most 8 output units (a token-classification head, polus/ner/models.py:26-44; the last layer of
- * tutorials/classifier_example.py:44-48): y = x W^T + b, W [C][H] row-major in `dtype`.  HBM-bound, one wave per row, no matrix
+/* ---- Dense layers with at most 8 output units (a token-classification head, polus/ner/models.py:26-44; the Dense(10) that ends
+ * tutorials/classifier_example.py:44-48 has C = 10 and stays on polus_gemm + polus_dense_bwd_params): y = x W^T + b, W [C][H]
+ * row-major in `dtype`.  HBM-bound, one wave per row, no matrix
  * pipe: a 128-wide MFMA tile would compute 97 % padding.  polus_dense_thin_supported: 1 when (dtype, H, C) fits (C <= 8,
  * H a multiple of 16 bytes of elements, H <= 1024).  forward: y [rows][C] in y_dtype (f32 or dtype).  backward: dy [rows][C] in
  * dy_dtype (f32 or dtype); dx [rows][H] in dtype or NULL; dW [C][H] and db [C] (or NULL) f32, (+)= when accumulate; sums in a fixed

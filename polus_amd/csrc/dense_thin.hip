@@ -1,5 +1,6 @@
 // Dense layers with a handful of output units (a token-classification head: hidden -> 4 labels; polus/ner/models.py:26-44 ends in
-// one, tutorials/classifier_example.py:44-48 likewise): y = x W^T + b with W [C][H], C <= 8.
+// one): y = x W^T + b with W [C][H], C <= 8.  The Dense(10) that ends tutorials/classifier_example.py:44-48 has C = 10 and stays
+// on the GEMM path.
 //
 // A 128 x 128 MFMA tile wastes 97 % of its columns on such a layer, and its weight gradient is a [C][H] matrix contracted over
 // every token -- three GEMM launches, a split-K reduce and two column-sum launches (141 us per step at 16384 tokens) for what is

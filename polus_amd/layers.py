@@ -214,8 +214,9 @@ class Dense(Layer):
             ops.act_bwd(dy2.contiguous(), self._u, du, self.activation)
             dy2 = du
         rows = x.shape[0]
-        acc = ops.GEMM_ACCUM_C if accumulate else 0
-        ops.dense_bwd_params(dy2.contiguous() if dy2.stride(1) != 1 else dy2, x, self.w.grad,
+        if dy2.stride(1) != 1:  # both GEMMs below read dy with a unit column stride
+            dy2 = dy2.contiguous()
+        ops.dense_bwd_params(dy2, x, self.w.grad,
                              self.b.grad if self.b is not None else None, accumulate,
                              dw_split_k(self.units, self.in_features, rows))
         if not need_dx:
