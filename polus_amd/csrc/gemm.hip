@@ -469,12 +469,22 @@ static int launch_splitk_reduce(int c_dtype, const float* slabs, int splits, int
     return POLUS_OK;
 }
 
+// K slicing, stated once: a contraction of K > 0 rows in tiles of bk, cut into at most split_k slices of whole tiles.
+// asked: split_k brought into 1 .. K tiles (what workspaces are sized for); rows: per slice; count: non-empty slices <= asked.
+struct KSlices { int asked, rows, count; };
+static KSlices k_slices(int K, int bk, int split_k) {
+    const int nkt = (K + bk - 1) / bk;
+    const int asked = split_k < 1 ? 1 : (split_k > nkt ? nkt : split_k);
+    const int kt_per_split = (nkt + asked - 1) / asked;
+    return {asked, kt_per_split * bk, (nkt + kt_per_split - 1) / kt_per_split};
+}
+
 // A validated polus_gemm(_dropout) call: the kernels' argument block (but for k_per_split and partial, which the launch
-// derives from the route), the route, and the K tiling the route was asked with.
+// derives from the route), the route, and the K slicing the route was asked with.
 struct GemmPlan {
     GemmArgs a;
     GemmRoute r;
-    int bk, nkt, kt_per_split;
+    int bk; KSlices ks;
 };
 
 // Validates a call and decides its route; launches nothing and dereferences no pointer (polus_gemm_route hands it made-up
@@ -496,11 +506,10 @@ static int gemm_plan(int dtype, int a_layout, int b_layout, int c_dtype,
     POLUS_REQUIRE(!resid || ldr >= N, "polus_gemm: ldr too small");
     POLUS_REQUIRE(!((flags & POLUS_GEMM_ACT_BWD) && !aux), "polus_gemm: ACT_BWD needs aux");
     POLUS_REQUIRE(!aux || ldaux >= N, "polus_gemm: ldaux too small");
-    if (split_k < 1) split_k = 1;
     const size_t es = polus_dtype_size(dtype), ecs = polus_dtype_size(c_dtype);
     const int bk = dtype == POLUS_BF16 ? 64 : 32;
-    const int nkt = (K + bk - 1) / bk;
-    if (split_k > nkt) split_k = nkt;
+    const KSlices ks = k_slices(K, bk, split_k);
+    split_k = ks.asked;
     const bool both_kc = a_layout == POLUS_K_CONTIG && b_layout == POLUS_K_CONTIG;
     if (split_k > 1) {
         const bool epi = resid || aux || (flags & (POLUS_GEMM_ACT_FWD | POLUS_GEMM_ACT_BWD | POLUS_GEMM_DROPOUT));
@@ -538,34 +547,21 @@ static int gemm_plan(int dtype, int a_layout, int b_layout, int c_dtype,
     a.epi_vec16 = ev16 && dtype == POLUS_BF16;
     a.order = polus_cfg().gemm_order;
 
-    const int kt_per_split = (nkt + split_k - 1) / split_k;
-    const bool c_is_f32 = c_dtype == POLUS_F32;
-    const int a_ks = a_layout == POLUS_K_STRIDED, b_ks = b_layout == POLUS_K_STRIDED;
-    p->r = gemm_route(a, dtype, c_is_f32, a_ks, b_ks, (nkt + kt_per_split - 1) / kt_per_split);
-    p->bk = bk; p->nkt = nkt; p->kt_per_split = kt_per_split;
+    p->r = gemm_route(a, dtype, c_dtype == POLUS_F32, a_layout == POLUS_K_STRIDED, b_layout == POLUS_K_STRIDED, ks.count);
+    p->bk = bk; p->ks = ks;
     return POLUS_OK;
 }
 
-static int gemm_impl(int dtype, int a_layout, int b_layout, int c_dtype,
-                     const void* A, long lda, const void* B, long ldb, void* C, long ldc,
-                     int M, int N, int K, float alpha,
-                     const float* bias, const void* resid, long ldr, void* aux, long ldaux,
-                     int act, int flags, int split_k, void* workspace, size_t workspace_bytes,
-                     float drop_p, uint32_t seed, void* stream) {
-    GemmPlan pl;
-    int rc = gemm_plan(dtype, a_layout, b_layout, c_dtype, A, lda, B, ldb, C, ldc, M, N, K, alpha, bias, resid, ldr, aux, ldaux,
-                       act, flags, split_k, workspace, &workspace_bytes, drop_p, seed, &pl);
-    if (rc != POLUS_OK) return rc;
+// Launches a plan; dtype, c_dtype and the layouts are those it was made with.
+static int gemm_launch(GemmPlan& pl, int dtype, int a_layout, int b_layout, int c_dtype, void* workspace, void* stream) {
     GemmArgs& a = pl.a;
     const GemmRoute& r = pl.r;
-    const int bk = pl.bk, nkt = pl.nkt, kt_per_split = pl.kt_per_split;
     const bool c_is_f32 = c_dtype == POLUS_F32;
     const int a_ks = a_layout == POLUS_K_STRIDED, b_ks = b_layout == POLUS_K_STRIDED;
-    if (r.splits > 1) { a.k_per_split = kt_per_split * bk; a.partial = static_cast<float*>(workspace); }
-    else a.k_per_split = r.kernel == GEMM_V1 ? nkt * bk : ((K + 31) / 32) * 32;
-
+    if (r.splits > 1) { a.k_per_split = pl.ks.rows; a.partial = static_cast<float*>(workspace); }
+    else a.k_per_split = r.kernel == GEMM_V1 ? ((a.K + pl.bk - 1) / pl.bk) * pl.bk : ((a.K + 31) / 32) * 32;    // all of K in whole tiles
     hipStream_t st = static_cast<hipStream_t>(stream);
-    rc = POLUS_ERR_INVALID;
+    int rc = POLUS_ERR_INVALID;
     switch (r.kernel) {
         case GEMM_V1: rc = launch_v1(dtype, c_dtype, a_layout, b_layout, a, r.drop, r.splits, st); break;
         case GEMM_RING:
@@ -582,10 +578,20 @@ static int gemm_impl(int dtype, int a_layout, int b_layout, int c_dtype,
         case REDUCE_NONE: break;
         case REDUCE_EPI: return launch_splitk_reduce_epi(a, r.splits, st);
         case REDUCE_PLAIN:
-            return launch_splitk_reduce(c_dtype, a.partial, r.splits, M, N, C, ldc, alpha, bias, (flags & POLUS_GEMM_ACCUM_C) ? 1 : 0,
-                                        "polus_gemm(splitk_reduce)", st);
+            return launch_splitk_reduce(c_dtype, a.partial, r.splits, a.M, a.N, a.C, a.ldc, a.alpha, a.bias,
+                                        (a.flags & POLUS_GEMM_ACCUM_C) ? 1 : 0, "polus_gemm(splitk_reduce)", st);
     }
     return POLUS_OK;
+}
+
+static int gemm_impl(int dtype, int a_layout, int b_layout, int c_dtype,
+                     const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K, float alpha,
+                     const float* bias, const void* resid, long ldr, void* aux, long ldaux, int act, int flags, int split_k,
+                     void* workspace, size_t workspace_bytes, float drop_p, uint32_t seed, void* stream) {
+    GemmPlan pl;
+    int rc = gemm_plan(dtype, a_layout, b_layout, c_dtype, A, lda, B, ldb, C, ldc, M, N, K, alpha, bias, resid, ldr, aux, ldaux,
+                       act, flags, split_k, workspace, &workspace_bytes, drop_p, seed, &pl);
+    return rc != POLUS_OK ? rc : gemm_launch(pl, dtype, a_layout, b_layout, c_dtype, workspace, stream);
 }
 
 extern "C" int polus_gemm(int dtype, int a_layout, int b_layout, int c_dtype,
@@ -642,12 +648,17 @@ extern "C" int polus_gemm_route(int dtype, int a_layout, int b_layout, int c_dty
 
 // ---- Dense backward for the parameters: dW = dY^T X (+)= and db = column sums of dY, one pass
 // over dY.  On the ring kernel the bias gradient rides on the matrix pipe (ones-fragment MFMA).
+// Workspace of one call with split_k >= 1 slices: f32 slabs [split_k][n_out][n_in] (none for one slice), then at the next 256-byte
+// boundary (cs_off) the ring kernel's column sums [split_k][n_out] or polus_colsum's scratch; the 256-byte tail covers the rounding.
+struct DwLayout { size_t cs_off, bytes; };
+static DwLayout dw_layout(int T, int n_out, int n_in, int split_k) {
+    const size_t slabs = split_k > 1 ? (size_t)split_k * n_out * n_in * sizeof(float) : 0;
+    const size_t cs = (size_t)split_k * n_out * sizeof(float), fallback = polus_colsum_workspace_bytes(T, n_out);
+    return {(slabs + 255) / 256 * 256, slabs + (cs > fallback ? cs : fallback) + 256};
+}
+// Shape only, so split_k is taken as asked: the launcher lays out min(split_k, K tiles of its dtype) slices in no more room.
 extern "C" size_t polus_dense_bwd_params_workspace_bytes(int T, int n_out, int n_in, int split_k) {
-    if (split_k < 1) split_k = 1;
-    size_t slabs = split_k > 1 ? (size_t)split_k * n_out * n_in * sizeof(float) : 0;
-    size_t cs = (size_t)split_k * n_out * sizeof(float);
-    size_t fallback = polus_colsum_workspace_bytes(T, n_out);
-    return slabs + (cs > fallback ? cs : fallback) + 256;
+    return dw_layout(T, n_out, n_in, split_k < 1 ? 1 : split_k).bytes;
 }
 
 namespace {
@@ -688,52 +699,72 @@ static void dw_dest(GemmArgs& a, const polus_dw_problem& q, void* slabs, int acc
     }
 }
 
-// Which form a polus_dense_bwd_params call takes: the ring kernel with the bias gradient on the matrix pipe, or
-// polus_gemm + polus_colsum.
-static bool dw_use_ring(int dtype, const void* dY, long lddy, const void* X, long ldx, const float* db, int n_out, int n_in) {
-    const size_t es = polus_dtype_size(dtype);
-    const bool vec = polus_aligned16(dY) && polus_aligned16(X) && ((lddy * es) % 16 == 0) && ((ldx * es) % 16 == 0) &&
-                     (n_out % (16 / es) == 0) && (n_in % (16 / es) == 0);
-    return dtype == POLUS_BF16 && vec && n_out >= 256 && n_in >= 128 && db != nullptr && !polus_cfg().gemm_v1;
+// The problem fits the ring dW kernel: bf16, dY and X in whole aligned 16-byte chunks (8 elements), at least one 256 x 128 tile.
+// The single call adds `db != nullptr`, the grouped one "not POLUS_DW_UNGROUPED, and every problem fits".
+static bool dw_fits_ring(int dtype, const polus_dw_problem& q) {
+    return dtype == POLUS_BF16 && polus_aligned16(q.dY) && polus_aligned16(q.X) && q.lddy % 8 == 0 && q.ldx % 8 == 0 &&
+           q.n_out % 8 == 0 && q.n_in % 8 == 0 && q.n_out >= 256 && q.n_in >= 128 && !polus_cfg().gemm_v1;
+}
+// Its dW allows the 16-byte accesses of the one-launch reductions of a group (polus_launch_dw_group_reduce / _sk).
+static bool dw_reduce_aligned(const polus_dw_problem& q) { return (q.n_in % 4 == 0) && (q.lddw % 4 == 0) && polus_aligned16(q.dW); }
+
+// A validated polus_dense_bwd_params call: the ring kernel or polus_gemm + polus_colsum, and what either form launches with.
+struct DwPlan {
+    bool ring;
+    int kps, splits;    // contraction rows per K slice, K slices launched
+    size_t cs_off;      // workspace: the slabs at 0, the column sums (fallback: polus_colsum's scratch) here
+    GemmPlan gemm;      // !ring: the polus_gemm the call stands for
+};
+
+// Validates and decides, like gemm_plan: no launch, no pointer dereferenced, ws_bytes null where there is no workspace to check.
+static int dw_plan(int dtype, const polus_dw_problem& q, int T, int accumulate, int split_k,
+                   const void* workspace, const size_t* ws_bytes, DwPlan* p) {
+    POLUS_REQUIRE(q.dY && q.X && q.dW, "polus_dense_bwd_params: null pointer");
+    POLUS_REQUIRE(T > 0 && q.n_out > 0 && q.n_in > 0, "polus_dense_bwd_params: bad shape");
+    const size_t need = polus_dense_bwd_params_workspace_bytes(T, q.n_out, q.n_in, split_k);
+    if (ws_bytes && (!workspace || *ws_bytes < need)) { polus_set_error("polus_dense_bwd_params: workspace %zu < %zu", *ws_bytes, need); return POLUS_ERR_WORKSPACE; }
+    const KSlices ks = k_slices(T, dtype == POLUS_BF16 ? 64 : 32, split_k);
+    p->ring = q.db != nullptr && dw_fits_ring(dtype, q);
+    p->kps = ks.rows; p->splits = ks.count;
+    p->cs_off = dw_layout(T, q.n_out, q.n_in, ks.asked).cs_off;
+    if (p->ring) return POLUS_OK;
+    int rc = gemm_plan(dtype, POLUS_K_STRIDED, POLUS_K_STRIDED, POLUS_F32, q.dY, q.lddy, q.X, q.ldx, q.dW, q.lddw, q.n_out, q.n_in, T,
+                       1.0f, nullptr, nullptr, 0, nullptr, 0, 0, accumulate ? POLUS_GEMM_ACCUM_C : 0, ks.asked,
+                       workspace, ws_bytes ? &p->cs_off : nullptr, 0.0f, 0u, &p->gemm);
+    p->splits = p->gemm.r.splits;
+    return rc;
+}
+
+// polus_dense_bwd_params: plan, then launch
+static int dw_impl(int dtype, const polus_dw_problem& q, int T, int accumulate, int split_k, void* workspace, size_t workspace_bytes, void* stream) {
+    DwPlan pl;
+    int rc = dw_plan(dtype, q, T, accumulate, split_k, workspace, &workspace_bytes, &pl);
+    if (rc != POLUS_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    unsigned char* ws = static_cast<unsigned char*>(workspace);
+    float* cs_ws = reinterpret_cast<float*>(ws + pl.cs_off);
+    if (!pl.ring) {
+        rc = gemm_launch(pl.gemm, dtype, POLUS_K_STRIDED, POLUS_K_STRIDED, POLUS_F32, ws, stream);
+        if (rc != POLUS_OK || !q.db) return rc;
+        return polus_colsum(dtype, q.dY, q.lddy, T, q.n_out, q.db, accumulate, cs_ws, workspace_bytes - pl.cs_off, stream);
+    }
+    GemmArgs a = dw_args(q, T, pl.kps, cs_ws);
+    dw_dest(a, q, pl.splits > 1 ? ws : nullptr, accumulate);
+    rc = polus_launch_gemm_ring(a, 1, 1, 1, pl.splits, -1, st);
+    if (rc != POLUS_OK) return rc;
+    if (pl.splits > 1) {
+        rc = launch_splitk_reduce(POLUS_F32, reinterpret_cast<const float*>(ws), pl.splits, q.n_out, q.n_in, q.dW, q.lddw, 1.0f, nullptr,
+                                  accumulate ? 1 : 0, "polus_dense_bwd_params(reduce)", st);
+        if (rc != POLUS_OK) return rc;
+    }
+    return launch_colsum_splits(cs_ws, pl.splits, q.n_out, q.db, accumulate ? 1 : 0, "polus_dense_bwd_params(colsum)", st);
 }
 
 extern "C" int polus_dense_bwd_params(int dtype, const void* dY, long lddy, const void* X, long ldx,
                                       float* dW, long lddw, float* db, int T, int n_out, int n_in,
                                       int accumulate, int split_k, void* workspace, size_t workspace_bytes,
                                       void* stream) {
-    POLUS_REQUIRE(dY && X && dW, "polus_dense_bwd_params: null pointer");
-    POLUS_REQUIRE(T > 0 && n_out > 0 && n_in > 0, "polus_dense_bwd_params: bad shape");
-    if (split_k < 1) split_k = 1;
-    size_t need = polus_dense_bwd_params_workspace_bytes(T, n_out, n_in, split_k);
-    if (!workspace || workspace_bytes < need) { polus_set_error("polus_dense_bwd_params: workspace %zu < %zu", workspace_bytes, need); return POLUS_ERR_WORKSPACE; }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int bk = dtype == POLUS_BF16 ? 64 : 32;
-    int nkt = (T + bk - 1) / bk;
-    if (split_k > nkt) split_k = nkt;
-    const size_t slab_bytes = split_k > 1 ? (((size_t)split_k * n_out * n_in * sizeof(float) + 255) / 256) * 256 : 0;
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    float* cs_ws = reinterpret_cast<float*>(ws + slab_bytes);
-    const bool ring = dw_use_ring(dtype, dY, lddy, X, ldx, db, n_out, n_in);
-    if (!ring) {
-        int rc = polus_gemm(dtype, POLUS_K_STRIDED, POLUS_K_STRIDED, POLUS_F32, dY, lddy, X, ldx, dW, lddw, n_out, n_in, T,
-                            1.0f, nullptr, nullptr, 0, nullptr, 0, 0, accumulate ? POLUS_GEMM_ACCUM_C : 0, split_k,
-                            ws, slab_bytes, stream);
-        if (rc != POLUS_OK || !db) return rc;
-        return polus_colsum(dtype, dY, lddy, T, n_out, db, accumulate, cs_ws, workspace_bytes - slab_bytes, stream);
-    }
-    const polus_dw_problem q = {dY, lddy, X, ldx, dW, lddw, db, n_out, n_in};
-    const int kt_per_split = (nkt + split_k - 1) / split_k;
-    const int splits = (nkt + kt_per_split - 1) / kt_per_split;
-    GemmArgs a = dw_args(q, T, kt_per_split * bk, cs_ws);
-    dw_dest(a, q, splits > 1 ? ws : nullptr, accumulate);
-    int rc = polus_launch_gemm_ring(a, 1, 1, 1, splits, -1, st);
-    if (rc != POLUS_OK) return rc;
-    if (splits > 1) {
-        rc = launch_splitk_reduce(POLUS_F32, reinterpret_cast<const float*>(ws), splits, n_out, n_in, dW, lddw, 1.0f, nullptr,
-                                  accumulate ? 1 : 0, "polus_dense_bwd_params(reduce)", st);
-        if (rc != POLUS_OK) return rc;
-    }
-    return launch_colsum_splits(cs_ws, splits, n_out, db, accumulate ? 1 : 0, "polus_dense_bwd_params(colsum)", st);
+    return dw_impl(dtype, {dY, lddy, X, ldx, dW, lddw, db, n_out, n_in}, T, accumulate, split_k, workspace, workspace_bytes, stream);
 }
 
 // Host only, no HIP call: out[0] = 1 the ring kernel, 0 the fallback (polus_gemm + polus_colsum); out[1] = K slices launched.
@@ -741,22 +772,10 @@ extern "C" int polus_dense_bwd_params(int dtype, const void* dY, long lddy, cons
 extern "C" int polus_dense_bwd_params_route(int dtype, const void* dY, long lddy, const void* X, long ldx,
                                             float* dW, long lddw, float* db, int T, int n_out, int n_in, int split_k, int* out) {
     POLUS_REQUIRE(out, "polus_dense_bwd_params_route: null out");
-    POLUS_REQUIRE(dY && X && dW, "polus_dense_bwd_params: null pointer");
-    POLUS_REQUIRE(T > 0 && n_out > 0 && n_in > 0, "polus_dense_bwd_params: bad shape");
-    if (split_k < 1) split_k = 1;
-    const int bk = dtype == POLUS_BF16 ? 64 : 32;
-    const int nkt = (T + bk - 1) / bk;
-    if (split_k > nkt) split_k = nkt;
-    if (!dw_use_ring(dtype, dY, lddy, X, ldx, db, n_out, n_in)) {
-        GemmPlan pl;
-        int rc = gemm_plan(dtype, POLUS_K_STRIDED, POLUS_K_STRIDED, POLUS_F32, dY, lddy, X, ldx, dW, lddw, n_out, n_in, T, 1.0f,
-                           nullptr, nullptr, 0, nullptr, 0, 0, 0, split_k, nullptr, nullptr, 0.0f, 0u, &pl);
-        if (rc != POLUS_OK) return rc;
-        out[0] = 0; out[1] = pl.r.splits;
-        return POLUS_OK;
-    }
-    const int kt_per_split = (nkt + split_k - 1) / split_k;
-    out[0] = 1; out[1] = (nkt + kt_per_split - 1) / kt_per_split;
+    DwPlan pl;
+    int rc = dw_plan(dtype, {dY, lddy, X, ldx, dW, lddw, db, n_out, n_in}, T, 0, split_k, nullptr, nullptr, &pl);
+    if (rc != POLUS_OK) return rc;
+    out[0] = pl.ring; out[1] = pl.splits;
     return POLUS_OK;
 }
 
@@ -788,11 +807,9 @@ static bool grouped_sk_plan(int n, const polus_dw_problem* pr, int T, int split_
 
 static void grouped_splits(int n, const polus_dw_problem* pr, int T, int split_k, int* splits, bool pp) {
     const int nkt = (T + 63) / 64;
-    int tiles[POLUS_MAX_GROUP], total = 0;
-    for (int k = 0; k < n; ++k) {
+    int tiles[POLUS_MAX_GROUP];
+    for (int k = 0; k < n; ++k)
         tiles[k] = pp ? polus_ppks_tiles(pr[k].n_out, pr[k].n_in) : ((pr[k].n_out + 255) / 256) * ((pr[k].n_in + 127) / 128);
-        total += tiles[k];
-    }
     if (split_k > 0) {
         for (int k = 0; k < n; ++k) splits[k] = split_k < nkt ? split_k : nkt;
         return;
@@ -821,32 +838,38 @@ static void grouped_splits(int n, const polus_dw_problem* pr, int T, int split_k
     }
 }
 
-// Everything the workspace query and the launcher of a grouped dW must agree on, computed in one place from what the query
-// knows: (n, problems' shapes, T, split_k) and the switches.
+// What runs a grouped dW call: one polus_dense_bwd_params call per problem, or one launch over every problem's (slice, tile)
+// list by the ring kernel, by the ping-pong kernel with an even split, or by its stream-K hybrid.  The values are the codes of
+// out[0] of polus_dense_bwd_params_grouped_route and the indices of ops.DW_GROUPED_KERNELS (tests/gemm_cases.py restates them).
+enum DwGroupedKernel { DWG_ONE_BY_ONE, DWG_RING, DWG_PP, DWG_PP_SK };
+
+// The plan has two stages.  grouped_dw_layout: everything the workspace query and the launcher of a grouped dW must agree on,
+// computed in one place from what the query knows: (n, problems' shapes, T, split_k) and the switches.
 // `pp` is grouped_use_pp, decided from shapes alone: the query cannot see the dtype and the pointers that can send the launcher
 // to its one-by-one fallback.  That is safe.  Where the grouped kernel runs, the launcher's conditions imply those of the
 // ring kernel, so pp (and sk, which needs pp) are exactly the kernel it takes and the layout here is the one it writes.
 // Where it does not, no grouped kernel writes anything: each problem runs alone with splits[k] slices -- a count sized for
 // ping-pong tiles is as valid a split_k as any -- in a workspace of at least `single` bytes, which is sized for those counts.
+// grouped_dw_plan: the route, which needs dtype and pointers; the launcher switches on it and the report copies it.
 struct GroupedDwPlan {
-    bool pp, sk;
+    bool pp, sk;                                             // layout: ping-pong tiles; there is a stream-K launch (skp)
     int splits[POLUS_MAX_GROUP];                             // K slices asked for, per problem
     int kps[POLUS_MAX_GROUP], eff[POLUS_MAX_GROUP];          // even split: contraction rows per slice, non-empty slices
     size_t slab_off[POLUS_MAX_GROUP], cs_off[POLUS_MAX_GROUP];   // even split: slabs [splits][n_out][n_in], column sums [splits][n_out]
     PPKSSKPlan skp;                                          // sk: the stream-K launch, its slabs at offset 0 ...
     size_t sk_cs_off[POLUS_MAX_GROUP];                       // ... and its column sums [slots][n_out]
     size_t bytes;                                            // the largest of the even, stream-K and one-by-one layouts
+    DwGroupedKernel kernel; bool fused_reduce;               // route; every slab reduction and bias gradient in one launch
+    int slices[POLUS_MAX_GROUP];                             // K slices each problem runs with (stream-K: its slots per tile)
 };
 
-static void grouped_dw_plan(int n, const polus_dw_problem* pr, int T, int split_k, GroupedDwPlan* pl) {
+static void grouped_dw_layout(int n, const polus_dw_problem* pr, int T, int split_k, GroupedDwPlan* pl) {
     pl->pp = grouped_use_pp(n, pr, T);
     grouped_splits(n, pr, T, split_k, pl->splits, pl->pp);
-    const int nkt = (T + 63) / 64;
     size_t off = 0, single = 0;
     for (int k = 0; k < n; ++k) {
-        const int sk = pl->splits[k] > nkt ? nkt : pl->splits[k];
-        pl->kps[k] = ((nkt + sk - 1) / sk) * 64;
-        pl->eff[k] = (nkt + (pl->kps[k] / 64) - 1) / (pl->kps[k] / 64);
+        const KSlices ks = k_slices(T, 64, pl->splits[k]);
+        pl->kps[k] = ks.rows; pl->eff[k] = ks.count;
         pl->slab_off[k] = off;
         if (pl->splits[k] > 1) off += (((size_t)pl->splits[k] * pr[k].n_out * pr[k].n_in * sizeof(float) + 255) / 256) * 256;
         pl->cs_off[k] = off;
@@ -870,8 +893,34 @@ static void grouped_dw_plan(int n, const polus_dw_problem* pr, int T, int split_
 extern "C" size_t polus_dense_bwd_params_grouped_workspace_bytes(int n, const polus_dw_problem* problems, int T, int split_k) {
     if (n < 1 || n > POLUS_MAX_GROUP || !problems || T < 1) return 0;
     GroupedDwPlan pl;
-    grouped_dw_plan(n, problems, T, split_k, &pl);
+    grouped_dw_layout(n, problems, T, split_k, &pl);
     return pl.bytes;
+}
+
+// Validates a grouped dW call and decides all of it, like gemm_plan: no launch, ws_bytes null where there is no workspace to check.
+static int grouped_dw_plan(int dtype, int n, const polus_dw_problem* problems, int T, int split_k,
+                           const void* workspace, const size_t* ws_bytes, GroupedDwPlan* pl) {
+    POLUS_REQUIRE(problems && n >= 1 && n <= POLUS_MAX_GROUP && T > 0, "polus_dense_bwd_params_grouped: bad arguments");
+    bool ring = !polus_cfg().dw_ungrouped, aligned = true;
+    for (int k = 0; k < n; ++k) {
+        const polus_dw_problem& q = problems[k];
+        POLUS_REQUIRE(q.dY && q.X && q.dW && q.n_out > 0 && q.n_in > 0, "polus_dense_bwd_params_grouped: problem %d: bad arguments", k);
+        ring = ring && dw_fits_ring(dtype, q);
+        aligned = aligned && dw_reduce_aligned(q);
+    }
+    grouped_dw_layout(n, problems, T, split_k, pl);
+    if (ws_bytes && (!workspace || *ws_bytes < pl->bytes)) { polus_set_error("polus_dense_bwd_params_grouped: workspace %zu < %zu", *ws_bytes, pl->bytes); return POLUS_ERR_WORKSPACE; }
+    // an unaligned dW drops the stream-K launch for the even split, and the one-launch reduce of either
+    pl->kernel = !ring ? DWG_ONE_BY_ONE : pl->sk && aligned ? DWG_PP_SK : pl->pp ? DWG_PP : DWG_RING;
+    pl->fused_reduce = ring && aligned && (pl->kernel == DWG_PP_SK || polus_cfg().dw_fused_reduce);
+    for (int k = 0; k < n; ++k) pl->slices[k] = pl->kernel == DWG_PP_SK ? pl->skp.slots : pl->eff[k];
+    for (int k = 0; k < n && !ring; ++k) {      // one by one: the plan that each problem's call will make for itself
+        DwPlan one;
+        int rc = dw_plan(dtype, problems[k], T, 0, pl->splits[k], nullptr, nullptr, &one);
+        if (rc != POLUS_OK) return rc;
+        pl->slices[k] = one.splits;
+    }
+    return POLUS_OK;
 }
 
 // Per-problem arrays for the one-launch reductions of a group (polus_launch_dw_group_reduce / _sk).
@@ -879,123 +928,43 @@ struct DwGroupOut {
     const float* slabs[POLUS_MAX_GROUP]; float* cs[POLUS_MAX_GROUP];
     float* dW[POLUS_MAX_GROUP]; float* db[POLUS_MAX_GROUP];
     long lddw[POLUS_MAX_GROUP]; int n_out[POLUS_MAX_GROUP], n_in[POLUS_MAX_GROUP];
-    bool aligned;     // every dW allows the reductions' 16-byte accesses
 };
-static bool dw_reduce_aligned(const polus_dw_problem& q) { return (q.n_in % 4 == 0) && (q.lddw % 4 == 0) && polus_aligned16(q.dW); }
 // slab_off: null where the slabs are not per problem (stream-K) -- else problem k has slabs iff eff[k] > 1
 static DwGroupOut dw_group_out(int n, const polus_dw_problem* pr, unsigned char* ws, const size_t* cs_off, const size_t* slab_off, const int* eff) {
     DwGroupOut o;
-    o.aligned = true;
     for (int k = 0; k < n; ++k) {
         const polus_dw_problem& q = pr[k];
         o.slabs[k] = slab_off && eff[k] > 1 ? reinterpret_cast<const float*>(ws + slab_off[k]) : nullptr;
         o.cs[k] = q.db ? reinterpret_cast<float*>(ws + cs_off[k]) : nullptr;
         o.dW[k] = q.dW; o.db[k] = q.db; o.lddw[k] = q.lddw; o.n_out[k] = q.n_out; o.n_in[k] = q.n_in;
-        o.aligned = o.aligned && dw_reduce_aligned(q);
     }
     return o;
 }
 
-// Validates a grouped dW call; *ring: one grouped launch (every problem fits the ring kernel), else one call per problem.
-static int grouped_dw_check(int dtype, int n, const polus_dw_problem* problems, int T, bool* ring_out) {
-    POLUS_REQUIRE(problems && n >= 1 && n <= POLUS_MAX_GROUP && T > 0, "polus_dense_bwd_params_grouped: bad arguments");
-    const size_t es = polus_dtype_size(dtype);
-    bool ring = dtype == POLUS_BF16 && !polus_cfg().gemm_v1 && !polus_cfg().dw_ungrouped;
-    for (int k = 0; k < n; ++k) {
-        const polus_dw_problem& q = problems[k];
-        POLUS_REQUIRE(q.dY && q.X && q.dW && q.n_out > 0 && q.n_in > 0, "polus_dense_bwd_params_grouped: problem %d: bad arguments", k);
-        ring = ring && polus_aligned16(q.dY) && polus_aligned16(q.X) && ((q.lddy * es) % 16 == 0) && ((q.ldx * es) % 16 == 0) &&
-               (q.n_out % 8 == 0) && (q.n_in % 8 == 0) && q.n_out >= 256 && q.n_in >= 128;
-    }
-    *ring_out = ring;
-    return POLUS_OK;
-}
-
-// Host only, no HIP call: out[0] = the kernel of a grouped dW call (0 one call per problem, 1 ring grouped, 2 ping-pong
-// grouped with an even split, 3 ping-pong stream-K), out[1] = 1 when the slab reductions and bias gradients of the group
-// take one launch, out[2 + k] = K slices of problem k (stream-K: its slots per tile).
-extern "C" int polus_dense_bwd_params_grouped_route(int dtype, int n, const polus_dw_problem* problems, int T, int split_k, int* out) {
-    POLUS_REQUIRE(out, "polus_dense_bwd_params_grouped_route: null out");
-    bool ring;
-    int rc = grouped_dw_check(dtype, n, problems, T, &ring);
-    if (rc != POLUS_OK) return rc;
-    GroupedDwPlan pl;
-    grouped_dw_plan(n, problems, T, split_k, &pl);
-    if (!ring) {
-        out[0] = 0; out[1] = 0;
-        for (int k = 0; k < n; ++k) {
-            const polus_dw_problem& q = problems[k];
-            int one[2];
-            if (q.db) rc = polus_dense_bwd_params_route(dtype, q.dY, q.lddy, q.X, q.ldx, q.dW, q.lddw, q.db, T, q.n_out, q.n_in, pl.splits[k], one);
-            else {
-                GemmPlan gp;
-                rc = gemm_plan(dtype, POLUS_K_STRIDED, POLUS_K_STRIDED, POLUS_F32, q.dY, q.lddy, q.X, q.ldx, q.dW, q.lddw, q.n_out, q.n_in, T,
-                               1.0f, nullptr, nullptr, 0, nullptr, 0, 0, 0, pl.splits[k], nullptr, nullptr, 0.0f, 0u, &gp);
-                one[1] = gp.r.splits;
-            }
-            if (rc != POLUS_OK) return rc;
-            out[2 + k] = one[1];
-        }
-        return POLUS_OK;
-    }
-    bool aligned = true;
-    for (int k = 0; k < n; ++k) aligned = aligned && dw_reduce_aligned(problems[k]);
-    if (pl.sk && aligned) {
-        out[0] = 3; out[1] = 1;
-        for (int k = 0; k < n; ++k) out[2 + k] = pl.skp.slots;
-        return POLUS_OK;
-    }
-    out[0] = pl.pp ? 2 : 1;
-    out[1] = polus_cfg().dw_fused_reduce && aligned;
-    for (int k = 0; k < n; ++k) out[2 + k] = pl.eff[k];
-    return POLUS_OK;
-}
-
-extern "C" int polus_dense_bwd_params_grouped(int dtype, int n, const polus_dw_problem* problems, int T, int accumulate,
-                                              int split_k, void* workspace, size_t workspace_bytes, void* stream) {
-    bool ring;
-    int rc0 = grouped_dw_check(dtype, n, problems, T, &ring);
-    if (rc0 != POLUS_OK) return rc0;
-    GroupedDwPlan pl;
-    grouped_dw_plan(n, problems, T, split_k, &pl);
-    if (!workspace || workspace_bytes < pl.bytes) { polus_set_error("polus_dense_bwd_params_grouped: workspace %zu < %zu", workspace_bytes, pl.bytes); return POLUS_ERR_WORKSPACE; }
-    if (!ring) {
-        for (int k = 0; k < n; ++k) {
-            const polus_dw_problem& q = problems[k];
-            int rc;
-            if (q.db) rc = polus_dense_bwd_params(dtype, q.dY, q.lddy, q.X, q.ldx, q.dW, q.lddw, q.db, T, q.n_out, q.n_in,
-                                                  accumulate, pl.splits[k], workspace, workspace_bytes, stream);
-            else rc = polus_gemm(dtype, POLUS_K_STRIDED, POLUS_K_STRIDED, POLUS_F32, q.dY, q.lddy, q.X, q.ldx, q.dW, q.lddw,
-                                 q.n_out, q.n_in, T, 1.0f, nullptr, nullptr, 0, nullptr, 0, 0, accumulate ? POLUS_GEMM_ACCUM_C : 0,
-                                 pl.splits[k], workspace, workspace_bytes, stream);
-            if (rc != POLUS_OK) return rc;
-        }
-        return POLUS_OK;
-    }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
+// DWG_PP_SK: the stream-K launch and its one-launch reduce.
+static int launch_dwg_sk(int n, const polus_dw_problem* problems, int T, int accumulate, const GroupedDwPlan& pl, unsigned char* ws, hipStream_t st) {
+    const DwGroupOut o = dw_group_out(n, problems, ws, pl.sk_cs_off, nullptr, nullptr);
     GemmArgs ga[POLUS_MAX_GROUP];
-    if (pl.sk) {
-        const DwGroupOut o = dw_group_out(n, problems, ws, pl.sk_cs_off, nullptr, nullptr);
-        if (o.aligned) {             // else: the even split below
-            for (int k = 0; k < n; ++k) {
-                ga[k] = dw_args(problems[k], T, 0, nullptr);     // the stream-K kernel addresses slabs and column sums itself
-                ga[k].epi_vec = ga[k].epi_vec16 = 1;
-            }
-            int rc = polus_launch_gemm_ppks_sk(ga, pl.skp, reinterpret_cast<float*>(ws), o.cs, st);
-            if (rc != POLUS_OK) return rc;
-            return polus_launch_dw_group_reduce_sk(pl.skp, reinterpret_cast<const float*>(ws), o.cs, o.dW, o.db, o.lddw, o.n_out, o.n_in, accumulate ? 1 : 0, st);
-        }
+    for (int k = 0; k < n; ++k) {
+        ga[k] = dw_args(problems[k], T, 0, nullptr);     // the stream-K kernel addresses slabs and column sums itself
+        ga[k].epi_vec = ga[k].epi_vec16 = 1;
     }
+    int rc = polus_launch_gemm_ppks_sk(ga, pl.skp, reinterpret_cast<float*>(ws), o.cs, st);
+    if (rc != POLUS_OK) return rc;
+    return polus_launch_dw_group_reduce_sk(pl.skp, reinterpret_cast<const float*>(ws), o.cs, o.dW, o.db, o.lddw, o.n_out, o.n_in, accumulate ? 1 : 0, st);
+}
+
+// DWG_RING / DWG_PP: eff[k] even slices per problem in one launch, then the reductions in one launch or one by one.
+static int launch_dwg_even(int n, const polus_dw_problem* problems, int T, int accumulate, const GroupedDwPlan& pl, unsigned char* ws, hipStream_t st) {
     const DwGroupOut o = dw_group_out(n, problems, ws, pl.cs_off, pl.slab_off, pl.eff);
+    GemmArgs ga[POLUS_MAX_GROUP];
     for (int k = 0; k < n; ++k) {
         ga[k] = dw_args(problems[k], T, pl.kps[k], o.cs[k]);
         dw_dest(ga[k], problems[k], pl.eff[k] > 1 ? ws + pl.slab_off[k] : nullptr, accumulate);
     }
-    int rc = pl.pp ? polus_launch_gemm_ppks_grouped_dw(ga, n, pl.eff, st) : polus_launch_gemm_ring_grouped_dw(ga, n, pl.eff, st);
+    int rc = pl.kernel == DWG_PP ? polus_launch_gemm_ppks_grouped_dw(ga, n, pl.eff, st) : polus_launch_gemm_ring_grouped_dw(ga, n, pl.eff, st);
     if (rc != POLUS_OK) return rc;
-    // every slab reduction and every bias-gradient finalisation of the group in ONE launch
-    if (polus_cfg().dw_fused_reduce && o.aligned)
+    if (pl.fused_reduce)
         return polus_launch_dw_group_reduce(n, o.slabs, o.cs, o.dW, o.db, o.lddw, o.n_out, o.n_in, pl.eff, accumulate ? 1 : 0, st);
     for (int k = 0; k < n; ++k) {
         const polus_dw_problem& q = problems[k];
@@ -1009,5 +978,36 @@ extern "C" int polus_dense_bwd_params_grouped(int dtype, int n, const polus_dw_p
             if (rc != POLUS_OK) return rc;
         }
     }
+    return POLUS_OK;
+}
+
+extern "C" int polus_dense_bwd_params_grouped(int dtype, int n, const polus_dw_problem* problems, int T, int accumulate,
+                                              int split_k, void* workspace, size_t workspace_bytes, void* stream) {
+    GroupedDwPlan pl;
+    int rc = grouped_dw_plan(dtype, n, problems, T, split_k, workspace, &workspace_bytes, &pl);
+    if (rc != POLUS_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    unsigned char* ws = static_cast<unsigned char*>(workspace);
+    switch (pl.kernel) {
+        case DWG_ONE_BY_ONE:            // each problem as a call of its own; one without db takes the fallback, then polus_gemm alone
+            for (int k = 0; k < n && rc == POLUS_OK; ++k)
+                rc = dw_impl(dtype, problems[k], T, accumulate, pl.splits[k], workspace, workspace_bytes, stream);
+            return rc;
+        case DWG_RING:
+        case DWG_PP: return launch_dwg_even(n, problems, T, accumulate, pl, ws, st);
+        case DWG_PP_SK: return launch_dwg_sk(n, problems, T, accumulate, pl, ws, st);
+    }
+    return POLUS_ERR_INVALID;
+}
+
+// Host only, no HIP call: out[0] = the DwGroupedKernel of a grouped dW call, out[1] = 1 when the slab reductions and bias
+// gradients of the group take one launch, out[2 + k] = K slices of problem k (stream-K: its slots per tile).
+extern "C" int polus_dense_bwd_params_grouped_route(int dtype, int n, const polus_dw_problem* problems, int T, int split_k, int* out) {
+    POLUS_REQUIRE(out, "polus_dense_bwd_params_grouped_route: null out");
+    GroupedDwPlan pl;
+    int rc = grouped_dw_plan(dtype, n, problems, T, split_k, nullptr, nullptr, &pl);
+    if (rc != POLUS_OK) return rc;
+    out[0] = pl.kernel; out[1] = pl.fused_reduce;
+    for (int k = 0; k < n; ++k) out[2 + k] = pl.slices[k];
     return POLUS_OK;
 }

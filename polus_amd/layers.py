@@ -49,15 +49,6 @@ def dw_split_k(out_rows, out_cols, contraction):
     return int(max(1, min(want, contraction // 256, 64)))
 
 
-def dw_group_split_k(shapes, contraction):
-    """Split-K factor for one grouped dW launch over `shapes` = [(n_out, n_in), ...]: the
-    concatenated 256x128 tile lists (each padded to a multiple of 8) times the splits should
-    fill the 512 workgroup slots once."""
-    tiles = sum((((o + 255) // 256) * ((i + 127) // 128) + 7) // 8 * 8 for o, i in shapes)
-    want = max(1, 512 // max(tiles, 1))
-    return int(max(1, min(want, contraction // 256, 64)))
-
-
 def dense_bwd_params_group(problems, accumulate=False):
     """dW (+ db) of several Dense layers that share T: one grouped launch on the bf16 engine; the
     f32 engine (128x128 exact-f32 kernel) runs them one by one with per-matrix split-K."""

@@ -97,12 +97,9 @@ def _req_cuda(*ts):
 _AUTO_SPLIT = {}
 
 
-def gemm(a, b, out, *, a_layout=K_CONTIG, b_layout=K_CONTIG, M=None, N=None, K=None, alpha=1.0,
-         bias=None, resid=None, aux=None, act=None, flags=0, split_k=1, drop_p=0.0, seed=0):
-    """out[M,N] = epilogue(alpha * A_op . B_op); see include/polus_hip.h polus_gemm."""
-    lib = _lib.load()
-    _req_cuda(a, b, out, bias, resid, aux)
-    dt = dtype_code(a.dtype)
+def _gemm_call(a, b, out, a_layout, b_layout, M, N, K, alpha, bias, resid, aux, act, flags, split_k):
+    """What `gemm` and `gemm_route` share: (M, N, K, split_k with "auto" settled, the arguments of polus_gemm and
+    polus_gemm_route up to split_k)."""
     assert b.dtype == a.dtype and a.dim() == 2 and b.dim() == 2 and out.dim() == 2
     if a_layout == K_CONTIG:
         m_, k_ = a.shape
@@ -118,8 +115,6 @@ def gemm(a, b, out, *, a_layout=K_CONTIG, b_layout=K_CONTIG, M=None, N=None, K=N
     assert kb_ == k_, f"contraction mismatch {k_} vs {kb_}"
     assert out.shape[0] >= M and out.shape[1] >= N
     assert a.stride(1) == 1 and b.stride(1) == 1 and out.stride(1) == 1
-    ws = None
-    ws_bytes = 0
     if split_k == "auto":
         # the library's recommendation for a bf16 Dense GEMM (K-contiguous operands, bf16 C); 1 for everything else
         split_k = 1
@@ -128,7 +123,23 @@ def gemm(a, b, out, *, a_layout=K_CONTIG, b_layout=K_CONTIG, M=None, N=None, K=N
             key = (M, N, K)
             split_k = _AUTO_SPLIT.get(key)
             if split_k is None:
-                split_k = _AUTO_SPLIT[key] = int(lib.polus_gemm_auto_split(M, N, K))
+                split_k = _AUTO_SPLIT[key] = int(_lib.load().polus_gemm_auto_split(M, N, K))
+    return M, N, K, split_k, (dtype_code(a.dtype), a_layout, b_layout, dtype_code(out.dtype),
+                              ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(out), out.stride(0),
+                              M, N, K, float(alpha), ptr(bias),
+                              ptr(resid), resid.stride(0) if resid is not None else 0,
+                              ptr(aux), aux.stride(0) if aux is not None else 0,
+                              ACT_CODES[act] if not isinstance(act, int) else act, flags, split_k)
+
+
+def gemm(a, b, out, *, a_layout=K_CONTIG, b_layout=K_CONTIG, M=None, N=None, K=None, alpha=1.0,
+         bias=None, resid=None, aux=None, act=None, flags=0, split_k=1, drop_p=0.0, seed=0):
+    """out[M,N] = epilogue(alpha * A_op . B_op); see include/polus_hip.h polus_gemm."""
+    lib = _lib.load()
+    _req_cuda(a, b, out, bias, resid, aux)
+    M, N, K, split_k, args = _gemm_call(a, b, out, a_layout, b_layout, M, N, K, alpha, bias, resid, aux, act, flags, split_k)
+    ws = None
+    ws_bytes = 0
     if split_k > 1:
         ws_bytes = lib.polus_gemm_workspace_bytes(M, N, split_k)
         ws = workspace(a.device).get(ws_bytes)
@@ -136,12 +147,7 @@ def gemm(a, b, out, *, a_layout=K_CONTIG, b_layout=K_CONTIG, M=None, N=None, K=N
     if prof is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    common = (dt, a_layout, b_layout, dtype_code(out.dtype),
-              ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(out), out.stride(0),
-              M, N, K, float(alpha), ptr(bias),
-              ptr(resid), resid.stride(0) if resid is not None else 0,
-              ptr(aux), aux.stride(0) if aux is not None else 0,
-              ACT_CODES[act] if not isinstance(act, int) else act, flags, split_k, ptr(ws), ws_bytes)
+    common = args + (ptr(ws), ws_bytes)
     if drop_p > 0.0:
         check(lib.polus_gemm_dropout(*common, float(drop_p), int(seed) & 0xFFFFFFFF, _st()), "polus_gemm_dropout")
     else:
@@ -165,20 +171,9 @@ DwGroupedRoute = collections.namedtuple("DwGroupedRoute", "kernel fused_reduce e
 def gemm_route(a, b, out, *, a_layout=K_CONTIG, b_layout=K_CONTIG, M=None, N=None, K=None, alpha=1.0,
                bias=None, resid=None, aux=None, act=None, flags=0, split_k=1, drop_p=0.0, seed=0):
     """The route `gemm` takes with these arguments under the current switches (polus_gemm_route); launches nothing."""
-    m_, k_ = a.shape if a_layout == K_CONTIG else a.shape[::-1]
-    n_ = b.shape[0] if b_layout == K_CONTIG else b.shape[1]
-    M, N, K = (m_ if M is None else M), (n_ if N is None else N), (k_ if K is None else K)
-    if split_k == "auto":
-        split_k = 1
-        if (a.dtype == torch.bfloat16 and out.dtype == a.dtype and a_layout == K_CONTIG and b_layout == K_CONTIG
-                and not (flags & GEMM_ACCUM_C)):
-            split_k = int(_lib.load().polus_gemm_auto_split(M, N, K))
+    args = _gemm_call(a, b, out, a_layout, b_layout, M, N, K, alpha, bias, resid, aux, act, flags, split_k)[4]
     r = (ctypes.c_int * 12)()
-    check(_lib.load().polus_gemm_route(
-        dtype_code(a.dtype), a_layout, b_layout, dtype_code(out.dtype),
-        ptr(a), a.stride(0), ptr(b), b.stride(0), ptr(out), out.stride(0), M, N, K, float(alpha), ptr(bias),
-        ptr(resid), resid.stride(0) if resid is not None else 0, ptr(aux), aux.stride(0) if aux is not None else 0,
-        ACT_CODES[act] if not isinstance(act, int) else act, flags, split_k, float(drop_p), r), "polus_gemm_route")
+    check(_lib.load().polus_gemm_route(*args, float(drop_p), r), "polus_gemm_route")
     v = list(r)
     return GemmRoute(GEMM_KERNELS[v[0]], v[1], v[2], v[3], v[4], GEMM_REDUCES[v[5]], v[6], *map(bool, v[7:]))
 
@@ -1196,14 +1191,13 @@ def dense_bwd_params_grouped(problems, accumulate=False, split_k=1):
     db f32 [n_out] or None), ...] with one common T."""
     lib = _lib.load()
     T = problems[0][0].shape[0]
-    arr = (_lib.DwProblem * len(problems))()
-    for k, (dy, x, dw, db) in enumerate(problems):
+    for dy, x, dw, db in problems:
         _req_cuda(dy, x, dw, db)
         assert dy.dtype == x.dtype and dw.dtype == torch.float32 and dy.shape[0] == T and x.shape[0] == T
         assert dy.stride(1) == 1 and x.stride(1) == 1 and dw.stride(1) == 1
         n_out, n_in = dy.shape[1], x.shape[1]
         assert tuple(dw.shape) == (n_out, n_in) and (db is None or (db.dtype == torch.float32 and db.numel() == n_out))
-        arr[k] = _lib.DwProblem(ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(dw), dw.stride(0), ptr(db), n_out, n_in)
+    arr = _dw_problems(problems)
     dt = dtype_code(problems[0][0].dtype)
     nb = lib.polus_dense_bwd_params_grouped_workspace_bytes(len(problems), arr, T, int(split_k))
     ws = workspace(problems[0][0].device).get(nb)

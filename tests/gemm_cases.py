@@ -611,7 +611,7 @@ def _make_cases():
     c += variants(Case(base="dw_fallback_no_db", op="dw", dtype="bf16", shape=DW, want="fallback", split_k=3, db=False), "ends")
     for dt in ("bf16", "f32"):
         c += variants(Case(base=f"dw_fallback_small_{dt}", op="dw", dtype=dt, shape=(75, 50, 97), want="fallback", split_k=2 if dt == "bf16" else 1, accumulate=dt == "f32"), "ends")
-    # grouped dW: two problems each
+    # grouped dW: two problems each (three and five where the hand-out of slices is to show)
     G = lambda base, T, probs, want, views=(), **kw: Case(base=base, op="dwg", dtype="bf16", shape=(T, probs), want=want, views=views, **kw)
     for kind in ("dense", "pad16", "pad1"):
         v = () if kind == "dense" else (("dW0", kind), ("dW1", kind))
@@ -624,6 +624,12 @@ def _make_cases():
     c.append(G("dwg_pp", 192, ((264, 264), (264, 264)), "pp_grouped", (("dY0", "cls"), ("X0", "pad16"), ("dY1", "pad16"), ("X1", "cls")), split_k=3))
     c.append(G("dwg_pp_unfused", 192, ((264, 264), (264, 264)), "pp_grouped", split_k=3, env=(("POLUS_DW_FUSED_REDUCE", 0),)))
     c.append(G("dwg_pp_no_db", 192, ((264, 264), (264, 264)), "pp_grouped", split_k=3, db=False))
+    # split_k = 0, the library chooses the slices (grouped_splits); the handout cases are the smallest at which its extra slice
+    # for the problems with most tiles shows in the report: eff (11, 11, 10) and (13, 13, 13, 13, 11)
+    c.append(G("dwg_pp_auto", 768, ((264, 264), (264, 264)), "pp_grouped", split_k=0))
+    c.append(G("dwg_ring_auto", 768, ((264, 264), (264, 136)), "ring_grouped", split_k=0))
+    c.append(G("dwg_pp_auto_handout", 3520, ((264, 264),) * 3, "pp_grouped", split_k=0))
+    c.append(G("dwg_ring_auto_handout", 3328, ((264, 136), (264, 264)) * 2 + ((264, 136),), "ring_grouped", split_k=0))
     c.append(G("dwg_one_by_one", 192, ((264, 264), (264, 264)), "one_by_one", (("dY1", "pad1"),), split_k=3))
     c.append(G("dwg_one_by_one", 192, ((264, 264), (264, 264)), "one_by_one", (("X0", "shift1"),), split_k=3))
     c.append(G("dwg_one_by_one_small", 192, ((264, 264), (120, 264)), "one_by_one", split_k=2, accumulate=True))

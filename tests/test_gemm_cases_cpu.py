@@ -87,6 +87,10 @@ def test_routes_match_the_library_and_cover_every_route(lib):
             seen_dw.add((got["ring"], got["splits"] > 1))
         else:
             seen_dwg.add((got["kernel"], got["fused_reduce"]))
+            if case.split_k <= 0:
+                seen_dwg.add((got["kernel"], "auto"))
+                if len(set(got["eff"])) > 1:
+                    seen_dwg.add((got["kernel"], "handout"))
         if not case.views:                  # the table's route: what the all-dense variant must run
             kernel = got.get("kernel", {True: "ring", False: "fallback"}.get(got.get("ring")))
             assert kernel == case.want, (case.name, got)
@@ -100,7 +104,11 @@ def test_routes_match_the_library_and_cover_every_route(lib):
         | {("pp", tn, m) for tn in (256, 192) for m in range(4)} | {("pp_persist", 192, m) for m in range(4)}
     assert seen_dw == {(True, False), (True, True), (False, False), (False, True)}
     assert seen_dwg == {("one_by_one", False), ("ring_grouped", True), ("ring_grouped", False), ("pp_grouped", True),
-                        ("pp_grouped", False), ("pp_streamk", True)}
+                        ("pp_grouped", False), ("pp_streamk", True),
+                        # split_k <= 0, the library's own slices: on each grouped kernel, and with grouped_splits' hand-out
+                        # of one extra slice visible in the report on both even-split kernels
+                        ("ring_grouped", "auto"), ("pp_grouped", "auto"), ("pp_streamk", "auto"),
+                        ("ring_grouped", "handout"), ("pp_grouped", "handout")}
 
 
 def test_every_view_kind_flips_the_predicate_it_is_for():
