@@ -644,6 +644,69 @@ int polus_centroid_codes(const float* sim, long lds, const int32_t* mask, uint16
  * non-null pointers. */
 int polus_centroid_update(int dtype, const void* x, const uint16_t* codes, const void* prev, void* out,
                           int32_t* counts, int T, int K, int E, float eps, void* stream);
+/* polus_centroid_scores over a candidate list per query (the probed search, ivf.hip below):
+ *   cand int32 [B, C], row stride ldc >= C;  score f32 [B, C], row stride lds >= C;  codes uint16 [N, Ld] as above
+ *   score[b*lds + c] = the bits polus_centroid_scores gives the pair (b, cand[b*ldc + c]): the same kernel body, lane
+ *                      mapping and summation order on either route, the document index alone taken from cand.
+ *   cand[b, c] < 0 or >= N:  score = -inf and nothing is read for it (-inf is what polus_topk_merge_ids drops).
+ * A repeated id is scored once per copy.  Columns of score past C are not written.  No atomics, no workspace, bitwise
+ * reproducible.  The routes are polus_centroid_scores' (polus_centroid_scores_route with N = C).
+ * Limits (refused before any launch): 1 <= Lq, Ld <= 512; 1 <= K <= 65535; 1 <= B, C <= 65535; N >= 1; ldt >= B*Lq;
+ * ldc >= C; lds >= C; table, codes, cand, score non-null. */
+int polus_centroid_scores_ids(const float* table, long ldt, const int32_t* qmask, const uint16_t* codes,
+                              const int32_t* cand, long ldc, float* score, long lds, int B, int C, int N, int Lq, int Ld,
+                              int K, void* stream);
+
+/* ---- inverted centroid lists and probed candidate generation for a token index (ivf.hip; the first step of PLAID,
+ * ColBERTv2's retrieval: no counterpart in the reference).  The list of centroid c names the documents that hold at
+ * least one present token coded c; a query probes the lists of the nprobe centroids nearest to each of its tokens, the
+ * union of those lists is its candidate set, and polus_centroid_scores_ids scores only that set.
+ *
+ * The lists, in CSR form:  offsets int32 [K + 1], offsets[0] = 0, offsets[K] = P, the number of (centroid, document)
+ * pairs;  docs int32 [P];  docs[offsets[c] .. offsets[c+1]) holds the ids of the documents of centroid c, each exactly
+ * once however many of its tokens share c.  THE ORDER OF THE IDS INSIDE ONE LIST IS UNSPECIFIED (it follows the order
+ * in which workgroups reach a cursor and may differ from run to run); the lists as SETS, counts and offsets are exact
+ * and reproducible (integer arithmetic).  Nothing downstream depends on the order: a list is only ever OR-ed into a
+ * bitmap.  codes uint16 [N, Ld] contiguous are polus_centroid_scores'; a code >= K (0xFFFF among them) is no token.
+ * The caller owns every buffer; nothing is allocated here.  Built in three steps:
+ *   polus_ivf_count:    counts int32 [K] (zeroed by the call itself): counts[c] = documents with a present token c.
+ *                       One wave per document: its codes go to LDS, a token counts iff no earlier token of the document
+ *                       has its code, and each such token adds 1 to its centroid's counter (int32 vector atomics).
+ *   polus_ivf_offsets:  the exclusive scan of counts, one workgroup, 64-bit sums.  P >= 2^31 cannot be addressed: then
+ *                       offsets[K] = -1 and offsets[0 .. K) are unspecified; the caller reads offsets[K] (it needs P to
+ *                       allocate docs) and must refuse a negative value.
+ *   polus_ivf_fill:     cursor int32 [K] is scratch (zeroed by the call itself, meaningless afterwards).  The same walk
+ *                       as count; a counted token takes slot = cursor[c]++ and stores its document id at
+ *                       docs[offsets[c] + slot], only if that index is < offsets[c+1] and < P: offsets that belong to
+ *                       other codes lose entries, they never write out of range.
+ * polus_ivf_mark, the candidate set as a bitmap:
+ *   probes int32 [B*Lq, nprobe], row stride ldp >= nprobe (the ids polus_topk_merge leaves: -1 padded);  qmask int32
+ *   [B, Lq] or NULL (all ones);  bitmap uint32 [B, W], W = ceil(N / 32), row stride ldb >= W words.
+ *   The call first clears the W words of every row (words past W are not touched), then sets bit d & 31 of word
+ *   d >> 5 of row b for every d in the list of every probe (b, i, p) with qmask[b, i] != 0 and 0 <= probe < K.  Any
+ *   other probe value is skipped and nothing is dereferenced for it.  A list position outside [0, P) is not read, a
+ *   list entry outside [0, N) is not written through, so stale or foreign lists cannot fault; bits >= N of the last
+ *   word stay 0.  The result is a set: exact, independent of scheduling and of the order inside the lists (int32 vector
+ *   atomic OR, skipped where the bit is seen set).  Work is spread by list ENTRIES, not by lists: a query's probes are
+ *   taken 256 at a time, their list lengths are prefix-summed in LDS, and the entries of the tile are dealt out evenly
+ *   to the query's workgroups (a binary search finds an entry's list), so one centroid that holds most of the corpus
+ *   costs no more than many small ones.
+ * polus_ivf_compact, the bitmap as ascending ids:
+ *   count int32 [B]: count[b] = the set bits of row b among bits [0, N), the full number also when it exceeds cap.
+ *   cand int32 [B, cap] (row stride ldc >= cap) or NULL: cand[b, 0 .. min(count[b], cap)) = the set positions in
+ *   ascending order, the rest of the row up to cap = -1.  cand == NULL (cap ignored) is the count-only call that sizes
+ *   the buffer.  One workgroup per row: popcounts and a prefix sum over the words, no atomics, deterministic.
+ * Limits (refused before any launch): 1 <= Ld <= 512; 1 <= K <= 65535; N >= 1; B >= 1; 1 <= Lq <= 512;
+ * 1 <= nprobe <= 1024; 0 <= P < 2^31; cap >= 1 with cand; ldp >= nprobe; ldb >= ceil(N/32); ldc >= cap; non-null
+ * pointers (qmask and cand may be NULL; docs may be NULL when P = 0). */
+int polus_ivf_count(const uint16_t* codes, int N, int Ld, int K, int32_t* counts, void* stream);
+int polus_ivf_offsets(const int32_t* counts, int K, int32_t* offsets, void* stream);
+int polus_ivf_fill(const uint16_t* codes, int N, int Ld, int K, const int32_t* offsets, int P, int32_t* cursor,
+                   int32_t* docs, void* stream);
+int polus_ivf_mark(const int32_t* probes, long ldp, const int32_t* qmask, const int32_t* offsets, const int32_t* docs,
+                   int P, int K, int N, uint32_t* bitmap, long ldb, int B, int Lq, int nprobe, void* stream);
+int polus_ivf_compact(const uint32_t* bitmap, long ldb, int B, int N, int32_t* cand, long ldc, int cap, int32_t* count,
+                      void* stream);
 
 /* ---- learned sparse retrieval, SPLADE (splade.hip; no counterpart in the reference, whose first stages are dense).
  * A text becomes one non-negative vector over the vocabulary, rep[v] = max over its valid tokens s of

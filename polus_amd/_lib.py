@@ -100,6 +100,12 @@ SIGNATURES = {
     "polus_centroid_scores": (_i, [_vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _vp]),
     "polus_centroid_codes": (_i, [_vp, _l, _vp, _vp, _i, _i, _vp]),
     "polus_centroid_update": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "polus_centroid_scores_ids": (_i, [_vp, _l, _vp, _vp, _vp, _l, _vp, _l, _i, _i, _i, _i, _i, _i, _vp]),
+    "polus_ivf_count": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "polus_ivf_offsets": (_i, [_vp, _i, _vp, _vp]),
+    "polus_ivf_fill": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "polus_ivf_mark": (_i, [_vp, _l, _vp, _vp, _vp, _i, _i, _i, _vp, _l, _i, _i, _i, _vp]),
+    "polus_ivf_compact": (_i, [_vp, _l, _i, _i, _vp, _l, _i, _vp, _vp]),
     "polus_splade_pool_fwd": (_i, [_i, _vp, _l, _vp, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _vp]),
     "polus_splade_pool_bwd": (_i, [_i, _vp, _l, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _vp]),
     "polus_flops_reg_workspace_bytes": (_sz, [_i]),

@@ -22,6 +22,8 @@
 //                 LDS bytes = (K + 1) * Lq * 4, route taken iff that is <= 160 KiB (K <= 1279 at Lq = 32).
 //   global route: 4 waves, the same loop with the rows read from global memory (L2 / Infinity Cache in practice);
 //                 an absent code reads nothing.
+// polus_centroid_scores_ids: the same kernel with the document of a column read from a candidate list (ivf.hip makes
+// the lists); a pair's bits are those of polus_centroid_scores.
 // polus_centroid_codes: one wave per row of a similarity matrix, 16-byte reads, the first maximum wins.
 // polus_centroid_update: one workgroup per centroid sums its tokens in a fixed order and normalises.
 #include <algorithm>
@@ -65,12 +67,16 @@ __device__ __forceinline__ float cs_fetch(const float* cs_rows, const float* tq,
 // issued before the first maximum is taken, so that a wave has UN * RM reads in flight, not one; a group may run past
 // the last step: the lanes behind it hold absent codes (-inf), or, by wrap-around, tokens already seen (a max is
 // idempotent).
-template <int MODE, int RM, bool LDS>
+// IDS (polus_centroid_scores_ids): the launch has N columns per query and column n is document cand[b, n] of a corpus of
+// `docs` documents; an id outside [0, docs) stores -inf and reads nothing.  Everything behind the document's address is
+// the code of the other instantiation, so a pair has the same bits from either.
+template <int MODE, int RM, bool LDS, bool IDS>
 __global__ __launch_bounds__(CS_LDS_THREADS) void centroid_scores_kernel(const float* __restrict__ table, long ldt,
                                                                          const int32_t* __restrict__ qmask,
                                                                          const uint16_t* __restrict__ codes,
-                                                                         float* __restrict__ score, long lds, int N,
-                                                                         int Lq, int Ld, int K, int dpb) {
+                                                                         const int32_t* __restrict__ cand, long ldc,
+                                                                         int docs, float* __restrict__ score, long lds,
+                                                                         int N, int Lq, int Ld, int K, int dpb) {
     extern __shared__ float cs_rows[];                        // LDS route: [K + 1, Lq]
     constexpr int UN = MODE == 0 ? (RM >= 4 ? 2 : 8 / RM) : (MODE == 1 ? 8 : 4);
     const int lane = threadIdx.x & 63;
@@ -105,7 +111,15 @@ __global__ __launch_bounds__(CS_LDS_THREADS) void centroid_scores_kernel(const f
     }
 
     for (int n = n0 + wave; n < n1; n += nw) {
-        const uint16_t* cn = codes + (size_t)n * Ld;
+        int d = n;
+        if constexpr (IDS) {
+            d = __builtin_amdgcn_readfirstlane(cand[(size_t)b * ldc + n]);
+            if (d < 0 || d >= docs) {                         // uniform
+                if (lane == 0) score[(size_t)b * lds + n] = -INFINITY;
+                continue;
+            }
+        }
+        const uint16_t* cn = codes + (size_t)d * Ld;
         float m[RM];
 #pragma unroll
         for (int r = 0; r < RM; ++r) m[r] = -INFINITY;
@@ -161,23 +175,37 @@ __global__ __launch_bounds__(CS_LDS_THREADS) void centroid_scores_kernel(const f
     }
 }
 
-template <int MODE, int RM>
-int cs_launch(const float* table, long ldt, const int32_t* qmask, const uint16_t* codes, float* score, long lds, int B,
-              int N, int Lq, int Ld, int K, hipStream_t st) {
-    const char* what = "polus_centroid_scores";
+// N = the columns of the launch: documents 0 .. N, or with IDS the candidates per query out of `docs` documents.
+template <int MODE, int RM, bool IDS>
+int cs_launch(const float* table, long ldt, const int32_t* qmask, const uint16_t* codes, const int32_t* cand, long ldc,
+              int docs, float* score, long lds, int B, int N, int Lq, int Ld, int K, hipStream_t st) {
+    const char* what = IDS ? "polus_centroid_scores_ids" : "polus_centroid_scores";
     if (cs_lds_route(Lq, K)) {
         const int dpb = cs_docs_per_block(B, N, CS_LDS_THREADS / 64);
         dim3 grid((unsigned)((N + dpb - 1) / dpb), (unsigned)B);
-        return polus_launch_lds<centroid_scores_kernel<MODE, RM, true>>(what, grid, dim3(CS_LDS_THREADS), CS_LDS_MAX,
-                                                                        cs_lds_bytes(Lq, K), st, table, ldt, qmask, codes,
-                                                                        score, lds, N, Lq, Ld, K, dpb);
+        return polus_launch_lds<centroid_scores_kernel<MODE, RM, true, IDS>>(what, grid, dim3(CS_LDS_THREADS), CS_LDS_MAX,
+                                                                             cs_lds_bytes(Lq, K), st, table, ldt, qmask,
+                                                                             codes, cand, ldc, docs, score, lds, N, Lq, Ld,
+                                                                             K, dpb);
     }
     const int dpb = cs_docs_per_block(B, N, CS_GLB_THREADS / 64);
     dim3 grid((unsigned)((N + dpb - 1) / dpb), (unsigned)B);
-    hipLaunchKernelGGL((centroid_scores_kernel<MODE, RM, false>), grid, dim3(CS_GLB_THREADS), 0, st, table, ldt, qmask,
-                       codes, score, lds, N, Lq, Ld, K, dpb);
+    hipLaunchKernelGGL((centroid_scores_kernel<MODE, RM, false, IDS>), grid, dim3(CS_GLB_THREADS), 0, st, table, ldt, qmask,
+                       codes, cand, ldc, docs, score, lds, N, Lq, Ld, K, dpb);
     POLUS_CHECK_LAUNCH(what);
     return POLUS_OK;
+}
+
+template <bool IDS>
+int cs_dispatch(const float* table, long ldt, const int32_t* qmask, const uint16_t* codes, const int32_t* cand, long ldc,
+                int docs, float* score, long lds, int B, int N, int Lq, int Ld, int K, hipStream_t st) {
+    if (cs_mode(Lq) == 1) return cs_launch<1, 1, IDS>(table, ldt, qmask, codes, cand, ldc, docs, score, lds, B, N, Lq, Ld, K, st);
+    if (cs_mode(Lq) == 2) return cs_launch<2, 1, IDS>(table, ldt, qmask, codes, cand, ldc, docs, score, lds, B, N, Lq, Ld, K, st);
+    const int R = (Lq + 63) / 64;
+    if (R == 1) return cs_launch<0, 1, IDS>(table, ldt, qmask, codes, cand, ldc, docs, score, lds, B, N, Lq, Ld, K, st);
+    if (R == 2) return cs_launch<0, 2, IDS>(table, ldt, qmask, codes, cand, ldc, docs, score, lds, B, N, Lq, Ld, K, st);
+    if (R <= 4) return cs_launch<0, 4, IDS>(table, ldt, qmask, codes, cand, ldc, docs, score, lds, B, N, Lq, Ld, K, st);
+    return cs_launch<0, 8, IDS>(table, ldt, qmask, codes, cand, ldc, docs, score, lds, B, N, Lq, Ld, K, st);
 }
 
 // ---------------------------------------------------------------- nearest centroid of each row
@@ -295,14 +323,26 @@ extern "C" int polus_centroid_scores(const float* table, long ldt, const int32_t
     POLUS_REQUIRE(ldt >= (long)B * Lq, "%s: table row stride ldt must be >= B*Lq (got %ld < %ld)", what, ldt, (long)B * Lq);
     POLUS_REQUIRE(lds >= N, "%s: score row stride lds must be >= N (got %ld < %d)", what, lds, N);
     POLUS_REQUIRE(table && codes && score, "%s: null pointer", what);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (cs_mode(Lq) == 1) return cs_launch<1, 1>(table, ldt, qmask, codes, score, lds, B, N, Lq, Ld, K, st);
-    if (cs_mode(Lq) == 2) return cs_launch<2, 1>(table, ldt, qmask, codes, score, lds, B, N, Lq, Ld, K, st);
-    const int R = (Lq + 63) / 64;
-    if (R == 1) return cs_launch<0, 1>(table, ldt, qmask, codes, score, lds, B, N, Lq, Ld, K, st);
-    if (R == 2) return cs_launch<0, 2>(table, ldt, qmask, codes, score, lds, B, N, Lq, Ld, K, st);
-    if (R <= 4) return cs_launch<0, 4>(table, ldt, qmask, codes, score, lds, B, N, Lq, Ld, K, st);
-    return cs_launch<0, 8>(table, ldt, qmask, codes, score, lds, B, N, Lq, Ld, K, st);
+    return cs_dispatch<false>(table, ldt, qmask, codes, nullptr, 0, N, score, lds, B, N, Lq, Ld, K,
+                              static_cast<hipStream_t>(stream));
+}
+
+extern "C" int polus_centroid_scores_ids(const float* table, long ldt, const int32_t* qmask, const uint16_t* codes,
+                                         const int32_t* cand, long ldc, float* score, long lds, int B, int C, int N, int Lq,
+                                         int Ld, int K, void* stream) {
+    const char* what = "polus_centroid_scores_ids";
+    POLUS_REQUIRE(Lq >= 1 && Lq <= CS_LMAX, "%s: need 1 <= Lq <= %d (got %d)", what, CS_LMAX, Lq);
+    POLUS_REQUIRE(Ld >= 1 && Ld <= CS_LMAX, "%s: need 1 <= Ld <= %d (got %d)", what, CS_LMAX, Ld);
+    POLUS_REQUIRE(K >= 1 && K <= CS_KMAX, "%s: need 1 <= K <= %d (got %d)", what, CS_KMAX, K);
+    POLUS_REQUIRE(B >= 1 && B <= 65535, "%s: need 1 <= B <= 65535 (got %d)", what, B);
+    POLUS_REQUIRE(C >= 1 && C <= 65535, "%s: need 1 <= C <= 65535 (got %d)", what, C);
+    POLUS_REQUIRE(N >= 1, "%s: need N >= 1 (got %d)", what, N);
+    POLUS_REQUIRE(ldt >= (long)B * Lq, "%s: table row stride ldt must be >= B*Lq (got %ld < %ld)", what, ldt, (long)B * Lq);
+    POLUS_REQUIRE(ldc >= C, "%s: candidate row stride ldc must be >= C (got %ld < %d)", what, ldc, C);
+    POLUS_REQUIRE(lds >= C, "%s: score row stride lds must be >= C (got %ld < %d)", what, lds, C);
+    POLUS_REQUIRE(table && codes && cand && score, "%s: null pointer", what);
+    return cs_dispatch<true>(table, ldt, qmask, codes, cand, ldc, N, score, lds, B, C, Lq, Ld, K,
+                             static_cast<hipStream_t>(stream));
 }
 
 extern "C" int polus_centroid_codes(const float* sim, long lds, const int32_t* mask, uint16_t* codes, int rows, int K,

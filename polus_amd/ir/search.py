@@ -32,6 +32,18 @@ What is approximate: WHICH documents get scored; a document the look-up score ra
 seen, however good its exact score.  How often that happens (recall against `search`) depends on K, `candidates`
 and the data; it has not been measured on a real collection.  With candidates >= len(index) the result is `search`'s.
 
+That search still computes the look-up score of every stored document.  With `nprobe` it does not: inverted lists
+(centroid -> the documents holding a token of it; built on first use, rebuilt after `add` or new centroids) name the
+documents worth scoring, those sharing a centroid with the `nprobe` nearest centroids of some query token, and the
+look-up scores are computed for them alone (ops.ivf_* and ops.centroid_scores_ids), with the bits the scan gives them.
+
+    scores, ids = index.search_pruned(queries, k=100, candidates=1000, nprobe=4)
+    probes, cand, count = index.probe(queries, nprobe=4)          # the candidates alone, e.g. for a cross-encoder
+
+A document without a present token is in no list, so `nprobe` never returns it (the scan ranks it with score 0.0); with
+nprobe = K and no such document the result is the scan's, bit for bit.  Not measured: probed search beyond the
+benchmark's 40 000 documents, and recall on a real collection.
+
 With centroids a token index can drop the full vectors altogether (ColBERTv2's residual compression): a token is stored
 as its centroid's 16-bit id plus nbits = 1, 2 or 4 bits per dimension naming a bucket of its residual, 2 + E * nbits / 8
 bytes beside the int32 mask: 38 at E = 128 and nbits = 2, against 260 in bf16 and 136 in FP8.
@@ -42,12 +54,14 @@ bytes beside the int32 mask: 38 at E = 128 and nbits = 2, against 260 in bf16 an
 
 `rerank`, `search_pruned` and TwoStageSearch score the compressed tokens directly (ops.maxsim_rerank_res decodes
 centroid + bucket weight in registers), bit for bit what a plain index holding the decoded vectors returns; `search`
-decodes a chunk at a time into scratch and runs ops.maxsim_scores (a pruned search never scans, so there is no
-exhaustive kernel over residual bits).  All of the error is the quantiser's.  Recall and score error of 1-, 2- and 4-bit
+decodes a chunk at a time into scratch and runs ops.maxsim_scores (a pruned search never touches the residual bits of
+a document it does not rerank, and with `nprobe` not even its codes, so there is no exhaustive kernel over residual
+bits).  All of the error is the quantiser's.  Recall and score error of 1-, 2- and 4-bit
 residuals have not been measured on any real collection here.
 
 As in ir/training.py, arithmetic is hand-written HIP (ops.gemm / ops.maxsim_scores / ops.maxsim_rerank,
-ops.l2norm_fwd, ops.topk_merge, ops.centroid_scores / centroid_codes / centroid_update, ops.residual_compress /
+ops.l2norm_fwd, ops.topk_merge, ops.centroid_scores / centroid_scores_ids / centroid_codes / centroid_update,
+ops.ivf_count / ivf_offsets / ivf_fill / ivf_mark / ivf_compact, ops.residual_compress /
 residual_decompress / maxsim_rerank_res); torch allocates, views and copies.  Data parallelism: every rank holds the whole
 index and searches its own shard of the queries; ValidationDataCallback gathers the predictions."""
 import numpy as np
@@ -127,6 +141,7 @@ class CorpusIndex:
         self._reps = self._mask = self._scale = None
         self._codes = self._centroids = None          # centroid codes int16 [cap, Ld] and centroids [K, E]
         self._cutoffs = self._weights = None          # a residual index: the codec's tables on the device
+        self._lists, self._lists_stale = None, False  # inverted lists (offsets, docs) of refresh_lists
         self._n = 0
         self.tokens = None            # True: token representations; fixed by the first add
 
@@ -187,9 +202,10 @@ class CorpusIndex:
 
     @property
     def nbytes(self):
-        """Bytes of the stored representations, scales, mask and centroid codes of the len(index) documents."""
+        """Bytes of the stored representations, scales, mask and centroid codes of the len(index) documents, and of
+        the inverted lists once a probed search has built them (4 (K + 1) + 4 P)."""
         return sum(t[:self._n].numel() * t.element_size() for t in (self._reps, self._scale, self._mask, self._codes)
-                   if t is not None)
+                   if t is not None) + sum(t.numel() * t.element_size() for t in self._lists or ())
 
     @property
     def mask(self):
@@ -284,6 +300,7 @@ class CorpusIndex:
     def _ids(self, n, dev):
         ids = torch.arange(self._n, self._n + n, dtype=torch.int32, device=dev)
         self._n += n
+        self._lists_stale = True
         return ids
 
     def _add_residual(self, v, m):
@@ -348,7 +365,7 @@ class CorpusIndex:
         scratch = torch.empty((Q, max(b - a for a, b in spans)), dtype=torch.float32, device=qv.device)
         top_val = torch.empty((Q, int(k)), dtype=torch.float32, device=qv.device)
         top_id = torch.empty((Q, int(k)), dtype=torch.int32, device=qv.device)
-        if res:       # no exhaustive kernel over residual bits (a pruned search never scans): decode, then the plain one
+        if res:       # no exhaustive kernel over residual bits (search_pruned never reads them in bulk): decode, then the plain one
             dec = torch.empty((max(b - a for a, b in spans), self._ld, qv.shape[2]), dtype=self._dtype, device=qv.device)
         for a, b in spans:
             s = scratch[:, :b - a]
@@ -490,6 +507,7 @@ class CorpusIndex:
         self._centroids = c.to(device=self._reps.device, dtype=self._token_dtype()).contiguous().clone()
         self._codes = torch.full((self._reps.shape[0], self._ld), -1, dtype=torch.int16, device=self._reps.device)
         self._assign(0, self._n)
+        self._lists_stale = True
 
     def fit_centroids(self, K, iters=4, sample=1 << 18, seed=0):
         """Spherical k-means on the device over a sample of the stored tokens, then set_centroids.
@@ -568,12 +586,20 @@ class CorpusIndex:
         weights = np.quantile(flat64, (np.arange(n) + 0.5) / n, method="linear").astype(np.float32)
         return ResidualCodec(self._centroids.clone(), cutoffs, weights, nbits)
 
-    def search_pruned(self, queries, k, candidates):
+    def search_pruned(self, queries, k, candidates, nprobe=None):
         """`search` over the `candidates` documents per query that score best under the centroid approximation:
         (scores f32 [Q, k], ids int32 [Q, k]) with exactly the contract of `search`.  The returned scores are exact
         MaxSim scores, bit for bit what `search` gives those documents; which documents are scored is approximate
         (see the module docstring).  One GEMM builds the table <centroid, query token>, ops.centroid_scores and
-        ops.topk_merge keep the best `candidates` per chunk of documents, and the rerank path scores them."""
+        ops.topk_merge keep the best `candidates` per chunk of documents, and the rerank path scores them.
+
+        nprobe=None: the look-up score of every stored document is computed (a scan, linear in the corpus).
+        1 <= nprobe <= min(K, 1024): only the documents holding at least one token whose centroid is among the
+        `nprobe` nearest of at least one valid query token are considered (PLAID's candidate generation: the inverted
+        lists of `refresh_lists`, ops.ivf_mark / ivf_compact, then ops.centroid_scores_ids, which gives a pair the
+        look-up score bits of the scan).  A document without any present token is in no list and never a candidate
+        here, while under the scan it scores 0.0 and is ranked.  With nprobe = K every non-empty document is
+        considered: on a corpus whose documents all have a present token the result is the scan's, bit for bit."""
         if self._n == 0:
             raise ValueError("the index is empty: add documents before searching")
         if self._centroids is None:
@@ -581,20 +607,144 @@ class CorpusIndex:
         if not 1 <= int(candidates) <= MAX_K:
             raise ValueError(f"need 1 <= candidates <= {MAX_K}, the limit of ops.topk_merge, which keeps the candidates "
                              f"(got {candidates})")
+        if nprobe is not None:
+            self._check_nprobe(nprobe)
+            self._fresh_lists()
         q = self.encode_queries(queries)
         qv = q.values
         Q, Lq, E = qv.shape
         table = torch.empty((self._centroids.shape[0], Q * Lq), dtype=torch.float32, device=qv.device)
         ops.gemm(self._centroids, qv.view(Q * Lq, E), table)
-        spans = self.chunks(Q)
-        scratch = torch.empty((Q, max(b - a for a, b in spans)), dtype=torch.float32, device=qv.device)
         cand_val = torch.empty((Q, int(candidates)), dtype=torch.float32, device=qv.device)
         cand_id = torch.empty((Q, int(candidates)), dtype=torch.int32, device=qv.device)
+        if nprobe is not None:
+            self._score_probed(q, table, int(nprobe), cand_val, cand_id)
+            return self._rerank_encoded(q, cand_id, k)
+        spans = self.chunks(Q)
+        scratch = torch.empty((Q, max(b - a for a, b in spans)), dtype=torch.float32, device=qv.device)
         for a, b in spans:
             s = scratch[:, :b - a]
             ops.centroid_scores(table, q.mask, self._codes[a:b], s, Q, Lq)
             ops.topk_merge(s, cand_val, cand_id, id0=a, init=(a == 0))
         return self._rerank_encoded(q, cand_id, k)
+
+    # ------------------------------------------------------------ inverted lists and probed candidates
+    def refresh_lists(self):
+        """Build the inverted lists from the codes of all stored documents (ops.ivf_count / ivf_offsets / ivf_fill):
+        offsets int32 [K + 1] and docs int32 [P], docs[offsets[c] : offsets[c + 1]] the documents holding a present
+        token of centroid c, each once, in no specified order.  One int (P) is copied to the host to size `docs`.
+        `add`, `set_centroids` and `fit_centroids` only mark the lists stale; a search with `nprobe`, `probe` and
+        `lists` call this when they are."""
+        if self._n == 0:
+            raise ValueError("the index is empty: add documents before building the lists")
+        if self._centroids is None:
+            raise ValueError("refresh_lists needs centroids: call fit_centroids or set_centroids first")
+        K, dev = self._centroids.shape[0], self._codes.device
+        codes = self._codes[:self._n]
+        counts = torch.empty((K,), dtype=torch.int32, device=dev)
+        offsets = torch.empty((K + 1,), dtype=torch.int32, device=dev)
+        ops.ivf_count(codes, K, counts)
+        ops.ivf_offsets(counts, offsets)
+        P = int(offsets[K:].cpu()[0])
+        if P < 0:
+            raise ValueError("the lists would hold 2^31 or more (centroid, document) pairs, more than an int32 offset "
+                             "addresses: shard the corpus")
+        docs = torch.empty((P,), dtype=torch.int32, device=dev)
+        ops.ivf_fill(codes, offsets, counts, docs)            # counts serves as the cursors
+        self._lists, self._lists_stale = (offsets, docs), False
+
+    def _fresh_lists(self):
+        if self._lists is None or self._lists_stale:
+            self.refresh_lists()
+
+    @property
+    def lists(self):
+        """(offsets int32 [K + 1], docs int32 [P]) on the device, brought up to date first (refresh_lists); None on
+        an index without documents or centroids."""
+        if self._n == 0 or self._centroids is None:
+            return None
+        self._fresh_lists()
+        return self._lists
+
+    def _check_nprobe(self, nprobe):
+        most = min(self._centroids.shape[0], MAX_K)
+        if not 1 <= int(nprobe) <= most:
+            raise ValueError(f"need 1 <= nprobe <= min(K, {MAX_K}) = {most}, the centroids there are and the limit of "
+                             f"ops.topk_merge, which keeps the probes (got {nprobe})")
+
+    def _mark_probed(self, q, nprobe):
+        """(probes int32 [Q * Lq, nprobe], bitmap int32 [Q, ceil(N / 32)], count int32 [Q]) on the device for
+        encode_queries' TokenReps: each query token's nprobe nearest centroids (ops.gemm + ops.topk_merge: similarity
+        descending, ties to the lower centroid; the queries in chunks whose [rows, K] f32 similarities stay within
+        scratch_bytes), the union of their lists as one bitmap row per query (ops.ivf_mark; masked query tokens probe
+        nothing) and its number of set bits (ops.ivf_compact)."""
+        qv = q.values
+        Q, Lq, E = qv.shape
+        K, dev = self._centroids.shape[0], qv.device
+        per = min(Q, self.scratch_bytes // (4 * Lq * K))
+        if per < 1:
+            raise ValueError(f"scratch_bytes = {self.scratch_bytes} does not hold one query's similarities to {K} "
+                             f"centroids ({4 * Lq * K} bytes)")
+        flat = qv.view(Q * Lq, E)
+        probes = torch.empty((Q * Lq, nprobe), dtype=torch.int32, device=dev)
+        val = torch.empty((per * Lq, nprobe), dtype=torch.float32, device=dev)
+        sim = torch.empty((per * Lq, K), dtype=torch.float32, device=dev)
+        for a in range(0, Q * Lq, per * Lq):
+            b = min(a + per * Lq, Q * Lq)
+            ops.gemm(flat[a:b], self._centroids, sim[:b - a])
+            ops.topk_merge(sim[:b - a], val[:b - a], probes[a:b], init=True)
+        offsets, docs = self._lists
+        bitmap = torch.empty((Q, (self._n + 31) // 32), dtype=torch.int32, device=dev)
+        count = torch.empty((Q,), dtype=torch.int32, device=dev)
+        ops.ivf_mark(probes, q.mask, offsets, docs, self._n, bitmap, Q, Lq)
+        ops.ivf_compact(bitmap, self._n, count)
+        return probes, bitmap, count
+
+    def probe(self, queries, nprobe):
+        """The candidate generation of `search_pruned(..., nprobe)` on its own: (probes int32 [Q, Lq, nprobe], cand
+        int32 [Q, M], count int32 [Q]) on the device.  probes[q, i] are the nprobe centroids nearest to query token
+        i (computed for masked tokens too, which then probe nothing); cand[q, :count[q]] are, in ascending order, the
+        documents holding a token of a centroid probed by a valid token of query q, the rest of the row is -1;
+        M = max(1, max count).  `cand` can go to `rerank`, or to another index holding the same documents."""
+        if self._n == 0:
+            raise ValueError("the index is empty: add documents before probing")
+        if self._centroids is None:
+            raise ValueError("probe needs centroids: call fit_centroids or set_centroids first")
+        self._check_nprobe(nprobe)
+        self._fresh_lists()
+        q = self.encode_queries(queries)
+        Q, Lq = q.values.shape[:2]
+        probes, bitmap, count = self._mark_probed(q, int(nprobe))
+        cand = torch.empty((Q, max(1, int(count.cpu().max()))), dtype=torch.int32, device=count.device)
+        ops.ivf_compact(bitmap, self._n, count, cand)
+        return probes.view(Q, Lq, int(nprobe)), cand, count
+
+    def _score_probed(self, q, table, nprobe, cand_val, cand_id):
+        """The candidate stage of search_pruned under `nprobe`: the look-up scores of each query's probed documents
+        only (ops.centroid_scores_ids: the bits the scan gives those pairs) merged into cand_val / cand_id.  The
+        queries' candidate counts come to the host in one copy; the queries are taken in consecutive groups whose
+        [group, largest count] int32 candidate buffer stays within scratch_bytes."""
+        Q, Lq = q.values.shape[:2]
+        _, bitmap, count = self._mark_probed(q, nprobe)
+        counts = np.maximum(count.cpu().numpy(), 1)           # a query without a candidate: one column of -1
+        if 4 * int(counts.max()) > self.scratch_bytes:
+            raise ValueError(f"scratch_bytes = {self.scratch_bytes} does not hold the {int(counts.max())} candidates "
+                             f"of one query ({4 * int(counts.max())} bytes)")
+        codes = self._codes[:self._n]
+        a = 0
+        while a < Q:
+            b, C = a + 1, int(counts[a])
+            while b < Q and 4 * (b + 1 - a) * max(C, int(counts[b])) <= self.scratch_bytes:
+                C, b = max(C, int(counts[b])), b + 1
+            cand = torch.empty((b - a, C), dtype=torch.int32, device=count.device)
+            ops.ivf_compact(bitmap[a:b], self._n, count[a:b], cand)
+            spans = self.rerank_chunks(b - a, C)
+            scratch = torch.empty((b - a, max(e - s for s, e in spans)), dtype=torch.float32, device=count.device)
+            for s, e in spans:
+                sc, c = scratch[:, :e - s], cand[:, s:e]
+                ops.centroid_scores_ids(table[:, a * Lq:], q.mask[a:b], codes, c, sc, b - a, Lq)
+                ops.topk_merge(sc, cand_val[a:b], cand_id[a:b], init=(s == 0), ids=c)
+            a = b
 
 
 class SparseCorpusIndex:
@@ -742,10 +892,16 @@ class RetrievalValidationCallback(ValidationDataCallback):
     shared_dict["validation"][name], where SaveModelCallback(strategy="best") reads them.  `storage` is the
     CorpusIndex's (None or "fp8", token representations only).  With `centroids` (a number K) the index fits that many
     centroids once the corpus is added (CorpusIndex.fit_centroids) and ranks with search_pruned over `candidates`
-    documents per query (None: 1024, the most it takes); the defaults rank with the exhaustive `search`."""
+    documents per query (None: 1024, the most it takes), with `nprobe` passed on to it (None: the scan; a number: the
+    probed candidate generation, which needs `centroids`); the defaults rank with the exhaustive `search`."""
 
     def __init__(self, corpus, tf_validation, k, name=None, validation_interval=1, show_progress=False,
-                 scratch_bytes=256 << 20, storage=None, centroids=None, candidates=None):
+                 scratch_bytes=256 << 20, storage=None, centroids=None, candidates=None, nprobe=None):
+        if nprobe is not None and centroids is None:
+            raise ValueError("nprobe needs centroids: it probes the lists of search_pruned's centroids")
+        if nprobe is not None and int(nprobe) < 1:
+            raise ValueError(f"need nprobe >= 1 (got {nprobe})")
+        self.nprobe = None if nprobe is None else int(nprobe)
         super().__init__(tf_validation, custom_inference_f=self._rank, name=name, show_progress=show_progress,
                          validation_interval=validation_interval)
         self.corpus, self.k, self.scratch_bytes, self.storage = corpus, int(k), scratch_bytes, storage
@@ -756,7 +912,7 @@ class RetrievalValidationCallback(ValidationDataCallback):
     def _rank(self, model, sample):
         queries, relevant = sample
         if self.centroids is not None:
-            return self.index.search_pruned(queries, self.k, self.candidates)[1], relevant
+            return self.index.search_pruned(queries, self.k, self.candidates, self.nprobe)[1], relevant
         return self.index.search(queries, self.k)[1], relevant
 
     def on_epoch_end(self, epoch):

@@ -705,6 +705,94 @@ def centroid_update(x, codes, prev, out, counts, eps=1e-12):
                                             float(eps), _st()), "polus_centroid_update")
 
 
+def centroid_scores_ids(table, qmask, codes, cand, score, B, Lq):
+    """score[b, c] (f32, any row stride) = the bits `centroid_scores` gives the pair (b, cand[b, c]); cand int32 [B, C]
+    (any row stride), an id outside [0, N) gives -inf and reads nothing; table, qmask and codes (int16 [N, Ld]) as for
+    `centroid_scores` (include/polus_hip.h polus_centroid_scores_ids)."""
+    _req_cuda(table, qmask, codes, cand, score)
+    K = table.shape[0]
+    N, Ld = codes.shape
+    C = cand.shape[1]
+    assert table.dtype == torch.float32 and table.dim() == 2 and table.shape[1] >= B * Lq and (table.stride(1) == 1 or table.shape[1] == 1)
+    assert codes.dtype == torch.int16 and codes.is_contiguous()
+    assert cand.dtype == torch.int32 and cand.dim() == 2 and cand.shape[0] >= B and (cand.stride(1) == 1 or C == 1)
+    assert score.dtype == torch.float32 and score.dim() == 2 and score.shape[0] >= B and score.shape[1] >= C and (score.stride(1) == 1 or score.shape[1] == 1)
+    check(_lib.load().polus_centroid_scores_ids(ptr(table), table.stride(0), ptr(_maxsim_mask(qmask, B, Lq, "qmask")), ptr(codes),
+                                                ptr(cand), cand.stride(0), ptr(score), score.stride(0), int(B), C, N, int(Lq), Ld,
+                                                K, _st()), "polus_centroid_scores_ids")
+
+
+def _ivf_codes(codes, K):
+    assert codes.dtype == torch.int16 and codes.dim() == 2 and codes.is_contiguous() and 1 <= int(K) <= 65535
+    return codes.shape
+
+
+def ivf_count(codes, K, counts):
+    """counts[c] (int32 [K], zeroed here) = the documents of codes (int16 [N, Ld], the bits of the unsigned code; >= K: no
+    token) that hold at least one token coded c (include/polus_hip.h polus_ivf_count)."""
+    _req_cuda(codes, counts)
+    N, Ld = _ivf_codes(codes, K)
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == K
+    check(_lib.load().polus_ivf_count(ptr(codes), N, Ld, int(K), ptr(counts), _st()), "polus_ivf_count")
+
+
+def ivf_offsets(counts, offsets):
+    """offsets (int32 [K + 1]) = the exclusive scan of counts (int32 [K]); offsets[K] = P, the number of (centroid,
+    document) pairs, or -1 when P >= 2^31 (include/polus_hip.h polus_ivf_offsets)."""
+    _req_cuda(counts, offsets)
+    K = counts.numel()
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and offsets.dtype == torch.int32 and offsets.is_contiguous()
+    assert offsets.numel() == K + 1
+    check(_lib.load().polus_ivf_offsets(ptr(counts), K, ptr(offsets), _st()), "polus_ivf_offsets")
+
+
+def ivf_fill(codes, offsets, cursor, docs):
+    """docs[offsets[c] .. offsets[c + 1]) (int32 [P]) = the ids of the documents counted for centroid c, each once, in
+    no specified order; cursor int32 [K] is scratch (include/polus_hip.h polus_ivf_fill)."""
+    _req_cuda(codes, offsets, cursor, docs)
+    K = cursor.numel()
+    N, Ld = _ivf_codes(codes, K)
+    assert offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.numel() == K + 1
+    assert cursor.dtype == torch.int32 and cursor.is_contiguous()
+    assert docs.dtype == torch.int32 and docs.dim() == 1 and docs.is_contiguous()
+    check(_lib.load().polus_ivf_fill(ptr(codes), N, Ld, K, ptr(offsets), docs.numel(), ptr(cursor),
+                                     ptr(docs) if docs.numel() else None, _st()), "polus_ivf_fill")
+
+
+def ivf_mark(probes, qmask, offsets, docs, N, bitmap, B, Lq):
+    """bitmap (int32 [B, >= ceil(N / 32)] words, any row stride; the first ceil(N / 32) words of a row are cleared here)
+    gets bit d of row b for every document d in the list of every probe of query b: probes int32 [B * Lq, nprobe] (any
+    row stride; an id outside [0, K) is skipped), qmask int32 [B, Lq] or None, lists (offsets int32 [K + 1], docs int32
+    [P]) (include/polus_hip.h polus_ivf_mark)."""
+    _req_cuda(probes, qmask, offsets, docs, bitmap)
+    K = offsets.numel() - 1
+    nprobe = probes.shape[1]
+    assert probes.dtype == torch.int32 and probes.dim() == 2 and probes.shape[0] >= B * Lq and (probes.stride(1) == 1 or nprobe == 1)
+    assert offsets.dtype == torch.int32 and offsets.is_contiguous() and docs.dtype == torch.int32 and docs.dim() == 1 and docs.is_contiguous()
+    assert bitmap.dtype == torch.int32 and bitmap.dim() == 2 and bitmap.shape[0] >= B and (bitmap.stride(1) == 1 or bitmap.shape[1] == 1)
+    assert bitmap.shape[1] >= (int(N) + 31) // 32
+    check(_lib.load().polus_ivf_mark(ptr(probes), probes.stride(0), ptr(_maxsim_mask(qmask, B, Lq, "qmask")), ptr(offsets),
+                                     ptr(docs) if docs.numel() else None, docs.numel(), K, int(N), ptr(bitmap), bitmap.stride(0),
+                                     int(B), int(Lq), nprobe, _st()), "polus_ivf_mark")
+
+
+def ivf_compact(bitmap, N, count, cand=None):
+    """count[b] (int32 [B]) = the set bits of row b of bitmap (int32 [B, >= ceil(N / 32)] words) among bits [0, N); with
+    cand (int32 [B, cap], any row stride) its row gets the first cap set positions in ascending order, then -1
+    (include/polus_hip.h polus_ivf_compact)."""
+    _req_cuda(bitmap, count, cand)
+    B = count.numel()
+    assert bitmap.dtype == torch.int32 and bitmap.dim() == 2 and bitmap.shape[0] >= B and (bitmap.stride(1) == 1 or bitmap.shape[1] == 1)
+    assert bitmap.shape[1] >= (int(N) + 31) // 32
+    assert count.dtype == torch.int32 and count.is_contiguous()
+    cap = ldc = 0
+    if cand is not None:
+        assert cand.dtype == torch.int32 and cand.dim() == 2 and cand.shape[0] >= B and (cand.stride(1) == 1 or cand.shape[1] == 1)
+        cap, ldc = cand.shape[1], cand.stride(0)
+    check(_lib.load().polus_ivf_compact(ptr(bitmap), bitmap.stride(0), B, int(N), ptr(cand), ldc, cap, ptr(count), _st()),
+          "polus_ivf_compact")
+
+
 def _rows2d(t, dtype, rows, cols, name):
     """t is a [>= rows, >= cols] matrix of `dtype` with contiguous columns; returns a row stride that is legal for one row too."""
     assert t.dtype == dtype and t.dim() == 2 and t.shape[0] >= rows and t.shape[1] >= cols, f"{name}: need {dtype} [>= {rows}, >= {cols}], got {t.dtype} {tuple(t.shape)}"
