@@ -845,6 +845,51 @@ int polus_mine_negatives(const int32_t* cand, long ldc, const float* score, long
                          int Q, int C, int P, int skip_top, float min_score, int k, uint32_t seed, int32_t* neg,
                          int32_t* neg_col, int32_t* n_pool, void* stream);
 
+/* ---- rank fusion (fuse.hip; no counterpart in the reference): L ranked lists per query, as L searches return them,
+ * joined by document id and fused by reciprocal rank (RRF), CombSUM, or CombSUM over min-max normalised scores.
+ *   ids int32 [L, Q, C] (list stride lsi, row stride ldi);  scores f32 [L, Q, C] (lss, lds) or NULL (rrf only)
+ *   weights: a HOST array f32 [L], read during the call, or NULL = all 1.0f;  rrf_k: the constant of RRF (60 in the paper)
+ *   out_id int32 and out_val f32 [Q, L*C] (row strides ldoi, ldov);  count int32 [Q]
+ * Kept.  Entry (l, r, c) is kept iff 0 <= ids[l, r, c] < n_docs and, when scores is given, scores[l, r, c] is finite
+ *   (NaN and +-inf are dropped; -inf is how polus_maxsim_rerank marks a missing candidate).  Every other entry is skipped
+ *   and nothing is indexed by it.
+ * Rank.  rank(l, r, c) = 1 + the number of kept entries of list row (l, r) at columns below c.  A dropped entry takes no
+ *   rank.  A list is taken in the order given and never re-sorted.
+ * Contribution of a kept entry with score s and weight w = weights[l], in f32, every fl one IEEE rounding to nearest
+ *   even, the division correctly rounded, nothing contracted into an fma (as polus_bm25_weights: NumPy float32 arithmetic
+ *   gives the same bits):
+ *     mode POLUS_FUSE_RRF     fl(w / fl(rrf_k + f32(rank)))
+ *     mode POLUS_FUSE_SUM     fl(w * s)
+ *     mode POLUS_FUSE_MINMAX  fl(w * fl(fl(s - lo) / fl(hi - lo))),  lo and hi the minimum and maximum, by IEEE
+ *                             comparison, of the kept scores of list row (l, r);  hi == lo (a list row with one kept
+ *                             entry among them):  fl(w * 1.0f) for each of its kept entries.
+ *   Precondition of MINMAX: hi - lo is finite.  -0.0 equals +0.0 under IEEE comparison: where the minimum of a list row
+ *   is a zero present with both signs, which of the two is lo, and with it the sign of a zero contribution, is
+ *   unspecified.  A document absent from a list gets nothing from it (so the worst document present also gets 0: the
+ *   usual reading of CombSUM over min-max scores).
+ * Fused score of a document = its contributions added left to right in (list, column) order, the first taken as it is:
+ *   fl(fl(c_1 + c_2) + c_3) ...  A repeated id inside one list row is not detected: every copy takes its own rank and
+ *   contributes, in column order (searches return no such rows; the rule keeps the result defined).
+ * Output.  count[r] = the number of distinct kept ids of row r;  out_id[r, 0 .. count[r]) = those ids ASCENDING and
+ *   out_val[r, 0 .. count[r]) their fused scores;  columns count[r] .. L*C - 1 are (-1, -inf).  Nothing beyond column
+ *   L*C - 1 is written.  This is the candidate row polus_ivf_compact hands out and what polus_topk_merge_ids and
+ *   polus_maxsim_rerank accept (a negative id is a missing candidate there).  Ids and counts are exact, the values are
+ *   the bits of the rule above whatever Q, the grid or the device.
+ * One workgroup per query (grid-stride): every list row read once in 64-column steps (kept flags by __ballot, ranks by
+ * popcount prefix, lo / hi by wave reduction), contributions and 64-bit keys id << 13 | (l C + c) in 48 KiB of LDS, one
+ * bitonic sort of the keys, run heads found by neighbour compares add their run in order and are compacted by ballot
+ * and popcount.  No atomics, no workspace, bitwise reproducible.
+ * Limits (refused before any launch): 1 <= L <= 8; Q >= 1; C >= 1; L*C <= 4096; 1 <= n_docs <= 2^31 - 1; ldi, lds >= C;
+ *   with L > 1, lsi >= (Q - 1) ldi + C and lss >= (Q - 1) lds + C (the extent of one list); ldoi, ldov >= L*C; scores
+ *   non-null for SUM and MINMAX; rrf_k finite and >= 0 for RRF; weights finite; mode one of the three; ids, out_id,
+ *   out_val, count non-null. */
+#define POLUS_FUSE_RRF 0
+#define POLUS_FUSE_SUM 1
+#define POLUS_FUSE_MINMAX 2
+int polus_fuse_lists(const int32_t* ids, long lsi, long ldi, const float* scores, long lss, long lds, int L, int Q, int C,
+                     int n_docs, int mode, const float* weights, float rrf_k, int32_t* out_id, long ldoi, float* out_val,
+                     long ldov, int32_t* count, void* stream);
+
 /* ---- argmax over the last axis (PolusClassifier.inference, polus/models.py:148-150) */
 int polus_argmax(const float* x, long ldx, int32_t* out, int rows, int C, void* stream);
 

@@ -115,6 +115,7 @@ SIGNATURES = {
     "polus_bm25_weights": (_i, [_vp, _l, _vp, _vp, _l, _i, _i, _f, _f, _f, _vp]),
     "polus_bm25_query": (_i, [_vp, _l, _vp, _l, _vp, _vp, _l, _i, _i, _i, _vp]),
     "polus_mine_negatives": (_i, [_vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i, _f, _i, _u32, _vp, _vp, _vp, _vp]),
+    "polus_fuse_lists": (_i, [_vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _i, _c.POINTER(_f), _f, _vp, _l, _vp, _l, _vp, _vp]),
     "polus_argmax": (_i, [_vp, _l, _vp, _i, _i, _vp]),
     "polus_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64,
                              _f, _f, _f, _f, _f, _f, _f, _vp, _vp]),

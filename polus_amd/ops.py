@@ -930,6 +930,46 @@ def mine_negatives(cand, neg, n_pool, score=None, exclude=None, skip_top=0, min_
                                            ptr(n_pool), _st()), "polus_mine_negatives")
 
 
+FUSE_MODES = {"rrf": 0, "sum": 1, "minmax": 2}
+
+
+def _lists3d(t, dtype, name):
+    """t is an [L, Q, C] stack of `dtype` with contiguous columns; returns strides that are legal for one list or row too."""
+    assert t.dtype == dtype and t.dim() == 3, f"{name}: need {dtype} [L, Q, C], got {t.dtype} {tuple(t.shape)}"
+    L, Q, C = t.shape
+    assert t.stride(2) == 1 or C == 1, f"{name}: the last axis must be contiguous"
+    ldr = t.stride(1) if Q > 1 else max(t.stride(1), C)
+    return (t.stride(0) if L > 1 else max(t.stride(0), (Q - 1) * ldr + C)), ldr
+
+
+def fuse_lists(ids, scores, out_id, out_val, count, n_docs, mode, weights=None, rrf_k=60.0):
+    """Join L ranked lists per query by document id and fuse their scores.  ids int32 and scores f32 [L, Q, C] (any list
+    and row stride; scores may be None under "rrf") are the stacked results of L searches; an entry counts iff its id is
+    in [0, n_docs) and its score is finite, and its rank is its position among the entries of its list row that count.
+    mode "rrf" (or 0): w / (rrf_k + rank);  "sum" (1): w * score;  "minmax" (2): w * (score - lo) / (hi - lo) over the
+    list row's own scores; `weights` is a host sequence of L floats (None: all 1).  out_id int32 / out_val f32 [Q, L*C]
+    (any row stride) get each query's distinct ids ascending with their fused scores, then (-1, -inf); count int32 [Q]
+    how many.  Every operation is one f32 rounding and a document's contributions are added in (list, column) order
+    (include/polus_hip.h polus_fuse_lists)."""
+    _req_cuda(ids, scores, out_id, out_val, count)
+    lsi, ldi = _lists3d(ids, torch.int32, "ids")
+    L, Q, C = ids.shape
+    lss = lds = 0
+    if scores is not None:
+        assert tuple(scores.shape) == (L, Q, C), f"ids is {tuple(ids.shape)}, scores {tuple(scores.shape)}"
+        lss, lds = _lists3d(scores, torch.float32, "scores")
+    assert tuple(out_id.shape) == (Q, L * C) and tuple(out_val.shape) == (Q, L * C), "out_id, out_val: need [Q, L*C]"
+    ldoi, ldov = _rows2d(out_id, torch.int32, Q, L * C, "out_id"), _rows2d(out_val, torch.float32, Q, L * C, "out_val")
+    assert count.dtype == torch.int32 and count.is_contiguous() and count.numel() >= Q
+    w = None
+    if weights is not None:
+        assert len(weights) == L, f"{L} lists, {len(weights)} weights"
+        w = (ctypes.c_float * L)(*[float(x) for x in weights])
+    check(_lib.load().polus_fuse_lists(ptr(ids), lsi, ldi, ptr(scores), lss, lds, L, Q, C, int(n_docs),
+                                       FUSE_MODES[mode] if isinstance(mode, str) else int(mode), w, float(rrf_k), ptr(out_id), ldoi, ptr(out_val), ldov,
+                                       ptr(count), _st()), "polus_fuse_lists")
+
+
 def maxsim_bwd(q, d, dscore, argmax, dq, dd):
     """dq [B, Lq, E] and dd [N, Ld, E] from dscore (f32 [B, N], row stride free) and the forward's argmax; every
     element is written."""
