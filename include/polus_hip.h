@@ -823,6 +823,86 @@ int polus_bm25_weights(const int32_t* tf, long ldf, const int32_t* doc_len, floa
 int polus_bm25_query(const int32_t* terms, long ldt, const int32_t* tf, long ldf, const float* idf, float* q, long ldq,
                      int B, int M, int V, void* stream);
 
+/* ---- block-inverted postings and term-at-a-time search (postings.hip; no counterpart in the reference).  The inverted
+ * route of the two lexical first stages, beside the forward route above: polus_sparse_scores reads every slot of
+ * every document for every query, Q * N * M * 8 bytes; a search over postings reads only the lists of the query's
+ * terms.  It also has no limit on V beyond int32, since no dense query row has to fit in LDS.
+ *
+ * Blocks.  The N documents are cut into blocks of block_docs consecutive ids; block_docs is a power of two in
+ * [64, 32768], the last block may be partial, nblk = ceil(N / block_docs).
+ * Postings.  A posting is a triple (term t, document d, weight w) taken from a forward slot (ids[d, m], w[d, m]) of
+ * ids int32 / w f32 [N, M] (row strides ldi, ldw).  A slot is a posting iff 0 <= id < V and w != 0: a NaN weight counts,
+ * +0.0 and -0.0 do not (SPLADE's zero-weight filler slots would otherwise give the lowest term ids a list of N
+ * entries each).  PRECONDITION: the ids in one document's slots are distinct (polus_bm25_term_counts and
+ * polus_topk_merge guarantee it); with duplicates the result is unspecified, but nothing faults.
+ * Storage, per block in CSR form over the terms:
+ *   offsets  int32 [nblk, V + 1] contiguous;  offsets[b, 0] = 0;  offsets[b, V] = the block's posting count,
+ *            <= block_docs * M <= 2^25.
+ *   base     int64 [nblk + 1]: the exclusive scan of the block totals;  base[nblk] = P.  P may exceed 2^31, so every
+ *            posting index is 64-bit.
+ *   post_doc uint16 [P]: the document id local to its block, d - b * block_docs.
+ *   post_w   f32 [P]: the weight.
+ *   The list of (b, t) is the positions base[b] + offsets[b, t] .. base[b] + offsets[b, t + 1].  THE ORDER INSIDE A LIST
+ *   IS UNSPECIFIED (a posting takes the slot an atomic cursor hands it); the lists as SETS, the counts, the offsets and
+ *   the base are exact and reproducible.  Nothing downstream depends on the order (the score rule below).
+ * Query lists.  q_terms int32 [Q, cap], q_w f32 [Q, cap] (row strides ldt, ldw), q_count int32 [Q]: row q's entries
+ *   0 .. min(q_count[q], cap) are in ascending term id, the rest of the row is (-1, 0.0).
+ * THE SCORE RULE.  For query q and document d:  acc = +0.0f;  the entries j = 0 .. min(q_count[q], cap) - 1 are taken in
+ *   that order;  an entry with q_terms[q, j] outside [0, V) is skipped;  if d's block holds a posting (t, d, w) for
+ *   t = q_terms[q, j], then  acc = fl(acc + fl(q_w[q, j] * w)):  one rounding for the product and one for the sum, no
+ *   fma.  NumPy float32 arithmetic reproduces these bits.  A document with no matching term scores +0.0 (and is still
+ *   ranked, as on the forward route).  An entry whose term repeats an earlier one counts again.
+ *
+ * The caller owns every buffer; nothing is allocated here; limits are refused on the host before any launch; integer
+ * atomics are int32 vector atomics; there are NO floating-point atomics: the score rule fixes the order of the sums.
+ *
+ * polus_postings_count:   counts int32 [nblk, V] contiguous, zeroed by the call itself;  counts[b, t] = the postings of
+ *   term t in block b.  One thread per forward slot, one int32 add per posting.
+ * polus_postings_offsets: offsets[b, :] = the exclusive scan of counts[b, :] (one workgroup per block, 64-bit sums,
+ *   a negative count reads as 0), then base = the int64 exclusive scan of the block totals (one workgroup): two launches.
+ * polus_postings_fill:    cursor int32 [nblk, V] is scratch, zeroed by the call itself, meaningless afterwards (it may be
+ *   the counts buffer, which is no longer needed).  The same walk as count;  a posting takes slot = cursor[b, t]++ and
+ *   is stored at base[b] + offsets[b, t] + slot only if offsets[b, t] + slot < offsets[b, t + 1] and the position lies in
+ *   [0, P): foreign or stale offsets lose entries, they never write out of range.  P = 0 is legal (nothing is stored;
+ *   post_doc and post_w may be NULL).
+ * polus_sparse_compact_rows:  a dense row q[r, 0 .. V) (f32, row stride ldq) becomes a query list: entry v is kept iff
+ *   q[r, v] != 0 (NaN kept, +-0.0 dropped), in ascending v, with weight q[r, v].  q_count[r] = the FULL number of kept
+ *   entries even when it exceeds cap; entries past cap are dropped; the rest of the row up to cap is (-1, 0.0); nothing
+ *   past column cap - 1 is written.  One workgroup per row, __ballot and popcount prefix, no atomics.  No limit on V
+ *   beyond int32; rows need no alignment beyond 4 bytes.
+ * polus_bm25_query_lists:  terms, tf int32 [Q, M] (row strides ldt, ldf) as polus_bm25_term_counts leaves a query (distinct
+ *   ids ordered by count, -1 in unused slots);  the query list q_terms / q_w [Q, M] (row strides ldt2, ldw; cap = M) in
+ *   ascending id with weight fl(f32(tf) * idf[t]), polus_bm25_query's arithmetic;  ids outside [0, V) are dropped;
+ *   q_count[r] = the kept entries.  One workgroup per row; an entry's place is the number of kept entries with a
+ *   smaller id (of equal ids, the lower slot first), counted through LDS.  No dense [Q, V] row is made, so
+ *   polus_bm25_query's limit on V is not involved.
+ * polus_postings_scores:  one workgroup per (query, block) for the blocks blk0 .. blk0 + nblk_launch.  An f32
+ *   accumulator of block_docs entries sits in dynamic LDS (at most 128 KiB of a CU's 160) and is zeroed first; the
+ *   query's entries are walked in order; for each one the threads stride over the list of (block, term) and do a plain
+ *   load-add-store on acc[post_doc] (the documents of one list are distinct: no two threads share an address); a
+ *   barrier separates the terms (an empty list, which is uniform over the workgroup, skips it).  At the end acc goes
+ *   out coalesced:  score[q * lds + (b - blk0) * block_docs + local]  for the documents b * block_docs + local < N only.
+ *   Bounds: a list is clamped to positions [0, P) before it is read; a local id >= the documents of its block is not
+ *   accumulated; so stale or foreign postings cannot fault or write outside the row.
+ * Limits (refused before any launch): N >= 1; 1 <= M <= 1024; 1 <= V < 2^31 - 1; block_docs a power of two in
+ * [64, 32768]; nblk >= 1; P >= 0; Q >= 1; cap >= 1; 0 <= blk0, nblk_launch >= 1, blk0 + nblk_launch <= nblk;
+ * Q * nblk_launch < 2^31; ldi, ldw >= M; ldq >= V; list row strides >= cap (>= M for polus_bm25_query_lists);
+ * lds >= the documents of the launch; non-null pointers (post_doc and post_w may be NULL when P = 0). */
+int polus_postings_count(const int32_t* ids, long ldi, const float* w, long ldw, int N, int M, int V, int block_docs,
+                         int32_t* counts, void* stream);
+int polus_postings_offsets(const int32_t* counts, int nblk, int V, int32_t* offsets, int64_t* base, void* stream);
+int polus_postings_fill(const int32_t* ids, long ldi, const float* w, long ldw, int N, int M, int V, int block_docs,
+                        const int32_t* offsets, const int64_t* base, long P, int32_t* cursor, uint16_t* post_doc,
+                        float* post_w, void* stream);
+int polus_sparse_compact_rows(const float* q, long ldq, int Q, int V, int cap, int32_t* q_terms, long ldt, float* q_w,
+                              long ldw, int32_t* q_count, void* stream);
+int polus_bm25_query_lists(const int32_t* terms, long ldt, const int32_t* tf, long ldf, const float* idf, int Q, int M,
+                           int V, int32_t* q_terms, long ldt2, float* q_w, long ldw, int32_t* q_count, void* stream);
+int polus_postings_scores(const int32_t* q_terms, long ldt, const float* q_w, long ldw, const int32_t* q_count, int cap,
+                          const int32_t* offsets, const int64_t* base, const uint16_t* post_doc, const float* post_w,
+                          long P, int V, int block_docs, int blk0, int nblk_launch, int N, float* score, long lds, int Q,
+                          void* stream);
+
 /* ---- hard-negative mining (mine.hip): k negatives per query sampled from a ranked candidate list, the step between a
  * first-stage search and the (question, positive, negatives) tuples of the trainers.  Integers only: exact.
  *   cand int32 [Q, C] (row stride ldc), in rank order, ids distinct within a row (as a search returns them)

@@ -114,6 +114,12 @@ SIGNATURES = {
     "polus_bm25_term_counts": (_i, [_vp, _l, _vp, _l, _i, _i, _i, _i, _i, _vp, _l, _vp, _l, _i, _vp, _vp, _vp, _vp]),
     "polus_bm25_weights": (_i, [_vp, _l, _vp, _vp, _l, _i, _i, _f, _f, _f, _vp]),
     "polus_bm25_query": (_i, [_vp, _l, _vp, _l, _vp, _vp, _l, _i, _i, _i, _vp]),
+    "polus_postings_count": (_i, [_vp, _l, _vp, _l, _i, _i, _i, _i, _vp, _vp]),
+    "polus_postings_offsets": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "polus_postings_fill": (_i, [_vp, _l, _vp, _l, _i, _i, _i, _i, _vp, _vp, _l, _vp, _vp, _vp, _vp]),
+    "polus_sparse_compact_rows": (_i, [_vp, _l, _i, _i, _i, _vp, _l, _vp, _l, _vp, _vp]),
+    "polus_bm25_query_lists": (_i, [_vp, _l, _vp, _l, _vp, _i, _i, _i, _vp, _l, _vp, _l, _vp, _vp]),
+    "polus_postings_scores": (_i, [_vp, _l, _vp, _l, _vp, _i, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _vp, _l, _i, _vp]),
     "polus_mine_negatives": (_i, [_vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i, _f, _i, _u32, _vp, _vp, _vp, _vp]),
     "polus_fuse_lists": (_i, [_vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _i, _c.POINTER(_f), _f, _vp, _l, _vp, _l, _vp, _vp]),
     "polus_argmax": (_i, [_vp, _l, _vp, _i, _i, _vp]),

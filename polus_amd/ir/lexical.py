@@ -29,16 +29,31 @@ Queries are counted by the same kernel (without df), turned into dense f32 [Q, V
 `search` is the chunk loop of SparseCorpusIndex.search over ops.sparse_scores and ops.topk_merge: its scores are the
 bits polus_sparse_scores gives for (q, terms, w), in slot order.
 
+Postings.  That search reads every slot of every document for every query.  `BM25Index(vocab_size, postings=True,
+block_docs=...)` searches block-inverted postings instead (polus_amd/ir/postings.py has the format and the score rule):
+
+    index = BM25Index(vocab_size=119547, postings=True)   # no dense query row: the vocabulary is bounded by int32 only
+    scores, ids = index.search(queries, k=1000)           # refresh, then refresh_postings, when stale
+
+`add` and `set_params` only mark the postings stale; `refresh_postings` rebuilds them from the stored (term id, weight)
+slots after a `refresh` (the weights change with N); queries are counted as before and become lists of (term, tf_q idf)
+in ascending id (ops.bm25_query_lists; no dense row, no synchronisation), and `search` is a chunk loop over
+ops.postings_scores and ops.topk_merge, whole blocks per launch.  The contract of `search` is the same; the scores are
+the bits of the postings score rule (products and sums in ascending term id, each rounded once), which differ from the
+forward route's fma chain in slot order by rounding.  The forward route is the default and keeps its bits.
+
 Tokens are the wordpieces of whatever tokeniser made the ids, which is known to cost some quality against word-level
 BM25 with stemming and stop words.  Not measured: retrieval quality on any real collection.
 
-Arithmetic is hand-written HIP (ops.bm25_term_counts / bm25_weights / bm25_query / sparse_scores / topk_merge) except
+Arithmetic is hand-written HIP (ops.bm25_term_counts / bm25_weights / bm25_query / sparse_scores / topk_merge, and on
+the postings route ops.postings_count / postings_offsets / postings_fill / bm25_query_lists / postings_scores) except
 the V idf values of a refresh, which are NumPy float64 on the host; torch allocates, views and copies."""
 import numpy as np
 import torch
 
 from .. import ops
 from ..tensor import device, to_device
+from .postings import MAX_POSTINGS_VOCAB, Postings, check_block_docs
 
 MAX_CHUNK = 65535             # documents per launch, as in polus_amd/ir/search.py
 MAX_TERMS = 1024              # slots per document: what ops.sparse_scores accepts
@@ -67,11 +82,19 @@ class BM25Index:
     `vocab_size` bounds the ids (a token outside [0, vocab_size) is dropped and counted in `rejected`); `terms` is the
     number of slots per document (None: min(width of the first batch, 1024)); `strip` = (head, tail) valid tokens taken
     off every document and query row, (1, 1) for the [CLS] and [SEP] of HF-tokenised inputs, (0, 0) for raw ids;
-    `scratch_bytes` bounds the [Q, n] f32 score buffer of one chunk of a search."""
+    `scratch_bytes` bounds the [Q, n] f32 score buffer of one chunk of a search.  `postings=True` searches block-inverted
+    postings of `block_docs` documents per block instead of the forward slots (polus_amd/ir/postings.py) and lifts the
+    limit on `vocab_size`; the default is the forward route, unchanged."""
 
-    def __init__(self, vocab_size, terms=None, k1=0.9, b=0.4, strip=(1, 1), scratch_bytes=256 << 20):
+    def __init__(self, vocab_size, terms=None, k1=0.9, b=0.4, strip=(1, 1), scratch_bytes=256 << 20, postings=False,
+                 block_docs=8192):
         V = int(vocab_size)
-        if not 1 <= V <= MAX_VOCAB:
+        self._postings = Postings(block_docs) if postings else None
+        self.block_docs = check_block_docs(block_docs)
+        if postings:
+            if not 1 <= V <= MAX_POSTINGS_VOCAB:
+                raise ValueError(f"need 1 <= vocab_size <= {MAX_POSTINGS_VOCAB} (got {vocab_size})")
+        elif not 1 <= V <= MAX_VOCAB:
             raise ValueError(f"need 1 <= vocab_size <= {MAX_VOCAB}, the query row ops.sparse_scores holds in LDS (got {vocab_size})")
         if terms is not None and not 1 <= int(terms) <= MAX_TERMS:
             raise ValueError(f"need 1 <= terms <= {MAX_TERMS}, what ops.sparse_scores accepts (got {terms})")
@@ -93,6 +116,9 @@ class BM25Index:
         """Empty the index (the storage and the statistics are released)."""
         self._terms = self._tf = self._w = self._len = self._stat = self._idf = None
         self._n, self._stale = 0, False
+        if self._postings is not None:
+            self._postings.clear()
+        self._postings_stale = False
         if self._auto_terms:
             self.terms = None
 
@@ -103,7 +129,7 @@ class BM25Index:
         """New k1 and b for the documents already stored: only marks the index stale, the counts are kept."""
         self._check_params(k1, b)
         self.k1, self.b = float(k1), float(b)
-        self._stale = self._n > 0
+        self._stale = self._postings_stale = self._n > 0
 
     # ------------------------------------------------------------ storage
     @property
@@ -154,7 +180,7 @@ class BM25Index:
         a, b = self._n, self._n + n
         ops.bm25_term_counts(ids, mask, self._terms[a:b], self._tf[a:b], self._len[a:b], self.vocab_size, self.strip,
                              df=self._df, stats=self._counters)
-        self._n, self._stale = b, True
+        self._n, self._stale, self._postings_stale = b, True, True
         return torch.arange(a, b, dtype=torch.int32, device=dev)
 
     def _host_stats(self):
@@ -175,6 +201,27 @@ class BM25Index:
         if self._stale:
             self.refresh()
 
+    def refresh_postings(self):
+        """Rebuild the postings from the stored (term id, weight) slots, after a `refresh` when the weights are stale
+        (polus_amd/ir/postings.py: count, offsets, one 8-byte copy to the host, fill).  Needs postings=True."""
+        if self._postings is None:
+            raise ValueError("this index was made with postings=False")
+        if self._n == 0:
+            raise ValueError("the index is empty: add documents before refreshing")
+        self._fresh()
+        self._postings.build(self._terms[:self._n], self._w[:self._n], self.vocab_size)
+        self._postings_stale = False
+
+    @property
+    def postings(self):
+        """(offsets int32 [nblk, V + 1], base int64 [nblk + 1], post_doc int16 [P], post_w f32 [P]), rebuilt first when
+        stale; None without postings=True or on an empty index."""
+        if self._postings is None or self._n == 0:
+            return None
+        if self._postings_stale or not self._postings.built:
+            self.refresh_postings()
+        return self._postings.arrays()
+
     # ------------------------------------------------------------ views
     @property
     def truncated(self):
@@ -188,8 +235,12 @@ class BM25Index:
 
     @property
     def nbytes(self):
-        """Bytes of the stored documents (12 * terms + 4 each: ids, counts, weights, length) plus df and the counters."""
-        return 0 if self._terms is None else self._n * (12 * self.terms + 4) + 4 * self.vocab_size + 24
+        """Bytes of the stored documents (12 * terms + 4 each: ids, counts, weights, length) plus df and the counters,
+        plus the postings that are built."""
+        if self._terms is None:
+            return 0
+        extra = 0 if self._postings is None else self._postings.nbytes
+        return self._n * (12 * self.terms + 4) + 4 * self.vocab_size + 24 + extra
 
     @property
     def term_ids(self):
@@ -233,6 +284,26 @@ class BM25Index:
     def encode_queries(self, queries):
         """The queries' dense f32 [Q, V] rows: tf_q(t) * idf(t) at the query's terms, 0 elsewhere.  A query row holds at
         most 1024 tokens; its tokens are stripped and rejected like a document's."""
+        terms, tf = self._query_counts(queries)
+        if self.vocab_size > MAX_VOCAB:
+            raise ValueError(f"dense query rows need vocab_size <= {MAX_VOCAB}, the row ops.sparse_scores holds in LDS "
+                             f"(got {self.vocab_size}): use encode_query_lists")
+        q = torch.empty((terms.shape[0], self.vocab_size), dtype=torch.float32, device=terms.device)
+        return ops.bm25_query(terms, tf, self._idf, q)
+
+    def encode_query_lists(self, queries):
+        """The queries as lists (q_terms int32 [Q, Lq], q_w f32 [Q, Lq], q_count int32 [Q]): the query's distinct terms
+        in ascending id with weight tf_q(t) * idf(t), then (-1, 0.0).  What the postings route searches with; no dense
+        row is made, so the vocabulary is not limited."""
+        terms, tf = self._query_counts(queries)
+        Q, Lq = terms.shape
+        q_terms = torch.empty((Q, Lq), dtype=torch.int32, device=terms.device)
+        q_w = torch.empty((Q, Lq), dtype=torch.float32, device=terms.device)
+        q_count = torch.empty((Q,), dtype=torch.int32, device=terms.device)
+        ops.bm25_query_lists(terms, tf, self._idf, q_terms, q_w, q_count)
+        return q_terms, q_w, q_count
+
+    def _query_counts(self, queries):
         if self._n == 0:
             raise ValueError("the index is empty: idf needs documents")
         self._fresh()
@@ -245,8 +316,7 @@ class BM25Index:
         tf = torch.empty((Q, Lq), dtype=torch.int32, device=dev)
         ln = torch.empty((Q,), dtype=torch.int32, device=dev)
         ops.bm25_term_counts(ids, mask, terms, tf, ln, self.vocab_size, self.strip)
-        q = torch.empty((Q, self.vocab_size), dtype=torch.float32, device=dev)
-        return ops.bm25_query(terms, tf, self._idf, q)
+        return terms, tf
 
     def search(self, queries, k):
         """(scores f32 [Q, k], ids int32 [Q, k]) on the device: per query the k best documents, score descending, ties
@@ -255,6 +325,16 @@ class BM25Index:
         such results with min_score = 0."""
         if self._n == 0:
             raise ValueError("the index is empty: add documents before searching")
+        if self._postings is not None:
+            q_terms, q_w, q_count = self.encode_query_lists(queries)
+            if self._postings_stale or not self._postings.built:
+                self.refresh_postings()
+            return self._postings.search(q_terms, q_w, q_count, k, self.scratch_bytes)
+        return self.search_forward(queries, k)
+
+    def search_forward(self, queries, k):
+        """`search` on the forward route, whatever `postings` says (tools/postings_bench.py compares the two routes of
+        one index with it); needs vocab_size <= 40960."""
         q = self.encode_queries(queries)
         Q = q.shape[0]
         spans = self.chunks(Q)

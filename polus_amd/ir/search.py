@@ -59,6 +59,15 @@ a document it does not rerank, and with `nprobe` not even its codes, so there is
 bits).  All of the error is the quantiser's.  Recall and score error of 1-, 2- and 4-bit
 residuals have not been measured on any real collection here.
 
+A learned sparse (SPLADE) first stage is a SparseCorpusIndex: per document its best (term id, weight) pairs, dense
+queries, every document scored for every query (ops.sparse_scores).  With `postings=True` it searches block-inverted
+postings instead (polus_amd/ir/postings.py has the format and the score rule): the dense queries become lists of their
+non-zeros (ops.sparse_compact_rows), only the lists of a query's terms are read (ops.postings_scores), and
+representations wider than 40 960 columns are accepted.
+
+    sparse = SparseCorpusIndex(splade, terms=128, postings=True, query_terms=1024)
+    scores, ids = sparse.search(queries, k=1000)        # the same contract; postings rebuilt when an add made them stale
+
 As in ir/training.py, arithmetic is hand-written HIP (ops.gemm / ops.maxsim_scores / ops.maxsim_rerank,
 ops.l2norm_fwd, ops.topk_merge, ops.centroid_scores / centroid_scores_ids / centroid_codes / centroid_update,
 ops.ivf_count / ivf_offsets / ivf_fill / ivf_mark / ivf_compact, ops.residual_compress /
@@ -70,6 +79,7 @@ import torch
 from .. import ops
 from ..callbacks import ValidationDataCallback
 from .models import TokenReps
+from .postings import Postings, check_block_docs
 
 MAX_CHUNK = 65535             # documents per launch: the MaxSim grid's limit, kept on the dot path too
 MAX_K = 1024                  # results per query: the limit of ops.topk_merge
@@ -759,18 +769,50 @@ class SparseCorpusIndex:
     their id.  Zero weights are kept when nothing better is left: they add nothing.
     `search` scores chunks of documents with ops.sparse_scores and merges them with ops.topk_merge, the loop of
     CorpusIndex.search.  `scratch_bytes` bounds the [Q, n] f32 score buffer of one chunk.
+    `postings=True` searches block-inverted postings of `block_docs` documents per block instead (polus_amd/ir/postings.py):
+    `add` marks them stale, `refresh_postings` (or the next search) rebuilds them from the stored slots, the dense
+    queries become lists of at most `query_terms` non-zeros (ops.sparse_compact_rows; their counts are copied to the
+    host, the route's one synchronisation, and a query with more raises), and representations wider than the 40 960
+    columns ops.sparse_scores holds in LDS are accepted.  The default is the forward route, unchanged.
     Not measured: retrieval quality and how sparse the representations of a trained model are on a real collection."""
 
-    def __init__(self, model, terms=128, scratch_bytes=256 << 20):
+    def __init__(self, model, terms=128, scratch_bytes=256 << 20, postings=False, block_docs=8192, query_terms=1024):
         if not 1 <= int(terms) <= MAX_K:
             raise ValueError(f"need 1 <= terms <= {MAX_K}, the limit of ops.topk_merge, which keeps them (got {terms})")
+        if int(query_terms) < 1:
+            raise ValueError(f"need query_terms >= 1 (got {query_terms})")
         self.model, self.terms, self.scratch_bytes = model, int(terms), int(scratch_bytes)
+        self.block_docs, self.query_terms = check_block_docs(block_docs), int(query_terms)
+        self._postings = Postings(block_docs) if postings else None
         self.clear()
 
     def clear(self):
         """Empty the index (the storage is released)."""
         self._ids = self._w = None
         self._n = 0
+        if self._postings is not None:
+            self._postings.clear()
+        self._postings_stale = False
+
+    def refresh_postings(self):
+        """Rebuild the postings from the stored (term id, weight) slots (polus_amd/ir/postings.py: count, offsets, one
+        8-byte copy to the host, fill).  Needs postings=True."""
+        if self._postings is None:
+            raise ValueError("this index was made with postings=False")
+        if self._n == 0:
+            raise ValueError("the index is empty: add documents before refreshing")
+        self._postings.build(self._ids[:self._n], self._w[:self._n], self._V)
+        self._postings_stale = False
+
+    @property
+    def postings(self):
+        """(offsets int32 [nblk, V + 1], base int64 [nblk + 1], post_doc int16 [P], post_w f32 [P]), rebuilt first when
+        stale; None without postings=True or on an empty index."""
+        if self._postings is None or self._n == 0:
+            return None
+        if self._postings_stale or not self._postings.built:
+            self.refresh_postings()
+        return self._postings.arrays()
 
     def __len__(self):
         return self._n
@@ -787,8 +829,11 @@ class SparseCorpusIndex:
 
     @property
     def nbytes(self):
-        """Bytes of the stored ids and weights of the len(index) documents."""
-        return 0 if self._ids is None else self._n * self.terms * (self._ids.element_size() + self._w.element_size())
+        """Bytes of the stored ids and weights of the len(index) documents, plus the postings that are built."""
+        if self._ids is None:
+            return 0
+        extra = 0 if self._postings is None else self._postings.nbytes
+        return self._n * self.terms * (self._ids.element_size() + self._w.element_size()) + extra
 
     def _grow(self, need, dev):
         cap = 0 if self._ids is None else self._ids.shape[0]
@@ -821,7 +866,21 @@ class SparseCorpusIndex:
         self._w[self._n:self._n + n].copy_(vals)
         out = torch.arange(self._n, self._n + n, dtype=torch.int32, device=rep.device)
         self._n += n
+        self._postings_stale = True
         return out
+
+    def query_lists(self, q):
+        """Dense f32 [Q, V] query representations as lists (q_terms int32, q_w f32 [Q, query_terms], q_count int32 [Q]) of
+        their non-zeros in ascending term id; copies the Q counts to the host and raises when one exceeds query_terms."""
+        Q, cap = q.shape[0], self.query_terms
+        q_terms = torch.empty((Q, cap), dtype=torch.int32, device=q.device)
+        q_w = torch.empty((Q, cap), dtype=torch.float32, device=q.device)
+        q_count = torch.empty((Q,), dtype=torch.int32, device=q.device)
+        ops.sparse_compact_rows(q, q_terms, q_w, q_count)
+        most = int(q_count.cpu().max())                                   # the route's one synchronisation
+        if most > cap:
+            raise ValueError(f"a query has {most} non-zero terms, more than query_terms = {cap}: raise query_terms")
+        return q_terms, q_w, q_count
 
     def chunks(self, Q):
         """[(start, stop), ...]: the document ranges a search with Q queries scores, one launch each (CorpusIndex.chunks)."""
@@ -842,6 +901,18 @@ class SparseCorpusIndex:
         if self._n == 0:
             raise ValueError("the index is empty: add documents before searching")
         q = self.encode_queries(queries)
+        if self._postings is not None:
+            if q.dim() != 2 or q.shape[1] != self._V:
+                raise ValueError(f"the index holds representations over {self._V} terms, the queries have {tuple(q.shape)}")
+            lists = self.query_lists(q)
+            if self._postings_stale or not self._postings.built:
+                self.refresh_postings()
+            return self._postings.search(*lists, k, self.scratch_bytes)
+        return self.search_forward(q, k)
+
+    def search_forward(self, q, k):
+        """`search` on the forward route for dense f32 [Q, V] query representations, whatever `postings` says
+        (tools/postings_bench.py compares the two routes of one index with it)."""
         Q = q.shape[0]
         spans = self.chunks(Q)
         scratch = torch.empty((Q, max(b - a for a, b in spans)), dtype=torch.float32, device=q.device)

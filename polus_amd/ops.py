@@ -906,6 +906,119 @@ def bm25_query(terms, tf, idf, q):
     return q
 
 
+def _postings_blocks(N, block_docs):
+    bd = int(block_docs)
+    assert 64 <= bd <= 32768 and bd & (bd - 1) == 0, f"block_docs must be a power of two in [64, 32768] (got {block_docs})"
+    return (int(N) + bd - 1) // bd
+
+
+def _postings_forward(ids, w, name):
+    assert ids.dim() == 2 and w.dim() == 2 and ids.shape == w.shape, f"{name}: ids and w must both be [N, M]"
+    N, M = ids.shape
+    return N, M, _rows2d(ids, torch.int32, N, M, "ids"), _rows2d(w, torch.float32, N, M, "w")
+
+
+def postings_count(ids, w, V, block_docs, counts):
+    """counts[b, t] (int32 [nblk, V] contiguous, zeroed here) = the postings of term t among the documents of block b:
+    the slots of ids int32 / w f32 [N, M] (any row stride) with 0 <= id < V and w != 0 (include/polus_hip.h
+    polus_postings_count)."""
+    _req_cuda(ids, w, counts)
+    N, M, ldi, ldw = _postings_forward(ids, w, "postings_count")
+    nblk = _postings_blocks(N, block_docs)
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and tuple(counts.shape) == (nblk, int(V))
+    check(_lib.load().polus_postings_count(ptr(ids), ldi, ptr(w), ldw, N, M, int(V), int(block_docs), ptr(counts), _st()),
+          "polus_postings_count")
+
+
+def postings_offsets(counts, offsets, base):
+    """offsets (int32 [nblk, V + 1]) = the exclusive scan of every row of counts (int32 [nblk, V]); base (int64
+    [nblk + 1]) = the exclusive scan of the block totals, base[nblk] = P (include/polus_hip.h polus_postings_offsets)."""
+    _req_cuda(counts, offsets, base)
+    nblk, V = counts.shape
+    assert counts.dtype == torch.int32 and counts.is_contiguous()
+    assert offsets.dtype == torch.int32 and offsets.is_contiguous() and tuple(offsets.shape) == (nblk, V + 1)
+    assert base.dtype == torch.int64 and base.is_contiguous() and base.numel() == nblk + 1
+    check(_lib.load().polus_postings_offsets(ptr(counts), nblk, V, ptr(offsets), ptr(base), _st()), "polus_postings_offsets")
+
+
+def postings_fill(ids, w, block_docs, offsets, base, cursor, post_doc, post_w):
+    """post_doc (int16 [P], the bits of the unsigned local id) and post_w (f32 [P]) receive the postings of ids / w
+    [N, M], the list of (block b, term t) at base[b] + offsets[b, t] .., in no specified order inside a list; cursor
+    int32 [nblk, V] is scratch, zeroed here (include/polus_hip.h polus_postings_fill)."""
+    _req_cuda(ids, w, offsets, base, cursor, post_doc, post_w)
+    N, M, ldi, ldw = _postings_forward(ids, w, "postings_fill")
+    nblk = _postings_blocks(N, block_docs)
+    V = offsets.shape[1] - 1
+    assert offsets.dtype == torch.int32 and offsets.is_contiguous() and tuple(offsets.shape) == (nblk, V + 1)
+    assert base.dtype == torch.int64 and base.is_contiguous() and base.numel() == nblk + 1
+    assert cursor.dtype == torch.int32 and cursor.is_contiguous() and tuple(cursor.shape) == (nblk, V)
+    P = post_doc.numel()
+    assert post_doc.dtype == torch.int16 and post_doc.dim() == 1 and post_doc.is_contiguous()
+    assert post_w.dtype == torch.float32 and post_w.dim() == 1 and post_w.is_contiguous() and post_w.numel() == P
+    check(_lib.load().polus_postings_fill(ptr(ids), ldi, ptr(w), ldw, N, M, V, int(block_docs), ptr(offsets), ptr(base), P,
+                                          ptr(cursor), ptr(post_doc) if P else None, ptr(post_w) if P else None, _st()),
+          "polus_postings_fill")
+
+
+def _query_list(q_terms, q_w, q_count, Q, cap):
+    ldt, ldw = _rows2d(q_terms, torch.int32, Q, cap, "q_terms"), _rows2d(q_w, torch.float32, Q, cap, "q_w")
+    assert q_count.dtype == torch.int32 and q_count.is_contiguous() and q_count.numel() >= Q
+    return ldt, ldw
+
+
+def sparse_compact_rows(q, q_terms, q_w, q_count):
+    """The non-zero entries (NaN included, -0.0 not) of every row of q (f32 [Q, V], any row stride) as a query list:
+    q_terms int32 / q_w f32 [Q, cap] (any row stride) in ascending term id, then (-1, 0.0); q_count int32 [Q] = the full
+    number of non-zeros, also when it exceeds cap (include/polus_hip.h polus_sparse_compact_rows)."""
+    _req_cuda(q, q_terms, q_w, q_count)
+    Q, V = q.shape
+    cap = q_terms.shape[1]
+    ldq = _rows2d(q, torch.float32, Q, V, "q")
+    assert q_w.shape[1] == cap
+    ldt, ldw = _query_list(q_terms, q_w, q_count, Q, cap)
+    check(_lib.load().polus_sparse_compact_rows(ptr(q), ldq, Q, V, cap, ptr(q_terms), ldt, ptr(q_w), ldw, ptr(q_count), _st()),
+          "polus_sparse_compact_rows")
+
+
+def bm25_query_lists(terms, tf, idf, q_terms, q_w, q_count):
+    """The used slots of terms / tf (int32 [Q, M], as bm25_term_counts leaves a query) as a query list in ascending id:
+    q_terms int32 / q_w f32 [Q, M] (any row stride), weight tf * idf[t], then (-1, 0.0); q_count int32 [Q]; idf f32 [V],
+    ids outside [0, V) are dropped (include/polus_hip.h polus_bm25_query_lists)."""
+    _req_cuda(terms, tf, idf, q_terms, q_w, q_count)
+    Q, M = terms.shape
+    ldt, ldf = _rows2d(terms, torch.int32, Q, M, "terms"), _rows2d(tf, torch.int32, Q, M, "tf")
+    assert tf.shape[1] == M and q_terms.shape[1] == M and q_w.shape[1] == M
+    assert idf.dtype == torch.float32 and idf.is_contiguous()
+    ldt2, ldw = _query_list(q_terms, q_w, q_count, Q, M)
+    check(_lib.load().polus_bm25_query_lists(ptr(terms), ldt, ptr(tf), ldf, ptr(idf), Q, M, idf.numel(), ptr(q_terms), ldt2,
+                                             ptr(q_w), ldw, ptr(q_count), _st()), "polus_bm25_query_lists")
+
+
+def postings_scores(q_terms, q_w, q_count, offsets, base, post_doc, post_w, block_docs, blk0, nblk_launch, N, score):
+    """score[q, (b - blk0) * block_docs + local] (f32, any row stride) = the score of query q and document
+    b * block_docs + local under the rule of include/polus_hip.h polus_postings_scores, for the blocks blk0 ..
+    blk0 + nblk_launch of an N-document corpus; columns of documents >= N are not written.  The query list is q_terms /
+    q_w [Q, cap] and q_count [Q]; the postings are (offsets, base, post_doc, post_w)."""
+    _req_cuda(q_terms, q_w, q_count, offsets, base, post_doc, post_w, score)
+    Q, cap = q_terms.shape
+    assert q_w.shape[1] == cap
+    ldt, ldw = _query_list(q_terms, q_w, q_count, Q, cap)
+    nblk = _postings_blocks(N, block_docs)
+    V = offsets.shape[1] - 1
+    assert offsets.dtype == torch.int32 and offsets.is_contiguous() and tuple(offsets.shape) == (nblk, V + 1)
+    assert base.dtype == torch.int64 and base.is_contiguous() and base.numel() == nblk + 1
+    P = post_doc.numel()
+    assert post_doc.dtype == torch.int16 and post_doc.dim() == 1 and post_doc.is_contiguous()
+    assert post_w.dtype == torch.float32 and post_w.dim() == 1 and post_w.is_contiguous() and post_w.numel() == P
+    cols = min(int(nblk_launch) * int(block_docs), int(N) - int(blk0) * int(block_docs))
+    lds = _rows2d(score, torch.float32, Q, cols, "score")
+    check(_lib.load().polus_postings_scores(ptr(q_terms), ldt, ptr(q_w), ldw, ptr(q_count), cap, ptr(offsets), ptr(base),
+                                            ptr(post_doc) if P else None, ptr(post_w) if P else None, P, V, int(block_docs),
+                                            int(blk0), int(nblk_launch), int(N), ptr(score), lds, Q, _st()),
+          "polus_postings_scores")
+    return score
+
+
 def mine_negatives(cand, neg, n_pool, score=None, exclude=None, skip_top=0, min_score=0.0, seed=0, neg_col=None):
     """k = neg.shape[1] negatives per row of cand (int32 [Q, C] in rank order, any row stride) into neg (int32 [Q, k]),
     their columns into neg_col (int32 [Q, k] or None) and the pool size into n_pool (int32 [Q]).  The pool of a row:
