@@ -277,6 +277,9 @@ extern "C" int polus_act_bwd(int dtype, const void* dy, const void* u, void* du,
 extern "C" int polus_transpose_bf16_batched(const void* src_base, void* dst_base, const void* segs_dev, int nseg,
                                             int total_tiles, void* stream) {
     POLUS_REQUIRE(src_base && dst_base && segs_dev && nseg > 0 && total_tiles > 0, "polus_transpose_bf16_batched: bad arguments");
+    // matrices whose rows and columns are multiples of 4 move 8 bytes per access from base + offset (offsets are 64-element aligned)
+    POLUS_REQUIRE(((uintptr_t)src_base % 8) == 0 && ((uintptr_t)dst_base % 8) == 0,
+                  "polus_transpose_bf16_batched: the arenas must be 8-byte aligned");
     hipLaunchKernelGGL(transpose16_batched_kernel, dim3(total_tiles), dim3(256), 0, static_cast<hipStream_t>(stream),
                        (const unsigned short*)src_base, (unsigned short*)dst_base, (const long*)segs_dev, nseg);
     POLUS_CHECK_LAUNCH("polus_transpose_bf16_batched");

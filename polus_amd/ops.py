@@ -66,7 +66,8 @@ def set_dynamic_params(block):
     kernels and the fused optimizer read per-step scalars from (include/polus_hip.h)."""
     if block is not None:
         _req_cuda(block)
-        assert block.numel() * block.element_size() >= 16 and block.is_contiguous()
+        assert block.numel() * block.element_size() >= 16 and block.is_contiguous(), \
+            f"set_dynamic_params: block must be contiguous and hold at least 16 bytes {_got(block)}"
     check(_lib.load().polus_set_dynamic_params(ptr(block)), "polus_set_dynamic_params")
 
 
@@ -94,13 +95,46 @@ def _req_cuda(*ts):
             raise _lib.PolusHipError("polus_amd ops need device (HBM) tensors; there is no CPU path")
 
 
+_F32T, _BF16T, _I32T, _I64T = torch.float32, torch.bfloat16, torch.int32, torch.int64
+
+
+def _got(t):
+    return f"(got {t.dtype} {list(t.shape)}, strides {list(t.stride())})"
+
+
+def _dt(op, name, t):
+    """dtype_code for a tensor whose dtype the entry point takes as an argument; the refusal names the parameter."""
+    d = t.dtype
+    if d == _F32T:
+        return F32
+    assert d == _BF16T, f"{op}: {name} must be f32 or bf16 {_got(t)}"
+    return BF16
+
+
+def _vec(op, name, t, dtype, n, optional=False):
+    """A flat pointer and a count: a contiguous tensor of `dtype` with at least n elements."""
+    if t is None:
+        assert optional, f"{op}: {name} is required"
+        return
+    assert t.dtype == dtype and t.numel() >= n and t.is_contiguous(), \
+        f"{op}: {name} must be contiguous {dtype} with at least {n} elements {_got(t)}"
+
+
+def _mat(op, name, t, dtype, rows, cols):
+    """A pointer and a row stride: a 2-D tensor of `dtype` with at least rows x cols elements whose inner stride is one."""
+    assert t.dtype == dtype and t.dim() == 2 and t.shape[0] >= rows and t.shape[1] >= cols and (t.stride(1) == 1 or t.shape[1] == 1), \
+        f"{op}: {name} must be {dtype} [>= {rows}, >= {cols}] with a unit inner stride {_got(t)}"
+
+
 _AUTO_SPLIT = {}
 
 
 def _gemm_call(a, b, out, a_layout, b_layout, M, N, K, alpha, bias, resid, aux, act, flags, split_k):
     """What `gemm` and `gemm_route` share: (M, N, K, split_k with "auto" settled, the arguments of polus_gemm and
     polus_gemm_route up to split_k)."""
-    assert b.dtype == a.dtype and a.dim() == 2 and b.dim() == 2 and out.dim() == 2
+    dt = a.dtype
+    assert a.dim() == 2 and a.stride(1) == 1, f"gemm: a must be 2-D with a unit inner stride {_got(a)}"
+    assert b.dtype == dt and b.dim() == 2 and b.stride(1) == 1, f"gemm: b must be 2-D {dt} with a unit inner stride {_got(b)}"
     if a_layout == K_CONTIG:
         m_, k_ = a.shape
     else:
@@ -112,9 +146,17 @@ def _gemm_call(a, b, out, a_layout, b_layout, M, N, K, alpha, bias, resid, aux, 
     M = m_ if M is None else M
     N = n_ if N is None else N
     K = k_ if K is None else K
-    assert kb_ == k_, f"contraction mismatch {k_} vs {kb_}"
-    assert out.shape[0] >= M and out.shape[1] >= N
-    assert a.stride(1) == 1 and b.stride(1) == 1 and out.stride(1) == 1
+    assert kb_ == k_, f"gemm: b: contraction mismatch with a, {k_} vs {kb_}"
+    assert m_ >= M and k_ >= K, f"gemm: a holds fewer than M={M} x K={K} elements {_got(a)}"
+    assert n_ >= N, f"gemm: b holds fewer than N={N} rows of the product {_got(b)}"
+    assert ((out.dtype == dt or out.dtype == _F32T) and out.dim() == 2 and out.shape[0] >= M and out.shape[1] >= N
+            and out.stride(1) == 1), f"gemm: out must be f32 or {dt} [>= {M}, >= {N}] with a unit inner stride {_got(out)}"
+    if bias is not None:
+        _vec("gemm", "bias", bias, _F32T, N)
+    if resid is not None:
+        _mat("gemm", "resid", resid, dt, M, N)
+    if aux is not None:
+        _mat("gemm", "aux", aux, dt, M, N)
     if split_k == "auto":
         # the library's recommendation for a bf16 Dense GEMM (K-contiguous operands, bf16 C); 1 for everything else
         split_k = 1
@@ -217,36 +259,64 @@ def rowwise_route(dtype, rows, H, deterministic=False):
     return RowwiseRoute(LN_ROUTES[r[0]], r[1], r[2], r[3], SCATTER_ROUTES[r[4]], r[5], r[6])
 
 
+def _dense(op, name, t, dtype, shape):
+    """A flat pointer whose extents the other arguments fix: a contiguous tensor of exactly this dtype and shape."""
+    assert t.dtype == dtype and t.shape == shape and t.is_contiguous(), \
+        f"{op}: {name} must be contiguous {dtype} {list(shape)} {_got(t)}"
+
+
 def attention_fwd(qkv, mask, ctx, lse, B, S, n_heads, drop_p=0.0, seed=0):
+    """ctx [B*S, H] = softmax attention over the fused projections qkv [B*S, 3H] (H = 64 n_heads), both contiguous and of
+    one dtype, f32 or bf16; mask int32 with B*S elements or None; lse f32 with at least B*n_heads*S elements, contiguous."""
     lib = _lib.load()
     _req_cuda(qkv, mask, ctx, lse)
     H = n_heads * 64
-    assert qkv.shape == (B * S, 3 * H) and ctx.shape == (B * S, H) and qkv.is_contiguous() and ctx.is_contiguous()
-    assert lse.dtype == torch.float32 and lse.numel() == B * n_heads * S
-    assert mask is None or (mask.dtype == torch.int32 and mask.numel() == B * S and mask.is_contiguous())
-    check(lib.polus_attention_fwd(dtype_code(qkv.dtype), ptr(qkv), ptr(mask), ptr(ctx), ptr(lse),
+    dt = qkv.dtype
+    _dense("attention_fwd", "qkv", qkv, dt, (B * S, 3 * H))
+    _dense("attention_fwd", "ctx", ctx, dt, (B * S, H))
+    _vec("attention_fwd", "lse", lse, _F32T, B * n_heads * S)
+    if mask is not None:
+        assert mask.dtype == _I32T and mask.numel() == B * S and mask.is_contiguous(), \
+            f"attention_fwd: mask must be contiguous int32 with {B * S} elements {_got(mask)}"
+    check(lib.polus_attention_fwd(_dt("attention_fwd", "qkv", qkv), ptr(qkv), ptr(mask), ptr(ctx), ptr(lse),
                                   B, S, n_heads, 64, float(drop_p), int(seed) & 0xFFFFFFFF, _st()), "polus_attention_fwd")
 
 
 def attention_bwd(qkv, mask, ctx, dctx, lse, dqkv, B, S, n_heads, drop_p=0.0, seed=0):
+    """dqkv [B*S, 3H] from dctx [B*S, H] and the forward's qkv, ctx and lse: the four matrices contiguous and of one dtype,
+    mask and lse as in attention_fwd."""
     lib = _lib.load()
     _req_cuda(qkv, mask, ctx, dctx, lse, dqkv)
     H = n_heads * 64
-    assert qkv.shape == (B * S, 3 * H) and dqkv.shape == (B * S, 3 * H) and dctx.shape == (B * S, H)
-    assert qkv.is_contiguous() and dqkv.is_contiguous() and dctx.is_contiguous() and ctx.is_contiguous()
+    dt = qkv.dtype
+    _dense("attention_bwd", "qkv", qkv, dt, (B * S, 3 * H))
+    _dense("attention_bwd", "dqkv", dqkv, dt, (B * S, 3 * H))
+    _dense("attention_bwd", "ctx", ctx, dt, (B * S, H))
+    _dense("attention_bwd", "dctx", dctx, dt, (B * S, H))
+    _vec("attention_bwd", "lse", lse, _F32T, B * n_heads * S)
+    if mask is not None:
+        assert mask.dtype == _I32T and mask.numel() == B * S and mask.is_contiguous(), \
+            f"attention_bwd: mask must be contiguous int32 with {B * S} elements {_got(mask)}"
     nb = lib.polus_attention_bwd_workspace_bytes(B, S, n_heads)
     ws = workspace(qkv.device).get(nb)
-    check(lib.polus_attention_bwd(dtype_code(qkv.dtype), ptr(qkv), ptr(mask), ptr(ctx), ptr(dctx), ptr(lse),
+    check(lib.polus_attention_bwd(_dt("attention_bwd", "qkv", qkv), ptr(qkv), ptr(mask), ptr(ctx), ptr(dctx), ptr(lse),
                                   ptr(dqkv), B, S, n_heads, 64, float(drop_p), int(seed) & 0xFFFFFFFF, ptr(ws), nb, _st()),
           "polus_attention_bwd")
 
 
 def layernorm_fwd(x, gamma, beta, y, mean, rstd, eps):
+    """y = LayerNorm(x) over the last axis; x and y contiguous [rows, H] of one dtype, f32 or bf16; gamma and beta f32 with
+    at least H elements, mean and rstd (saved for backward) f32 with at least rows, all contiguous."""
     lib = _lib.load()
     _req_cuda(x, gamma, beta, y, mean, rstd)
+    assert x.dim() == 2 and x.is_contiguous(), f"layernorm_fwd: x must be contiguous [rows, H] {_got(x)}"
     rows, H = x.shape
-    assert x.is_contiguous() and y.is_contiguous() and y.shape == x.shape
-    check(lib.polus_layernorm_fwd(dtype_code(x.dtype), ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd),
+    _dense("layernorm_fwd", "y", y, x.dtype, x.shape)
+    _vec("layernorm_fwd", "gamma", gamma, _F32T, H)
+    _vec("layernorm_fwd", "beta", beta, _F32T, H)
+    _vec("layernorm_fwd", "mean", mean, _F32T, rows)
+    _vec("layernorm_fwd", "rstd", rstd, _F32T, rows)
+    check(lib.polus_layernorm_fwd(_dt("layernorm_fwd", "x", x), ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd),
                                   rows, H, float(eps), _st()), "polus_layernorm_fwd")
 
 
@@ -261,37 +331,77 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, dbias=None, accum
     leave the per-workgroup sums there; dgamma / dbeta / dbias are then written by layernorm_bwd_finalize, which the caller
     queues on any stream ordered behind this call."""
     lib = _lib.load()
-    _req_cuda(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, dbias)
+    _req_cuda(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, dbias, dx_masked, partials)
+    assert x.dim() == 2 and x.is_contiguous(), f"layernorm_bwd: x must be contiguous [rows, H] {_got(x)}"
     rows, H = x.shape
-    assert dy.is_contiguous() and x.is_contiguous() and dx.is_contiguous()
+    dt = x.dtype
+    _dense("layernorm_bwd", "dy", dy, dt, x.shape)
+    _dense("layernorm_bwd", "dx", dx, dt, x.shape)
+    _vec("layernorm_bwd", "gamma", gamma, _F32T, H)
+    _vec("layernorm_bwd", "mean", mean, _F32T, rows)
+    _vec("layernorm_bwd", "rstd", rstd, _F32T, rows)
+    if dbias is not None:
+        _vec("layernorm_bwd", "dbias", dbias, _F32T, H)
+    if dx_masked is not None:
+        _vec("layernorm_bwd", "dx_masked", dx_masked, dt, rows * H)
     nb = lib.polus_layernorm_bwd_workspace_bytes(rows, H)
     if partials is not None:
-        assert partials.dtype == torch.float32 and partials.numel() * 4 >= nb and partials.is_contiguous()
-        check(lib.polus_layernorm_bwd(dtype_code(x.dtype), ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dx),
+        _vec("layernorm_bwd", "partials", partials, _F32T, (nb + 3) // 4)
+        check(lib.polus_layernorm_bwd(_dt("layernorm_bwd", "x", x), ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dx),
                                       None, None, ptr(dbias), int(accumulate), rows, H,
                                       ptr(dx_masked), float(drop_p), int(seed) & 0xFFFFFFFF, ptr(partials), partials.numel() * 4, _st()),
               "polus_layernorm_bwd")
         return
+    _vec("layernorm_bwd", "dgamma", dgamma, _F32T, H)
+    _vec("layernorm_bwd", "dbeta", dbeta, _F32T, H)
     ws = workspace(x.device).get(nb)
-    check(lib.polus_layernorm_bwd(dtype_code(x.dtype), ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dx),
+    check(lib.polus_layernorm_bwd(_dt("layernorm_bwd", "x", x), ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dx),
                                   ptr(dgamma), ptr(dbeta), ptr(dbias), int(accumulate), rows, H,
                                   ptr(dx_masked), float(drop_p), int(seed) & 0xFFFFFFFF, ptr(ws), nb, _st()), "polus_layernorm_bwd")
 
 
 def layernorm_bwd_finalize(partials, rows, H, dgamma, dbeta, dbias=None, accumulate=False):
+    """Reduce the partial sums that layernorm_bwd(..., partials=...) left for `rows` rows of H features into dgamma, dbeta and
+    (if given) dbias, each f32 with at least H elements; partials f32 with at least layernorm_bwd_partial_floats(rows, H)."""
     _req_cuda(partials, dgamma, dbeta, dbias)
+    _vec("layernorm_bwd_finalize", "partials", partials, _F32T, layernorm_bwd_partial_floats(rows, H))
+    _vec("layernorm_bwd_finalize", "dgamma", dgamma, _F32T, H)
+    _vec("layernorm_bwd_finalize", "dbeta", dbeta, _F32T, H)
+    if dbias is not None:
+        _vec("layernorm_bwd_finalize", "dbias", dbias, _F32T, H)
     check(_lib.load().polus_layernorm_bwd_finalize(ptr(partials), partials.numel() * 4, rows, H, ptr(dgamma), ptr(dbeta), ptr(dbias),
                                                    int(accumulate), _st()), "polus_layernorm_bwd_finalize")
 
 
+def _embed_args(op, ids, type_ids, word, pos, typ, gamma, mean, rstd):
+    """What both embedding calls share; returns (B, S, V, H)."""
+    assert ids.dtype == _I32T and ids.dim() == 2 and ids.is_contiguous(), f"{op}: ids must be contiguous int32 [B, S] {_got(ids)}"
+    B, S = ids.shape
+    if type_ids is not None:
+        _vec(op, "type_ids", type_ids, _I32T, B * S)
+    assert word.dtype == _F32T and word.dim() == 2 and word.is_contiguous(), f"{op}: word must be contiguous f32 [V, H] {_got(word)}"
+    V, H = word.shape
+    assert pos.dtype == _F32T and pos.dim() == 2 and pos.shape[0] >= S and pos.shape[1] == H and pos.is_contiguous(), \
+        f"{op}: pos must be contiguous f32 [>= {S}, {H}] {_got(pos)}"
+    assert typ.dtype == _F32T and typ.dim() == 2 and typ.shape[1] == H and typ.is_contiguous(), \
+        f"{op}: typ must be contiguous f32 [T, {H}] {_got(typ)}"
+    _vec(op, "gamma", gamma, _F32T, H)
+    _vec(op, "mean", mean, _F32T, B * S)
+    _vec(op, "rstd", rstd, _F32T, B * S)
+    return B, S, V, H
+
+
 def embed_ln_fwd(ids, type_ids, word, pos, typ, gamma, beta, y, mean, rstd, eps, drop_p=0.0, seed=0):
+    """y [B*S, H] (f32 or bf16, contiguous) = LayerNorm(word[ids] + pos[s] + typ[type_ids]); ids int32 [B, S] and type_ids
+    (int32, B*S elements, or None) contiguous; the tables word [V, H], pos [>= S, H] and typ [T, H] are contiguous f32 whatever
+    y's dtype; gamma and beta f32 with at least H elements, mean and rstd f32 with at least B*S."""
     lib = _lib.load()
     _req_cuda(ids, type_ids, word, pos, typ, gamma, beta, y, mean, rstd)
-    B, S = ids.shape
-    V, H = word.shape
-    assert ids.dtype == torch.int32 and ids.is_contiguous()
-    assert type_ids is None or (type_ids.dtype == torch.int32 and type_ids.is_contiguous())
-    check(lib.polus_embed_ln_fwd(dtype_code(y.dtype), ptr(ids), ptr(type_ids), ptr(word), ptr(pos), ptr(typ),
+    B, S, V, H = _embed_args("embed_ln_fwd", ids, type_ids, word, pos, typ, gamma, mean, rstd)
+    _vec("embed_ln_fwd", "beta", beta, _F32T, H)
+    assert y.numel() >= B * S * H and y.is_contiguous(), \
+        f"embed_ln_fwd: y must be contiguous with at least {B * S * H} elements {_got(y)}"
+    check(lib.polus_embed_ln_fwd(_dt("embed_ln_fwd", "y", y), ptr(ids), ptr(type_ids), ptr(word), ptr(pos), ptr(typ),
                                  ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(rstd),
                                  B, S, H, V, pos.shape[0], typ.shape[0], float(eps), float(drop_p), int(seed) & 0xFFFFFFFF,
                                  _st()), "polus_embed_ln_fwd")
@@ -299,13 +409,21 @@ def embed_ln_fwd(ids, type_ids, word, pos, typ, gamma, beta, y, mean, rstd, eps,
 
 def embed_ln_bwd(dy, ids, type_ids, word, pos, typ, gamma, mean, rstd, gword, gpos, gtyp, ggamma, gbeta,
                  accumulate=False, deterministic=False, drop_p=0.0, seed=0):
+    """Gradients of embed_ln_fwd from dy [B*S, H] (f32 or bf16, contiguous): gword, gpos and gtyp are contiguous f32 with at
+    least the elements of word, pos and typ, ggamma and gbeta f32 with at least H elements; the inputs are as in embed_ln_fwd."""
     lib = _lib.load()
-    _req_cuda(dy, ids, word, gword)
-    B, S = ids.shape
-    V, H = word.shape
+    _req_cuda(dy, ids, type_ids, word, pos, typ, gamma, mean, rstd, gword, gpos, gtyp, ggamma, gbeta)
+    B, S, V, H = _embed_args("embed_ln_bwd", ids, type_ids, word, pos, typ, gamma, mean, rstd)
+    assert dy.numel() >= B * S * H and dy.is_contiguous(), \
+        f"embed_ln_bwd: dy must be contiguous with at least {B * S * H} elements {_got(dy)}"
+    _vec("embed_ln_bwd", "gword", gword, _F32T, V * H)
+    _vec("embed_ln_bwd", "gpos", gpos, _F32T, pos.shape[0] * H)
+    _vec("embed_ln_bwd", "gtyp", gtyp, _F32T, typ.shape[0] * H)
+    _vec("embed_ln_bwd", "ggamma", ggamma, _F32T, H)
+    _vec("embed_ln_bwd", "gbeta", gbeta, _F32T, H)
     nb = lib.polus_embed_bwd_workspace_bytes(B, S, H)
     ws = workspace(dy.device).get(nb)
-    check(lib.polus_embed_ln_bwd(dtype_code(dy.dtype), ptr(dy), ptr(ids), ptr(type_ids), ptr(word), ptr(pos), ptr(typ),
+    check(lib.polus_embed_ln_bwd(_dt("embed_ln_bwd", "dy", dy), ptr(dy), ptr(ids), ptr(type_ids), ptr(word), ptr(pos), ptr(typ),
                                  ptr(gamma), ptr(mean), ptr(rstd), ptr(gword), ptr(gpos), ptr(gtyp), ptr(ggamma),
                                  ptr(gbeta), int(accumulate), int(deterministic),
                                  B, S, H, V, pos.shape[0], typ.shape[0], float(drop_p), int(seed) & 0xFFFFFFFF,
@@ -313,36 +431,59 @@ def embed_ln_bwd(dy, ids, type_ids, word, pos, typ, gamma, mean, rstd, gword, gp
 
 
 def colsum(x, out, accumulate=False, rows=None, cols=None):
+    """out[c] (+)= sum over r < rows of x[r, c]; x f32 or bf16 [>= rows, >= cols] with any row stride and a unit inner
+    stride, out contiguous f32 with at least cols elements."""
     lib = _lib.load()
     _req_cuda(x, out)
+    assert x.dim() == 2, f"colsum: x must be 2-D {_got(x)}"
     rows = x.shape[0] if rows is None else rows
     cols = x.shape[1] if cols is None else cols
+    _mat("colsum", "x", x, x.dtype, rows, cols)
+    _vec("colsum", "out", out, _F32T, cols)
     nb = lib.polus_colsum_workspace_bytes(rows, cols)
     ws = workspace(x.device).get(nb)
-    check(lib.polus_colsum(dtype_code(x.dtype), ptr(x), x.stride(0), rows, cols, ptr(out), int(accumulate),
+    check(lib.polus_colsum(_dt("colsum", "x", x), ptr(x), x.stride(0), rows, cols, ptr(out), int(accumulate),
                            ptr(ws), nb, _st()), "polus_colsum")
 
 
 def softmax_xent(logits, labels, loss, dlogits, class_weights=None, rows=None, C=None):
+    """loss (f32 [1]) = mean sparse softmax cross-entropy of logits f32 [>= rows, >= C] against labels (contiguous int32, at
+    least rows), dlogits (f32 or bf16, [>= rows, >= C]) its gradient; both matrices have free row strides and a unit inner
+    stride; class_weights None or contiguous f32 with at least C elements."""
     lib = _lib.load()
     _req_cuda(logits, labels, loss, dlogits, class_weights)
+    assert logits.dim() == 2, f"softmax_xent: logits must be 2-D {_got(logits)}"
     rows = logits.shape[0] if rows is None else rows
     C = logits.shape[1] if C is None else C
-    assert logits.dtype == torch.float32 and labels.dtype == torch.int32 and loss.dtype == torch.float32
+    _mat("softmax_xent", "logits", logits, _F32T, rows, C)
+    _vec("softmax_xent", "labels", labels, _I32T, rows)
+    _vec("softmax_xent", "loss", loss, _F32T, 1)
+    _mat("softmax_xent", "dlogits", dlogits, dlogits.dtype, rows, C)
+    if class_weights is not None:
+        _vec("softmax_xent", "class_weights", class_weights, _F32T, C)
     nb = lib.polus_loss_workspace_bytes(rows)
     ws = workspace(logits.device).get(nb)
-    check(lib.polus_softmax_xent(dtype_code(dlogits.dtype), ptr(logits), logits.stride(0), ptr(labels),
+    check(lib.polus_softmax_xent(_dt("softmax_xent", "dlogits", dlogits), ptr(logits), logits.stride(0), ptr(labels),
                                  ptr(class_weights), ptr(loss), ptr(dlogits), dlogits.stride(0), rows, C,
                                  ptr(ws), nb, _st()), "polus_softmax_xent")
 
 
 def sigmoid_xent(logits, y_true, class_weights, negative_weight, loss, dlogits):
+    """loss (f32 [1]) = mean weighted sigmoid cross-entropy of logits f32 [rows, C] against the multi-hot y_true f32
+    [rows, C], dlogits (f32 or bf16 [rows, C]) its gradient; the three matrices have free row strides and a unit inner
+    stride; class_weights contiguous f32 with at least C elements."""
     lib = _lib.load()
     _req_cuda(logits, y_true, class_weights, loss, dlogits)
+    assert logits.dim() == 2, f"sigmoid_xent: logits must be 2-D {_got(logits)}"
     rows, C = logits.shape
+    _mat("sigmoid_xent", "logits", logits, _F32T, rows, C)
+    _mat("sigmoid_xent", "y_true", y_true, _F32T, rows, C)
+    _vec("sigmoid_xent", "class_weights", class_weights, _F32T, C)
+    _vec("sigmoid_xent", "loss", loss, _F32T, 1)
+    _mat("sigmoid_xent", "dlogits", dlogits, dlogits.dtype, rows, C)
     nb = lib.polus_loss_workspace_bytes(rows)
     ws = workspace(logits.device).get(nb)
-    check(lib.polus_sigmoid_xent(dtype_code(dlogits.dtype), ptr(logits), logits.stride(0), ptr(y_true), y_true.stride(0),
+    check(lib.polus_sigmoid_xent(_dt("sigmoid_xent", "dlogits", dlogits), ptr(logits), logits.stride(0), ptr(y_true), y_true.stride(0),
                                  ptr(class_weights), float(negative_weight), ptr(loss), ptr(dlogits), dlogits.stride(0),
                                  rows, C, ptr(ws), nb, _st()), "polus_sigmoid_xent")
 
@@ -1312,19 +1453,30 @@ def pair_scatter_scores(s, cand, N, out, rows=None):
 
 
 def argmax(x, out, rows=None, C=None):
+    """out[r] (contiguous int32, at least rows) = argmax over c < C of x[r, c]; x f32 [>= rows, >= C] with any row stride and
+    a unit inner stride."""
     lib = _lib.load()
     _req_cuda(x, out)
+    assert x.dim() == 2, f"argmax: x must be 2-D {_got(x)}"
     rows = x.shape[0] if rows is None else rows
     C = x.shape[1] if C is None else C
+    _mat("argmax", "x", x, _F32T, rows, C)
+    _vec("argmax", "out", out, _I32T, rows)
     check(lib.polus_argmax(ptr(x), x.stride(0), ptr(out), rows, C, _st()), "polus_argmax")
 
 
 def confusion_matrix(row_idx, col_idx, cm, rejected=None):
     """cm[row_idx[i], col_idx[i]] += 1 (int32 [C, C] on the device); pairs with an index outside [0, C) are counted in
     `rejected` (int32 [1] on the device) instead."""
-    _req_cuda(row_idx, col_idx, cm)
-    assert row_idx.dtype == torch.int32 and col_idx.dtype == torch.int32 and cm.dtype == torch.int32
-    assert row_idx.numel() == col_idx.numel() and row_idx.is_contiguous() and col_idx.is_contiguous() and cm.is_contiguous()
+    _req_cuda(row_idx, col_idx, cm, rejected)
+    n = row_idx.numel()
+    assert row_idx.dtype == _I32T and row_idx.is_contiguous(), f"confusion_matrix: row_idx must be contiguous int32 {_got(row_idx)}"
+    _vec("confusion_matrix", "col_idx", col_idx, _I32T, n)
+    assert col_idx.numel() == n, f"confusion_matrix: col_idx must pair up with the {n} elements of row_idx {_got(col_idx)}"
+    assert cm.dtype == _I32T and cm.dim() == 2 and cm.shape[0] == cm.shape[1] and cm.is_contiguous(), \
+        f"confusion_matrix: cm must be contiguous int32 [C, C] {_got(cm)}"
+    if rejected is not None:
+        _vec("confusion_matrix", "rejected", rejected, _I32T, 1)
     check(_lib.load().polus_confusion_matrix(ptr(row_idx), ptr(col_idx), row_idx.numel(), cm.shape[0], ptr(cm),
                                              ptr(rejected) if rejected is not None else None, _st()),
           "polus_confusion_matrix")
@@ -1372,58 +1524,94 @@ def bio_spans(tags, scheme, spans, count, mask=None, rejected=None):
 
 def adam_step(p, g, m, v, shadow, seg, n_seg, lr, lr_t, beta1, beta2, eps, weight_decay, grad_scale=1.0,
               clip_scale=None):
+    """One Adam / AdamW update of the flat arena p from g, with the moments m and v: contiguous f32, g, m and v with at least
+    p's elements; shadow None or contiguous bf16 of at least as many; seg contiguous int64 with at least 3 n_seg elements
+    (begin, end, flags per window); clip_scale None or f32 [1] on the device."""
     lib = _lib.load()
     _req_cuda(p, g, m, v, shadow, seg, clip_scale)
+    n = p.numel()
+    _vec("adam_step", "p", p, _F32T, 1)
+    _vec("adam_step", "g", g, _F32T, n)
+    _vec("adam_step", "m", m, _F32T, n)
+    _vec("adam_step", "v", v, _F32T, n)
+    if shadow is not None:
+        _vec("adam_step", "shadow", shadow, _BF16T, n)
+    _vec("adam_step", "seg", seg, _I64T, 3 * n_seg)
+    if clip_scale is not None:
+        _vec("adam_step", "clip_scale", clip_scale, _F32T, 1)
     check(lib.polus_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), ptr(shadow), ptr(seg), n_seg, p.numel(),
                               float(lr), float(lr_t), float(beta1), float(beta2), float(eps), float(weight_decay),
                               float(grad_scale), ptr(clip_scale), _st()), "polus_adam_step")
 
 
 def sqnorm(g, out):
+    """out[0] (f32) = the sum of squares of g, contiguous f32 of any shape."""
     lib = _lib.load()
     _req_cuda(g, out)
+    _vec("sqnorm", "g", g, _F32T, 1)
+    _vec("sqnorm", "out", out, _F32T, 1)
     nb = lib.polus_sqnorm_workspace_bytes(g.numel())
     ws = workspace(g.device).get(nb)
     check(lib.polus_sqnorm(ptr(g), g.numel(), ptr(out), ptr(ws), nb, _st()), "polus_sqnorm")
 
 
 def sqnorm_segments(g, seg, n_seg, out):
-    """sum of g^2 over the windows of the Adam segment table `seg` (int64 [n_seg, 3]) -> out[0]."""
+    """sum of g^2 over the windows of the Adam segment table `seg` (int64 [n_seg, 3]) -> out[0]; g contiguous f32 that
+    covers every window, seg contiguous with at least 3 n_seg elements, out f32."""
     lib = _lib.load()
     _req_cuda(g, seg, out)
-    ws = workspace(g.device).get(4096)
+    _vec("sqnorm_segments", "g", g, _F32T, 1)
+    _vec("sqnorm_segments", "seg", seg, _I64T, 3 * n_seg)
+    _vec("sqnorm_segments", "out", out, _F32T, 1)
+    ws =workspace(g.device).get(4096)
     check(lib.polus_sqnorm_segments(ptr(g), ptr(seg), int(n_seg), ptr(out), ptr(ws), 4096, _st()), "polus_sqnorm_segments")
 
 
 def clip_scale(sq, grad_scale, clip_norm, out):
-    """out = clip_norm / max(sqrt(sum(sq)) * |grad_scale|, clip_norm); sq holds one partial sum per arena."""
+    """out = clip_norm / max(sqrt(sum(sq)) * |grad_scale|, clip_norm); sq holds one partial sum per arena (contiguous f32,
+    every element is read), out f32 [1]."""
+    _req_cuda(sq, out)
+    _vec("clip_scale", "sq", sq, _F32T, 1)
+    _vec("clip_scale", "out", out, _F32T, 1)
     check(_lib.load().polus_clip_scale(ptr(sq), sq.numel(), float(grad_scale), float(clip_norm), ptr(out), _st()), "polus_clip_scale")
 
 
 def cast(src, dst):
+    """dst = src converted, element by element: both contiguous, f32 or bf16 each, with the same number of elements."""
     _req_cuda(src, dst)
-    assert src.numel() == dst.numel()
-    check(_lib.load().polus_cast(dtype_code(src.dtype), ptr(src), dtype_code(dst.dtype), ptr(dst), src.numel(), _st()),
+    n = src.numel()
+    assert src.is_contiguous(), f"cast: src must be contiguous {_got(src)}"
+    assert dst.numel() == n and dst.is_contiguous(), f"cast: dst must be contiguous with the {n} elements of src {_got(dst)}"
+    check(_lib.load().polus_cast(_dt("cast", "src", src), ptr(src), _dt("cast", "dst", dst), ptr(dst), n, _st()),
           "polus_cast")
 
 
 def scale_(x, a):
+    """x *= a in place; x contiguous f32 of any shape."""
     _req_cuda(x)
+    assert x.dtype == _F32T and x.is_contiguous(), f"scale_: x must be contiguous f32 {_got(x)}"
     check(_lib.load().polus_scale(ptr(x), float(a), x.numel(), _st()), "polus_scale")
 
 
 def act_bwd(dy, u, du, act):
+    """du = dy * act'(u) element by element: three contiguous tensors of one dtype, f32 or bf16, and one size."""
     _req_cuda(dy, u, du)
-    assert dy.numel() == u.numel() == du.numel() and dy.is_contiguous() and u.is_contiguous() and du.is_contiguous()
-    check(_lib.load().polus_act_bwd(dtype_code(dy.dtype), ptr(dy), ptr(u), ptr(du), dy.numel(),
+    n = dy.numel()
+    dt = dy.dtype
+    assert dy.is_contiguous(), f"act_bwd: dy must be contiguous {_got(dy)}"
+    assert u.dtype == dt and u.numel() == n and u.is_contiguous(), f"act_bwd: u must be contiguous {dt} with {n} elements {_got(u)}"
+    assert du.dtype == dt and du.numel() == n and du.is_contiguous(), f"act_bwd: du must be contiguous {dt} with {n} elements {_got(du)}"
+    check(_lib.load().polus_act_bwd(_dt("act_bwd", "dy", dy), ptr(dy), ptr(u), ptr(du), n,
                                     ACT_CODES[act] if not isinstance(act, int) else act, _st()), "polus_act_bwd")
 
 
 def transpose_bf16(src, dst):
+    """dst [C, R] = the transpose of src [R, C]; both contiguous bf16, dst with src's number of elements."""
     _req_cuda(src, dst)
+    assert src.dtype == _BF16T and src.dim() == 2 and src.is_contiguous(), f"transpose_bf16: src must be contiguous bf16 [R, C] {_got(src)}"
     R, C = src.shape
-    assert src.dtype == torch.bfloat16 and dst.dtype == torch.bfloat16 and dst.numel() == src.numel()
-    assert src.is_contiguous() and dst.is_contiguous()
+    assert dst.dtype == _BF16T and dst.numel() == R * C and dst.is_contiguous(), \
+        f"transpose_bf16: dst must be contiguous bf16 with {R * C} elements {_got(dst)}"
     check(_lib.load().polus_transpose_bf16(ptr(src), ptr(dst), R, C, _st()), "polus_transpose_bf16")
 
 
@@ -1432,14 +1620,20 @@ def dense_bwd_params_grouped(problems, accumulate=False, split_k=1):
     db f32 [n_out] or None), ...] with one common T."""
     lib = _lib.load()
     T = problems[0][0].shape[0]
-    for dy, x, dw, db in problems:
+    dt0 = problems[0][0].dtype
+    for k, (dy, x, dw, db) in enumerate(problems):
         _req_cuda(dy, x, dw, db)
-        assert dy.dtype == x.dtype and dw.dtype == torch.float32 and dy.shape[0] == T and x.shape[0] == T
-        assert dy.stride(1) == 1 and x.stride(1) == 1 and dw.stride(1) == 1
+        assert dy.dtype == dt0 and dy.dim() == 2 and dy.shape[0] == T and dy.stride(1) == 1, \
+            f"dense_bwd_params_grouped: problems[{k}]: dy must be {dt0} [{T}, n_out] with a unit inner stride {_got(dy)}"
+        assert x.dtype == dt0 and x.dim() == 2 and x.shape[0] == T and x.stride(1) == 1, \
+            f"dense_bwd_params_grouped: problems[{k}]: x must be {dt0} [{T}, n_in] with a unit inner stride {_got(x)}"
         n_out, n_in = dy.shape[1], x.shape[1]
-        assert tuple(dw.shape) == (n_out, n_in) and (db is None or (db.dtype == torch.float32 and db.numel() == n_out))
+        assert dw.dtype == _F32T and dw.shape == (n_out, n_in) and dw.stride(1) == 1, \
+            f"dense_bwd_params_grouped: problems[{k}]: dw must be f32 [{n_out}, {n_in}] with a unit inner stride {_got(dw)}"
+        if db is not None:
+            _vec("dense_bwd_params_grouped", f"problems[{k}]: db", db, _F32T, n_out)
     arr = _dw_problems(problems)
-    dt = dtype_code(problems[0][0].dtype)
+    dt = _dt("dense_bwd_params_grouped", "problems[0]: dy", problems[0][0])
     nb = lib.polus_dense_bwd_params_grouped_workspace_bytes(len(problems), arr, T, int(split_k))
     ws = workspace(problems[0][0].device).get(nb)
     prof = GEMM_PROFILE
@@ -1461,11 +1655,17 @@ def dense_thin_supported(dtype, H, C):
 def dense_thin_fwd(x, w, bias, y):
     """y [rows, C] = x [rows, H] . w [C, H]^T + bias; y in f32 or x's dtype."""
     _req_cuda(x, w, bias, y)
+    assert x.dim() == 2 and x.stride(1) == 1, f"dense_thin_fwd: x must be [rows, H] with a unit inner stride {_got(x)}"
     rows, H = x.shape
+    dt = x.dtype
+    assert w.dtype == dt and w.dim() == 2 and w.shape[1] == H and w.stride(1) == 1, \
+        f"dense_thin_fwd: w must be {dt} [C, {H}] with a unit inner stride {_got(w)}"
     C = w.shape[0]
-    assert w.dtype == x.dtype and w.shape[1] == H and y.shape == (rows, C)
-    assert x.stride(1) == 1 and w.stride(1) == 1 and y.stride(1) == 1
-    check(_lib.load().polus_dense_thin_fwd(dtype_code(x.dtype), ptr(x), x.stride(0), ptr(w), w.stride(0), ptr(bias),
+    if bias is not None:
+        _vec("dense_thin_fwd", "bias", bias, _F32T, C)
+    assert (y.dtype == dt or y.dtype == _F32T) and y.shape == (rows, C) and (y.stride(1) == 1 or C == 1), \
+        f"dense_thin_fwd: y must be f32 or {dt} [{rows}, {C}] with a unit inner stride {_got(y)}"
+    check(_lib.load().polus_dense_thin_fwd(_dt("dense_thin_fwd", "x", x), ptr(x), x.stride(0), ptr(w), w.stride(0), ptr(bias),
                                            dtype_code(y.dtype), ptr(y), y.stride(0), rows, H, C, _st()), "polus_dense_thin_fwd")
 
 
@@ -1473,21 +1673,38 @@ def dense_thin_bwd(x, dy, w, dx, dw, db, accumulate=False):
     """dx [rows, H] = dy . w (dx None: skipped), dw [C, H] (+)= dy^T x, db [C] (+)= colsum(dy): one pass over x."""
     lib = _lib.load()
     _req_cuda(x, dy, w, dx, dw, db)
+    assert x.dim() == 2 and x.stride(1) == 1, f"dense_thin_bwd: x must be [rows, H] with a unit inner stride {_got(x)}"
     rows, H = x.shape
+    dt = x.dtype
+    assert w.dtype == dt and w.dim() == 2 and w.shape[1] == H and w.stride(1) == 1, \
+        f"dense_thin_bwd: w must be {dt} [C, {H}] with a unit inner stride {_got(w)}"
     C = w.shape[0]
-    assert dy.shape == (rows, C) and dy.stride(1) == 1 and dw.dtype == torch.float32 and tuple(dw.shape) == (C, H) and dw.stride(1) == 1
-    assert dx is None or (dx.dtype == x.dtype and dx.shape == x.shape and dx.stride(1) == 1)
-    nb = lib.polus_dense_thin_bwd_workspace_bytes(dtype_code(x.dtype), rows, H, C)
+    assert (dy.dtype == dt or dy.dtype == _F32T) and dy.shape == (rows, C) and dy.stride(1) == 1, \
+        f"dense_thin_bwd: dy must be f32 or {dt} [{rows}, {C}] with a unit inner stride {_got(dy)}"
+    assert dw.dtype == _F32T and dw.shape == (C, H) and dw.stride(1) == 1, \
+        f"dense_thin_bwd: dw must be f32 [{C}, {H}] with a unit inner stride {_got(dw)}"
+    if dx is not None:
+        assert dx.dtype == dt and dx.shape == x.shape and dx.stride(1) == 1, \
+            f"dense_thin_bwd: dx must be {dt} {list(x.shape)} with a unit inner stride {_got(dx)}"
+    if db is not None:
+        _vec("dense_thin_bwd", "db", db, _F32T, C)
+    code = _dt("dense_thin_bwd", "x", x)
+    nb = lib.polus_dense_thin_bwd_workspace_bytes(code, rows, H, C)
     ws = workspace(x.device).get(nb)
-    check(lib.polus_dense_thin_bwd(dtype_code(x.dtype), ptr(x), x.stride(0), dtype_code(dy.dtype), ptr(dy), dy.stride(0),
+    check(lib.polus_dense_thin_bwd(code, ptr(x), x.stride(0), dtype_code(dy.dtype), ptr(dy), dy.stride(0),
                                    ptr(w), w.stride(0), ptr(dx), dx.stride(0) if dx is not None else 0, ptr(dw), dw.stride(0), ptr(db),
                                    rows, H, C, 1 if accumulate else 0, ptr(ws), ws.numel(), _st()), "polus_dense_thin_bwd")
 
 
 def transpose_bf16_batched(src_base, dst_base, segs_dev, nseg, total_tiles):
-    """All matrices of a flat bf16 arena into its transposed twin in one launch (segs: int64 [nseg, 4])."""
+    """All matrices of a flat bf16 arena into its transposed twin in one launch (segs: int64 [nseg, 4]); both arenas
+    contiguous bf16 of one size, segs_dev contiguous with at least 4 nseg elements."""
     _req_cuda(src_base, dst_base, segs_dev)
-    assert src_base.dtype == torch.bfloat16 and dst_base.dtype == torch.bfloat16 and segs_dev.dtype == torch.int64
+    assert src_base.dtype == _BF16T and src_base.is_contiguous(), f"transpose_bf16_batched: src_base must be contiguous bf16 {_got(src_base)}"
+    assert dst_base.dtype == _BF16T and dst_base.numel() >= src_base.numel() and dst_base.is_contiguous(), \
+        f"transpose_bf16_batched: dst_base must be contiguous bf16 with the {src_base.numel()} elements of src_base {_got(dst_base)}"
+    assert nseg > 0, f"transpose_bf16_batched: segs_dev: nseg must be positive (got {nseg})"
+    _vec("transpose_bf16_batched", "segs_dev", segs_dev, _I64T, 4 * nseg)
     check(_lib.load().polus_transpose_bf16_batched(ptr(src_base), ptr(dst_base), ptr(segs_dev), int(nseg), int(total_tiles), _st()),
           "polus_transpose_bf16_batched")
 
@@ -1496,17 +1713,22 @@ def dense_bwd_params(dy, x, dw, db, accumulate=False, split_k=1):
     """dW (+)= dY^T X and db (+)= colsum(dY) in one pass over dY."""
     lib = _lib.load()
     _req_cuda(dy, x, dw, db)
+    assert dy.dim() == 2 and dy.stride(1) == 1, f"dense_bwd_params: dy must be [T, n_out] with a unit inner stride {_got(dy)}"
     T, n_out = dy.shape
+    assert x.dtype == dy.dtype and x.dim() == 2 and x.shape[0] == T and x.stride(1) == 1, \
+        f"dense_bwd_params: x must be {dy.dtype} [{T}, n_in] with a unit inner stride {_got(x)}"
     n_in = x.shape[1]
-    assert x.shape[0] == T and dw.shape == (n_out, n_in) and dw.dtype == torch.float32
-    assert dy.stride(1) == 1 and x.stride(1) == 1 and dw.stride(1) == 1
+    assert dw.dtype == _F32T and dw.shape == (n_out, n_in) and dw.stride(1) == 1, \
+        f"dense_bwd_params: dw must be f32 [{n_out}, {n_in}] with a unit inner stride {_got(dw)}"
+    if db is not None:
+        _vec("dense_bwd_params", "db", db, _F32T, n_out)
     nb = lib.polus_dense_bwd_params_workspace_bytes(T, n_out, n_in, split_k)
     ws = workspace(dy.device).get(nb)
     prof = GEMM_PROFILE
     if prof is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    check(lib.polus_dense_bwd_params(dtype_code(dy.dtype), ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(dw), dw.stride(0),
+    check(lib.polus_dense_bwd_params(_dt("dense_bwd_params", "dy", dy), ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(dw), dw.stride(0),
                                      ptr(db), T, n_out, n_in, int(accumulate), split_k, ptr(ws), nb, _st()),
           "polus_dense_bwd_params")
     if prof is not None:
@@ -1515,9 +1737,13 @@ def dense_bwd_params(dy, x, dw, db, accumulate=False, split_k=1):
 
 
 def dropout(x, y, drop_p, seed):
+    """y = inverted dropout of x under the counter-based mask of `seed`; x and y contiguous, of one dtype (f32 or bf16) and
+    one size."""
     _req_cuda(x, y)
-    assert x.is_contiguous() and y.is_contiguous() and x.numel() == y.numel()
-    check(_lib.load().polus_dropout(dtype_code(x.dtype), ptr(x), ptr(y), x.numel(), float(drop_p), int(seed) & 0xFFFFFFFF, _st()),
+    assert x.is_contiguous(), f"dropout: x must be contiguous {_got(x)}"
+    assert y.dtype == x.dtype and y.numel() == x.numel() and y.is_contiguous(), \
+        f"dropout: y must be contiguous {x.dtype} with the {x.numel()} elements of x {_got(y)}"
+    check(_lib.load().polus_dropout(_dt("dropout", "x", x), ptr(x), ptr(y), x.numel(), float(drop_p), int(seed) & 0xFFFFFFFF, _st()),
           "polus_dropout")
 
 

@@ -1,11 +1,39 @@
 """CPU test doubles for the host-logic tests: a tiny NumPy softmax-regression 'model' that
 implements the model / loss / optimizer protocols the trainer drives (the oracle is the
-compute here — test infrastructure only)."""
+compute here — test infrastructure only), and a recording proxy over the real library for the
+wrapper-contract tests."""
 import numpy as np
 import torch
 
 from oracle import losses as ol
 from polus_amd.optimizers import _LearningRate
+
+
+class RecordingLib:
+    """A proxy over the real in-tree library for the wrapper-contract tests: the host-only functions (workspace sizes, route
+    reports, polus_last_error, polus_abi_version, ...) go to the real library; every other entry point is recorded as
+    (name, args) and answers POLUS_OK without touching the device."""
+    HOST_ONLY = ("_workspace_bytes", "_route", "_supported")
+    HOST_ONLY_NAMES = ("polus_last_error", "polus_abi_version")
+
+    def __init__(self, real):
+        self._real = real
+        self.calls = []
+
+    def __getattr__(self, name):
+        if not name.startswith("polus_"):
+            raise AttributeError(name)
+        if name.endswith(self.HOST_ONLY) or name in self.HOST_ONLY_NAMES:
+            return getattr(self._real, name)
+        getattr(self._real, name)                  # an entry point the library does not have is an error here too
+
+        def record(*args):
+            self.calls.append((name, args))
+            return 0
+        return record
+
+    def names(self):
+        return [n for n, _ in self.calls]
 
 
 class FakeArena:
