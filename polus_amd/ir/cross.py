@@ -26,6 +26,7 @@ import torch
 from .. import ops
 from ..callbacks import ValidationDataCallback
 from ..tensor import to_device
+from .store import RowStore, check_candidates, stored, stored_rows
 
 MAX_K = 1024                  # results per query: the limit of ops.topk_merge
 
@@ -55,29 +56,6 @@ def plan_buckets(lengths, tokens_per_batch, round_to=64, max_length=None):
         out.append((S, order[at:at + n]))
         at += n
     return out
-
-
-def check_candidates(candidates, Q, n_docs, dev):
-    """The candidate contract of CorpusIndex.rerank: an integer [Q, C] array of document ids padded with -1.  A host
-    array is checked (an id outside [-1, n_docs) raises ValueError) and copied over; a device tensor must be int32 and
-    is taken as it is, values unseen."""
-    if isinstance(candidates, torch.Tensor) and candidates.is_cuda:
-        cand = candidates
-        if cand.dtype != torch.int32:
-            raise ValueError(f"candidates on the device must be int32, the ids a search returns (got {cand.dtype})")
-        host = None
-    else:
-        host = candidates.numpy() if isinstance(candidates, torch.Tensor) else np.asarray(candidates)
-        if host.dtype.kind not in "iu":
-            raise ValueError(f"candidates must be integers (got {host.dtype})")
-        if host.size and (int(host.min()) < -1 or int(host.max()) >= n_docs):
-            raise ValueError(f"candidates must lie in [-1, {n_docs}) (got {int(host.min())} .. {int(host.max())})")
-        cand = host
-    if cand.ndim != 2 or cand.shape[0] != Q or cand.shape[1] < 1:
-        raise ValueError(f"candidates must be [{Q}, C] with C >= 1 (got {tuple(cand.shape)})")
-    if host is not None:
-        return torch.as_tensor(np.ascontiguousarray(host.astype(np.int32))).to(dev)
-    return cand if cand.stride(1) == 1 else cand.contiguous()
 
 
 class CrossEncoderIndex:
@@ -115,8 +93,9 @@ class CrossEncoderIndex:
         self.clear()
 
     def clear(self):
-        self._ids = self._mask = None
-        self._n = 0
+        self._store = RowStore()
+
+    _n, _ids, _mask = stored_rows, stored("ids"), stored("mask")
 
     def __len__(self):
         return self._n
@@ -137,20 +116,6 @@ class CrossEncoderIndex:
     def _device(self):
         return self.model.arena.device
 
-    def _grow(self, need, dev):
-        """Room for `need` documents: capacity doubles, the stored rows are copied over."""
-        cap = 0 if self._ids is None else self._ids.shape[0]
-        if need <= cap:
-            return
-        cap = max(need, 2 * cap)
-        # zeros: the padding of documents shorter than doc_tokens is never written, and its mask is 0
-        ids = torch.zeros((cap, self.doc_tokens), dtype=torch.int32, device=dev)
-        mask = torch.zeros((cap, self.doc_tokens), dtype=torch.int32, device=dev)
-        if self._n:
-            ids[:self._n].copy_(self._ids[:self._n])
-            mask[:self._n].copy_(self._mask[:self._n])
-        self._ids, self._mask = ids, mask
-
     def add(self, documents):
         """Append a batch {"input_ids" [n, L][, "attention_mask"]}; returns its ids, the consecutive int32 positions in
         the index (the numbering of CorpusIndex.add).  A batch wider than doc_tokens raises ValueError."""
@@ -164,8 +129,11 @@ class CrossEncoderIndex:
             self.doc_tokens = L
         if L > self.doc_tokens:
             raise ValueError(f"a document batch of {L} tokens does not fit the index's document length {self.doc_tokens}")
-        self._grow(self._n + n, dev)
+        if not self._store.fields:
+            # zeros: the padding of documents shorter than doc_tokens is never written, and its mask is 0
+            self._store.declare(ids=((self.doc_tokens,), torch.int32, 0), mask=((self.doc_tokens,), torch.int32, 0))
         a, b = self._n, self._n + n
+        self._store.reserve(b, dev)
         self._ids[a:b, :L].copy_(ids)
         if m is None:
             self._mask[a:b, :L].fill_(1)

@@ -26,8 +26,8 @@ synchronisation), idf and three constants in float64 rounded once to f32, one up
 ops.bm25_weights over all rows.  `search` refreshes a stale index first.
 
 Queries are counted by the same kernel (without df), turned into dense f32 [Q, V] rows tf_q idf (ops.bm25_query), and
-`search` is the chunk loop of SparseCorpusIndex.search over ops.sparse_scores and ops.topk_merge: its scores are the
-bits polus_sparse_scores gives for (q, terms, w), in slot order.
+`search` is the chunked scan every index shares (store.topk_scan) over ops.sparse_scores: its scores are the bits
+polus_sparse_scores gives for (q, terms, w), in slot order.
 
 Postings.  That search reads every slot of every document for every query.  `BM25Index(vocab_size, postings=True,
 block_docs=...)` searches block-inverted postings instead (polus_amd/ir/postings.py has the format and the score rule):
@@ -37,8 +37,8 @@ block_docs=...)` searches block-inverted postings instead (polus_amd/ir/postings
 
 `add` and `set_params` only mark the postings stale; `refresh_postings` rebuilds them from the stored (term id, weight)
 slots after a `refresh` (the weights change with N); queries are counted as before and become lists of (term, tf_q idf)
-in ascending id (ops.bm25_query_lists; no dense row, no synchronisation), and `search` is a chunk loop over
-ops.postings_scores and ops.topk_merge, whole blocks per launch.  The contract of `search` is the same; the scores are
+in ascending id (ops.bm25_query_lists; no dense row, no synchronisation), and `search` is the same scan over
+ops.postings_scores, whole blocks per launch.  The contract of `search` is the same; the scores are
 the bits of the postings score rule (products and sums in ascending term id, each rounded once), which differ from the
 forward route's fma chain in slot order by rounding.  The forward route is the default and keeps its bits.
 
@@ -54,8 +54,8 @@ import torch
 from .. import ops
 from ..tensor import device, to_device
 from .postings import MAX_POSTINGS_VOCAB, Postings, check_block_docs
+from .store import RowStore, score_chunks, stored, stored_rows, topk_scan
 
-MAX_CHUNK = 65535             # documents per launch, as in polus_amd/ir/search.py
 MAX_TERMS = 1024              # slots per document: what ops.sparse_scores accepts
 MAX_TOKENS = 2048             # tokens per row: the limit of ops.bm25_term_counts
 MAX_VOCAB = 163840 // 4       # the dense query row ops.sparse_scores holds in LDS
@@ -114,11 +114,9 @@ class BM25Index:
 
     def clear(self):
         """Empty the index (the storage and the statistics are released)."""
-        self._terms = self._tf = self._w = self._len = self._stat = self._idf = None
-        self._n, self._stale = 0, False
+        self._store, self._stat, self._idf, self._stale = RowStore(), None, None, False
         if self._postings is not None:
             self._postings.clear()
-        self._postings_stale = False
         if self._auto_terms:
             self.terms = None
 
@@ -129,9 +127,18 @@ class BM25Index:
         """New k1 and b for the documents already stored: only marks the index stale, the counts are kept."""
         self._check_params(k1, b)
         self.k1, self.b = float(k1), float(b)
-        self._stale = self._postings_stale = self._n > 0
+        if self._n:
+            self._mark_stale()
+
+    def _mark_stale(self):
+        self._stale = True
+        if self._postings is not None:
+            self._postings.stale = True
 
     # ------------------------------------------------------------ storage
+    _n, _terms, _tf, _w, _len = stored_rows, stored("terms"), stored("tf"), stored("w"), stored("len")
+    _postings_stale = property(lambda self: self._postings is not None and self._postings.stale)
+
     @property
     def _df(self):
         return self._stat[6:]
@@ -139,20 +146,6 @@ class BM25Index:
     @property
     def _counters(self):
         return self._stat[:6].view(torch.int64)
-
-    def _grow(self, need, dev):
-        cap = 0 if self._terms is None else self._terms.shape[0]
-        if need <= cap:
-            return
-        cap = max(need, 2 * cap)
-        new = (torch.full((cap, self.terms), -1, dtype=torch.int32, device=dev),
-               torch.zeros((cap, self.terms), dtype=torch.int32, device=dev),
-               torch.zeros((cap, self.terms), dtype=torch.float32, device=dev),
-               torch.zeros((cap,), dtype=torch.int32, device=dev))
-        if self._n:
-            for dst, src in zip(new, (self._terms, self._tf, self._w, self._len)):
-                dst[:self._n].copy_(src[:self._n])
-        self._terms, self._tf, self._w, self._len = new
 
     @staticmethod
     def _rows(batch, what):
@@ -176,11 +169,15 @@ class BM25Index:
         if self._stat is None:
             # one buffer, so that a refresh is one copy: the three int64 counters, then df
             self._stat = torch.zeros(6 + self.vocab_size, dtype=torch.int32, device=dev)
-        self._grow(self._n + n, dev)
+            slots = (self.terms,)
+            self._store.declare(terms=(slots, torch.int32, -1), tf=(slots, torch.int32, 0), w=(slots, torch.float32, 0),
+                                len=((), torch.int32, 0))
         a, b = self._n, self._n + n
+        self._store.reserve(b, dev)
         ops.bm25_term_counts(ids, mask, self._terms[a:b], self._tf[a:b], self._len[a:b], self.vocab_size, self.strip,
                              df=self._df, stats=self._counters)
-        self._n, self._stale, self._postings_stale = b, True, True
+        self._n = b
+        self._mark_stale()
         return torch.arange(a, b, dtype=torch.int32, device=dev)
 
     def _host_stats(self):
@@ -208,9 +205,12 @@ class BM25Index:
             raise ValueError("this index was made with postings=False")
         if self._n == 0:
             raise ValueError("the index is empty: add documents before refreshing")
+        self._postings.build(*self._forward())
+
+    def _forward(self):
+        """What the postings are built from: the stored (term id, weight) slots, the weights refreshed first."""
         self._fresh()
-        self._postings.build(self._terms[:self._n], self._w[:self._n], self.vocab_size)
-        self._postings_stale = False
+        return self._terms[:self._n], self._w[:self._n], self.vocab_size
 
     @property
     def postings(self):
@@ -218,9 +218,7 @@ class BM25Index:
         stale; None without postings=True or on an empty index."""
         if self._postings is None or self._n == 0:
             return None
-        if self._postings_stale or not self._postings.built:
-            self.refresh_postings()
-        return self._postings.arrays()
+        return self._postings.update(self._forward).arrays()
 
     # ------------------------------------------------------------ views
     @property
@@ -274,12 +272,8 @@ class BM25Index:
 
     # ------------------------------------------------------------ search
     def chunks(self, Q):
-        """[(start, stop), ...]: the document ranges a search with Q queries scores, one launch each (CorpusIndex.chunks)."""
-        per = min(MAX_CHUNK, self.scratch_bytes // (4 * int(Q)))
-        if per < 1:
-            raise ValueError(f"scratch_bytes = {self.scratch_bytes} does not hold the scores of one document for "
-                             f"{Q} queries ({4 * int(Q)} bytes)")
-        return [(s, min(s + per, self._n)) for s in range(0, self._n, per)]
+        """[(start, stop), ...]: the document ranges a search with Q queries scores, one launch each (store.score_chunks)."""
+        return score_chunks(self._n, Q, self.scratch_bytes, "document")
 
     def encode_queries(self, queries):
         """The queries' dense f32 [Q, V] rows: tf_q(t) * idf(t) at the query's terms, 0 elsewhere.  A query row holds at
@@ -326,23 +320,14 @@ class BM25Index:
         if self._n == 0:
             raise ValueError("the index is empty: add documents before searching")
         if self._postings is not None:
-            q_terms, q_w, q_count = self.encode_query_lists(queries)
-            if self._postings_stale or not self._postings.built:
-                self.refresh_postings()
-            return self._postings.search(q_terms, q_w, q_count, k, self.scratch_bytes)
+            lists = self.encode_query_lists(queries)
+            return self._postings.update(self._forward).search(*lists, k, self.scratch_bytes)
         return self.search_forward(queries, k)
 
     def search_forward(self, queries, k):
         """`search` on the forward route, whatever `postings` says (tools/postings_bench.py compares the two routes of
         one index with it); needs vocab_size <= 40960."""
         q = self.encode_queries(queries)
-        Q = q.shape[0]
-        spans = self.chunks(Q)
-        scratch = torch.empty((Q, max(b - a for a, b in spans)), dtype=torch.float32, device=q.device)
-        top_val = torch.empty((Q, int(k)), dtype=torch.float32, device=q.device)
-        top_id = torch.empty((Q, int(k)), dtype=torch.int32, device=q.device)
-        for a, b in spans:
-            s = scratch[:, :b - a]
-            ops.sparse_scores(q, self._terms[a:b], self._w[a:b], s)
-            ops.topk_merge(s, top_val, top_id, id0=a, init=(a == 0))
-        return top_val, top_id
+        terms, w = self._terms, self._w
+        return topk_scan(q.shape[0], k, self.chunks(q.shape[0]), q.device,
+                         lambda a, b, s: ops.sparse_scores(q, terms[a:b], w[a:b], s))

@@ -17,14 +17,16 @@ so the two routes agree bit for bit only where every sum is exact; otherwise the
 
 Build: ops.postings_count -> ops.postings_offsets -> one 8-byte copy of base[nblk] to the host, which sizes the arrays
 -> ops.postings_fill.  A full rebuild per refresh; counts and cursor are one scratch buffer of nblk * V int32, released
-afterwards.  Search: a chunk loop over ops.postings_scores and ops.topk_merge; a chunk is as many whole blocks as fit
-`scratch_bytes`.
+afterwards.  Search: the chunked scan of the other indexes (store.topk_scan) over ops.postings_scores; a chunk is as many
+whole blocks as fit `scratch_bytes`.  The owning index marks the postings `stale` when its forward arrays change, and
+`update` rebuilds them before the next use.
 
 Arithmetic is hand-written HIP (ops.postings_* / sparse_compact_rows / bm25_query_lists / topk_merge); torch
 allocates, views and copies."""
 import torch
 
 from .. import ops
+from .store import topk_scan
 
 MIN_BLOCK_DOCS, MAX_BLOCK_DOCS = 64, 32768
 MAX_POSTINGS_VOCAB = (1 << 31) - 2
@@ -58,6 +60,7 @@ class Postings:
     def clear(self):
         self.offsets = self.base = self.post_doc = self.post_w = None
         self.n_docs = self.vocab = self.count = 0
+        self.stale = False
 
     @property
     def built(self):
@@ -71,6 +74,12 @@ class Postings:
 
     def arrays(self):
         return self.offsets, self.base, self.post_doc, self.post_w
+
+    def update(self, forward):
+        """Bring the postings up to date: `build` from forward() = (ids, w, V) when they are stale or were never built."""
+        if self.stale or not self.built:
+            self.build(*forward())
+        return self
 
     def build(self, ids, w, V):
         """Rebuild from the forward arrays ids int32 / w f32 [N, M] (views of the index's storage)."""
@@ -88,19 +97,14 @@ class Postings:
         post_w = torch.empty((P,), dtype=torch.float32, device=dev)
         ops.postings_fill(ids, w, bd, offsets, base, scratch, post_doc, post_w)
         self.offsets, self.base, self.post_doc, self.post_w = offsets, base, post_doc, post_w
-        self.n_docs, self.vocab, self.count = N, int(V), P
+        self.n_docs, self.vocab, self.count, self.stale = N, int(V), P, False
 
     def search(self, q_terms, q_w, q_count, k, scratch_bytes):
         """(scores f32 [Q, k], ids int32 [Q, k]) of the query lists over the built postings."""
         Q, bd, N = q_terms.shape[0], self.block_docs, self.n_docs
-        spans = block_chunks(N, Q, bd, scratch_bytes)
-        width = min(N, max(n for _, n in spans) * bd)
-        scratch = torch.empty((Q, width), dtype=torch.float32, device=q_terms.device)
-        top_val = torch.empty((Q, int(k)), dtype=torch.float32, device=q_terms.device)
-        top_id = torch.empty((Q, int(k)), dtype=torch.int32, device=q_terms.device)
-        for b0, nb in spans:
-            a = b0 * bd
-            s = scratch[:, :min(nb * bd, N - a)]
-            ops.postings_scores(q_terms, q_w, q_count, self.offsets, self.base, self.post_doc, self.post_w, bd, b0, nb, N, s)
-            ops.topk_merge(s, top_val, top_id, id0=a, init=(b0 == 0))
-        return top_val, top_id
+        spans = [(b0 * bd, min((b0 + nb) * bd, N)) for b0, nb in block_chunks(N, Q, bd, scratch_bytes)]
+
+        def score(a, b, s):
+            ops.postings_scores(q_terms, q_w, q_count, self.offsets, self.base, self.post_doc, self.post_w, bd, a // bd,
+                                (b - a + bd - 1) // bd, N, s)
+        return topk_scan(Q, k, spans, q_terms.device, score)

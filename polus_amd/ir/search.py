@@ -80,8 +80,8 @@ from .. import ops
 from ..callbacks import ValidationDataCallback
 from .models import TokenReps
 from .postings import Postings, check_block_docs
+from .store import RowStore, check_candidates, score_chunks, stored, stored_rows, topk_scan
 
-MAX_CHUNK = 65535             # documents per launch: the MaxSim grid's limit, kept on the dot path too
 MAX_K = 1024                  # results per query: the limit of ops.topk_merge
 MAX_CENTROIDS = 65535         # codes are 16 bits and 0xFFFF is "no token"
 ASSIGN_ROWS = 16384           # tokens per nearest-centroid GEMM, at most (see CorpusIndex._assign_rows)
@@ -111,6 +111,180 @@ class ResidualCodec:
         if not bool((cut[1:] >= cut[:-1]).all()) or bool(torch.isnan(cut).any()):
             raise ValueError("cutoffs must be non-decreasing (and not NaN)")
         self.centroids, self.cutoffs, self.weights, self.nbits = c, cut, w, int(nbits)
+
+
+class _ClsVectors:
+    """What a CorpusIndex stores, chosen once (from `storage`, or at the first `add`).  A kind declares its fields of the
+    index's RowStore, writes a projected batch, gives `search` the callback that scores a span of documents
+    (store.topk_scan) and, for tokens, `rerank` the one that scores a span of candidate columns, returns
+    `representations`, reads stored tokens back as vectors for the centroid code, and states the bytes of one document
+    `search` decodes into scratch.  This one: [CLS] vectors [N, E] in the model's dtype, a span scored by one GEMM."""
+    decoded_bytes = 0
+
+    def __init__(self, ix):
+        self.ix, self.store = ix, ix._store
+
+    def fields(self, v):
+        return dict(reps=(v.shape[1:], v.dtype, 0))
+
+    def _room(self, v):
+        """Rows a .. b for the batch v: the fields are declared by the first batch, the buffers hold b rows."""
+        st = self.store
+        if not st.fields:
+            st.declare(**self.fields(v))       # fill 0: the padding of documents shorter than the index's length is never written
+        st.reserve(st.n + v.shape[0], v.device)
+        self.dtype = v.dtype
+        return st.n, st.n + v.shape[0]
+
+    def write(self, v, m):
+        a, b = self._room(v)
+        self.store.bufs["reps"][a:b].copy_(v)
+
+    def scorer(self, q):
+        reps = self.store.bufs["reps"]
+        return lambda a, b, s: ops.gemm(q, reps[a:b], s)
+
+    def representations(self):
+        return self.store.view("reps")
+
+
+class _Tokens(_ClsVectors):
+    """Token vectors [N, Ld, E] in the model's dtype with their int32 mask [N, Ld]."""
+
+    def fields(self, v):
+        return dict(reps=((self.ix._ld, v.shape[2]), v.dtype, 0), mask=((self.ix._ld,), torch.int32, 0))
+
+    def write(self, v, m):
+        a, b = self._room(v)
+        self.store.bufs["mask"][a:b, :v.shape[1]].copy_(m)
+        self.put(a, b, v)
+        if self.ix._centroids is not None:
+            self.ix._assign(a, b)
+
+    def put(self, a, b, v):
+        self.store.bufs["reps"][a:b, :v.shape[1]].copy_(v)
+
+    def scorer(self, q):
+        reps, mask = self.store.bufs["reps"], self.store.bufs["mask"]
+        return lambda a, b, s: ops.maxsim_scores(q.values, reps[a:b], q.mask, mask[a:b], s)
+
+    def reranker(self, q, cand):
+        reps, mask = self.store.view("reps"), self.store.view("mask")
+        return lambda a, b, s: ops.maxsim_rerank(q.values, reps, q.mask, mask, cand[:, a:b], s)
+
+    def loader(self, a, b):
+        """load(s, e, dst) of CorpusIndex._assign_rows over the tokens of documents a .. b."""
+        flat = self.store.bufs["reps"][a:b].view(-1, self.store.bufs["reps"].shape[2])
+        return lambda s, e, dst: dst.copy_(flat[s:e])
+
+    def gather(self, at):
+        """The stored token slots `at` (int64 on the device; slot = document * Ld + position) as vectors [len(at), E]."""
+        reps = self.store.view("reps")
+        return reps.view(-1, reps.shape[2])[at].contiguous()
+
+
+class _Fp8Tokens(_Tokens):
+    """e4m3fn codes uint8 [N, Ld, E] and power-of-two scales f32 [N, Ld]; scored as they are, read back dequantised."""
+
+    def fields(self, v):
+        Ld = self.ix._ld
+        return dict(reps=((Ld, v.shape[2]), torch.uint8, 0), mask=((Ld,), torch.int32, 0), scale=((Ld,), torch.float32, 0))
+
+    def put(self, a, b, v):
+        v = v.contiguous()
+        codes = torch.empty(v.shape, dtype=torch.uint8, device=v.device)
+        scale = torch.empty(v.shape[:-1], dtype=torch.float32, device=v.device)
+        ops.fp8_quantize(v, codes, scale)
+        self.store.bufs["scale"][a:b, :v.shape[1]].copy_(scale)
+        self.store.bufs["reps"][a:b, :v.shape[1]].copy_(codes)
+
+    def scorer(self, q):
+        reps, scale, mask = (self.store.bufs[f] for f in ("reps", "scale", "mask"))
+        return lambda a, b, s: ops.maxsim_scores_fp8(q.values, reps[a:b], scale[a:b], q.mask, mask[a:b], s)
+
+    def reranker(self, q, cand):
+        reps, scale, mask = (self.store.view(f) for f in ("reps", "scale", "mask"))
+        return lambda a, b, s: ops.maxsim_rerank_fp8(q.values, reps, scale, q.mask, mask, cand[:, a:b], s)
+
+    def _dequantized(self, codes, scale):
+        y = torch.empty(codes.shape, dtype=self.dtype, device=codes.device)
+        if codes.shape[0]:
+            ops.fp8_dequantize(codes, scale, y)
+        return y
+
+    def representations(self):
+        return self._dequantized(self.store.view("reps"), self.store.view("scale"))
+
+    def loader(self, a, b):
+        reps = self.store.bufs["reps"][a:b].view(-1, self.store.bufs["reps"].shape[2])
+        scale = self.store.bufs["scale"][a:b].view(-1)
+        return lambda s, e, dst: ops.fp8_dequantize(reps[s:e], scale[s:e], dst)
+
+    def gather(self, at):
+        reps = self.store.view("reps")
+        return self._dequantized(reps.view(-1, reps.shape[2])[at].contiguous(), self.store.view("scale").view(-1)[at].contiguous())
+
+
+class _ResidualTokens(_Tokens):
+    """The codec's centroid codes int16 [N, Ld] and residual bits uint8 [N, Ld, E * nbits / 8]; reranked as they are.
+    `search` has no kernel over residual bits (search_pruned never reads them in bulk): it decodes a span into scratch
+    and runs the plain kernel.  Centroids cannot be set again, so nothing reads the tokens back (no loader, no gather)."""
+
+    def fields(self, v):
+        Ld = self.ix._ld
+        return dict(reps=((Ld, v.shape[2] * self.ix.codec.nbits // 8), torch.uint8, 0), mask=((Ld,), torch.int32, 0),
+                    codes=((Ld,), torch.int16, -1))                              # 0xFFFF: no token
+
+    def write(self, v, m):
+        """v [n, L, E] projected and normalised, m its mask.  The batch is padded to the index's length, its tokens get
+        their codes by _assign_rows (the rule a plain index with these centroids follows in `add`) and
+        ops.residual_compress writes the bits into the storage."""
+        ix, codec = self.ix, self.ix.codec
+        n, L, E = v.shape
+        if codec.centroids.shape[1] != E:
+            raise ValueError(f"the codec's centroids have {codec.centroids.shape[1]} features, the model's tokens {E}")
+        if ix._centroids is None:
+            ix._centroids = codec.centroids.to(device=v.device, dtype=v.dtype).contiguous().clone()
+            ix._cutoffs, ix._weights = codec.cutoffs.to(v.device), codec.weights.to(v.device)
+        a, b = self._room(v)
+        mask = self.store.bufs["mask"][a:b]
+        mask[:, :L].copy_(m)
+        if L < ix._ld:
+            x = torch.zeros((n, ix._ld, E), dtype=v.dtype, device=v.device)
+            x[:, :L].copy_(v)
+        else:
+            x = v.contiguous()
+        flat = x.view(-1, E)
+        codes = self.store.bufs["codes"][a:b].view(-1)
+        ix._assign_rows(lambda s, e, dst: dst.copy_(flat[s:e]), n * ix._ld, mask.view(-1), codes, ix._centroids)
+        ops.residual_compress(x, codes, ix._centroids, ix._cutoffs, codec.nbits, self.store.bufs["reps"][a:b])
+
+    @property
+    def decoded_bytes(self):
+        return self.ix._ld * self.ix._centroids.shape[1] * self.ix._centroids.element_size()
+
+    def decoded(self, a, b, out=None):
+        """Documents a .. b decoded into `out` (or a new tensor) [b - a, Ld, E]."""
+        ix, bufs = self.ix, self.store.bufs
+        y = out if out is not None else torch.empty((b - a, ix._ld, ix._centroids.shape[1]), dtype=self.dtype,
+                                                    device=ix._centroids.device)
+        if b > a:
+            ops.residual_decompress(bufs["codes"][a:b], bufs["reps"][a:b], ix._centroids, ix._weights, ix.codec.nbits, y)
+        return y
+
+    def representations(self):
+        return self.decoded(0, self.store.n)
+
+    def scorer(self, q):
+        mask = self.store.bufs["mask"]
+        width = max(b - a for a, b in self.ix.chunks(q.values.shape[0], decode=True))
+        dec = torch.empty((width, self.ix._ld, q.values.shape[2]), dtype=self.dtype, device=q.values.device)
+        return lambda a, b, s: ops.maxsim_scores(q.values, self.decoded(a, b, dec[:b - a]), q.mask, mask[a:b], s)
+
+    def reranker(self, q, cand):
+        ix, codes, reps, mask = self.ix, self.store.view("codes"), self.store.view("reps"), self.store.view("mask")
+        return lambda a, b, s: ops.maxsim_rerank_res(q.values, codes, reps, ix._centroids, ix._weights, ix.codec.nbits,
+                                                     q.mask, mask, cand[:, a:b], s)
 
 
 class CorpusIndex:
@@ -148,12 +322,14 @@ class CorpusIndex:
     def clear(self):
         """Empty the index (the storage is released; the next `add` fixes the document length again).  A residual
         index keeps its codec."""
-        self._reps = self._mask = self._scale = None
-        self._codes = self._centroids = None          # centroid codes int16 [cap, Ld] and centroids [K, E]
+        self._store = RowStore()
+        self._kind = {"fp8": _Fp8Tokens, "residual": _ResidualTokens}[self.storage](self) if self.storage else None
+        self._centroids = None                        # [K, E]; the codes are the store's int16 [cap, Ld] field
         self._cutoffs = self._weights = None          # a residual index: the codec's tables on the device
         self._lists, self._lists_stale = None, False  # inverted lists (offsets, docs) of refresh_lists
-        self._n = 0
         self.tokens = None            # True: token representations; fixed by the first add
+
+    _n, _reps, _mask, _scale, _codes = stored_rows, stored("reps"), stored("mask"), stored("scale"), stored("codes")
 
     def __len__(self):
         return self._n
@@ -162,39 +338,22 @@ class CorpusIndex:
     def representations(self):
         """[N, E] or [N, Ld, E]: a view of the stored documents.  On an FP8 index a COPY: the codes dequantised into
         a new tensor of the model's dtype (exactly codes * scales); writing to it does not change the index."""
-        if self._reps is None:
-            return None
-        if self.storage == "fp8":
-            y = torch.empty(self._reps[:self._n].shape, dtype=self._dtype, device=self._reps.device)
-            if self._n:
-                ops.fp8_dequantize(self._reps[:self._n], self._scale[:self._n], y)
-            return y
-        if self.storage == "residual":
-            return self._decoded(0, self._n)
-        return self._reps[:self._n]
-
-    def _decoded(self, a, b, out=None):
-        """Documents a .. b of a residual index, decoded into `out` (or a new tensor) [b - a, Ld, E]."""
-        E = self._centroids.shape[1]
-        y = torch.empty((b - a, self._ld, E), dtype=self._dtype, device=self._reps.device) if out is None else out
-        if b > a:
-            ops.residual_decompress(self._codes[a:b], self._reps[a:b], self._centroids, self._weights, self.codec.nbits, y)
-        return y
+        return None if self._reps is None else self._kind.representations()
 
     @property
     def residuals(self):
         """uint8 [N, Ld, E * nbits / 8]: a view of the stored residual bits (a residual index; None otherwise)."""
-        return None if self.storage != "residual" or self._reps is None else self._reps[:self._n]
+        return None if self.storage != "residual" else self._store.view("reps")
 
     @property
     def codes(self):
         """uint8 [N, Ld, E]: a view of the stored e4m3fn codes (an FP8 index; None otherwise)."""
-        return None if self.storage != "fp8" or self._reps is None else self._reps[:self._n]
+        return None if self.storage != "fp8" else self._store.view("reps")
 
     @property
     def scales(self):
         """f32 [N, Ld]: a view of the stored per-token scales, exact powers of two (an FP8 index; None otherwise)."""
-        return None if self._scale is None else self._scale[:self._n]
+        return self._store.view("scale")
 
     @property
     def centroids(self):
@@ -208,18 +367,18 @@ class CorpusIndex:
     def centroid_codes(self):
         """int16 [N, Ld]: a view of the stored tokens' nearest-centroid ids; the 16 bits are the unsigned code, so -1
         is 0xFFFF, "no token" (None before centroids exist)."""
-        return None if self._codes is None else self._codes[:self._n]
+        return self._store.view("codes")
 
     @property
     def nbytes(self):
         """Bytes of the stored representations, scales, mask and centroid codes of the len(index) documents, and of
         the inverted lists once a probed search has built them (4 (K + 1) + 4 P)."""
-        return sum(t[:self._n].numel() * t.element_size() for t in (self._reps, self._scale, self._mask, self._codes)
-                   if t is not None) + sum(t.numel() * t.element_size() for t in self._lists or ())
+        return sum(t[:self._n].numel() * t.element_size() for t in self._store.bufs.values()) + sum(
+            t.numel() * t.element_size() for t in self._lists or ())
 
     @property
     def mask(self):
-        return None if self._mask is None else self._mask[:self._n]
+        return self._store.view("mask")
 
     def _l2norm(self, x):
         y = torch.empty_like(x)
@@ -239,32 +398,6 @@ class CorpusIndex:
                              "model's dtype")
         return tokens
 
-    def _grow(self, need, like, tail):
-        """Room for `need` documents in one buffer: capacity doubles, the stored rows are copied over."""
-        cap = 0 if self._reps is None else self._reps.shape[0]
-        if need <= cap:
-            return
-        cap = max(need, 2 * cap)
-        # zeros: the padding of documents shorter than the index's length is never written
-        fp8, res = self.storage == "fp8", self.storage == "residual"
-        if res:
-            tail = (tail[0], tail[1] * self.codec.nbits // 8)
-        reps = torch.zeros((cap,) + tail, dtype=torch.uint8 if fp8 or res else like.dtype, device=like.device)
-        mask = torch.zeros((cap, tail[0]), dtype=torch.int32, device=like.device) if self.tokens else None
-        scale = torch.zeros((cap, tail[0]), dtype=torch.float32, device=like.device) if fp8 else None
-        if self._n:
-            reps[:self._n].copy_(self._reps[:self._n])
-            if mask is not None:
-                mask[:self._n].copy_(self._mask[:self._n])
-            if scale is not None:
-                scale[:self._n].copy_(self._scale[:self._n])
-        if self._codes is not None or res:
-            codes = torch.full((cap, tail[0]), -1, dtype=torch.int16, device=like.device)         # 0xFFFF: no token
-            if self._codes is not None:
-                codes[:self._n].copy_(self._codes[:self._n])
-            self._codes = codes
-        self._reps, self._mask, self._scale = reps, mask, scale
-
     def add(self, documents):
         """Encode, project (and normalise) a batch of documents and append it; returns its ids, the consecutive int32
         positions in the index.  Token documents are padded with masked tokens to the length of the first batch;
@@ -272,86 +405,33 @@ class CorpusIndex:
         residual index gives them their nearest centroid of the codec and compresses them."""
         model = self.model
         rep = model.document_projection(model.encode_document(documents, training=False), training=False)
-        tokens = self._check_kind(rep)
-        if tokens:
+        if self._check_kind(rep):
             v, m = rep.values, rep.mask
             if self.normalize:
                 v = self._l2norm(v.contiguous())
-            n, L, E = v.shape
+            L = v.shape[1]
             if self.tokens is None:
                 self.tokens, self._ld = True, L
             if L > self._ld:
                 raise ValueError(f"a document batch of {L} tokens does not fit the index's document length {self._ld} "
                                  "(fixed by the first add)")
-            if self.storage == "residual":
-                self._add_residual(v, m)
-                return self._ids(n, v.device)
-            self._grow(self._n + n, v, (self._ld, E))
-            if self.storage == "fp8":
-                self._dtype = v.dtype
-                v = v.contiguous()
-                codes = torch.empty(v.shape, dtype=torch.uint8, device=v.device)
-                scale = torch.empty(v.shape[:-1], dtype=torch.float32, device=v.device)
-                ops.fp8_quantize(v, codes, scale)
-                self._scale[self._n:self._n + n, :L].copy_(scale)
-                v = codes
-            self._reps[self._n:self._n + n, :L].copy_(v)
-            self._mask[self._n:self._n + n, :L].copy_(m)
-            if self._centroids is not None:
-                self._assign(self._n, self._n + n)
         else:
-            v = rep if self.post_process_logits is None else self.post_process_logits(rep)
-            n, E = v.shape
+            v, m = rep if self.post_process_logits is None else self.post_process_logits(rep), None
             self.tokens = False
-            self._grow(self._n + n, v, (E,))
-            self._reps[self._n:self._n + n].copy_(v)
-        return self._ids(n, v.device)
-
-    def _ids(self, n, dev):
-        ids = torch.arange(self._n, self._n + n, dtype=torch.int32, device=dev)
-        self._n += n
+        if self._kind is None:
+            self._kind = (_Tokens if self.tokens else _ClsVectors)(self)
+        self._kind.write(v, m)
+        ids = torch.arange(self._n, self._n + v.shape[0], dtype=torch.int32, device=v.device)
+        self._n += v.shape[0]
         self._lists_stale = True
         return ids
 
-    def _add_residual(self, v, m):
-        """`add` on a residual index: v [n, L, E] projected and normalised, m its mask.  The batch is padded to the
-        index's length, its tokens get their codes by _assign_rows (the rule a plain index with these centroids
-        follows in `add`) and ops.residual_compress writes the bits into the storage."""
-        n, L, E = v.shape
-        codec = self.codec
-        if codec.centroids.shape[1] != E:
-            raise ValueError(f"the codec's centroids have {codec.centroids.shape[1]} features, the model's tokens {E}")
-        if self._centroids is None:
-            self._dtype = v.dtype
-            self._centroids = codec.centroids.to(device=v.device, dtype=v.dtype).contiguous().clone()
-            self._cutoffs, self._weights = codec.cutoffs.to(v.device), codec.weights.to(v.device)
-        self._grow(self._n + n, v, (self._ld, E))
-        a, b = self._n, self._n + n
-        self._mask[a:b, :L].copy_(m)
-        if L < self._ld:
-            x = torch.zeros((n, self._ld, E), dtype=v.dtype, device=v.device)
-            x[:, :L].copy_(v)
-        else:
-            x = v.contiguous()
-        flat = x.view(-1, E)
-        codes = self._codes[a:b].view(-1)
-        self._assign_rows(lambda s, e, dst: dst.copy_(flat[s:e]), n * self._ld, self._mask[a:b].view(-1), codes, self._centroids)
-        ops.residual_compress(x, codes, self._centroids, self._cutoffs, codec.nbits, self._reps[a:b])
-
     def chunks(self, Q, decode=False):
         """[(start, stop), ...]: the document ranges a search with Q queries scores, one launch each: at most 65535
-        documents, and at most as many as keep the [Q, n] f32 scores within scratch_bytes.  decode=True (the `search` of
-        a residual index): the chunk's decoded vectors [n, Ld, E] stay within scratch_bytes as well."""
-        per = min(MAX_CHUNK, self.scratch_bytes // (4 * int(Q)))
-        if per < 1:
-            raise ValueError(f"scratch_bytes = {self.scratch_bytes} does not hold the scores of one document for "
-                             f"{Q} queries ({4 * int(Q)} bytes)")
-        if decode and self._n:
-            doc = self._ld * self._centroids.shape[1] * self._centroids.element_size()
-            if self.scratch_bytes < doc:
-                raise ValueError(f"scratch_bytes = {self.scratch_bytes} does not hold one decoded document ({doc} bytes)")
-            per = min(per, self.scratch_bytes // doc)
-        return [(s, min(s + per, self._n)) for s in range(0, self._n, per)]
+        documents, and at most as many as keep the [Q, n] f32 scores within scratch_bytes (store.score_chunks).
+        decode=True (what `search` asks for): on a residual index the chunk's decoded vectors [n, Ld, E] stay within
+        scratch_bytes as well."""
+        return score_chunks(self._n, Q, self.scratch_bytes, "document", self._kind.decoded_bytes if decode and self._n else 0)
 
     def encode_queries(self, queries):
         """The query side of the trainer: encode_query, query_projection, then the normalisation (tokens) or
@@ -369,35 +449,12 @@ class CorpusIndex:
             raise ValueError("the index is empty: add documents before searching")
         q = self.encode_queries(queries)
         qv = q.values if self.tokens else q
-        Q = qv.shape[0]
-        res = self.storage == "residual"
-        spans = self.chunks(Q, decode=res)
-        scratch = torch.empty((Q, max(b - a for a, b in spans)), dtype=torch.float32, device=qv.device)
-        top_val = torch.empty((Q, int(k)), dtype=torch.float32, device=qv.device)
-        top_id = torch.empty((Q, int(k)), dtype=torch.int32, device=qv.device)
-        if res:       # no exhaustive kernel over residual bits (search_pruned never reads them in bulk): decode, then the plain one
-            dec = torch.empty((max(b - a for a, b in spans), self._ld, qv.shape[2]), dtype=self._dtype, device=qv.device)
-        for a, b in spans:
-            s = scratch[:, :b - a]
-            if res:
-                ops.maxsim_scores(qv, self._decoded(a, b, dec[:b - a]), q.mask, self._mask[a:b], s)
-            elif self.storage == "fp8":
-                ops.maxsim_scores_fp8(qv, self._reps[a:b], self._scale[a:b], q.mask, self._mask[a:b], s)
-            elif self.tokens:
-                ops.maxsim_scores(qv, self._reps[a:b], q.mask, self._mask[a:b], s)
-            else:
-                ops.gemm(qv, self._reps[a:b], s)
-            ops.topk_merge(s, top_val, top_id, id0=a, init=(a == 0))
-        return top_val, top_id
+        return topk_scan(qv.shape[0], k, self.chunks(qv.shape[0], decode=True), qv.device, self._kind.scorer(q))
 
     def rerank_chunks(self, Q, C):
         """[(start, stop), ...]: the candidate columns one rerank launch scores: at most 65535, and at most as many as
-        keep the [Q, c] f32 scores within scratch_bytes."""
-        per = min(MAX_CHUNK, self.scratch_bytes // (4 * int(Q)))
-        if per < 1:
-            raise ValueError(f"scratch_bytes = {self.scratch_bytes} does not hold the scores of one candidate for "
-                             f"{Q} queries ({4 * int(Q)} bytes)")
-        return [(s, min(s + per, int(C))) for s in range(0, int(C), per)]
+        keep the [Q, c] f32 scores within scratch_bytes (store.score_chunks)."""
+        return score_chunks(C, Q, self.scratch_bytes, "candidate")
 
     def rerank(self, queries, candidates, k):
         """Score every query against its own candidates only (a token index): (scores f32 [Q, k], ids int32 [Q, k]) on
@@ -418,43 +475,13 @@ class CorpusIndex:
 
     def _rerank_encoded(self, q, candidates, k):
         """`rerank` behind the query encoder: q is encode_queries' TokenReps."""
-        qv = q.values
-        Q = qv.shape[0]
-        if isinstance(candidates, torch.Tensor) and candidates.is_cuda:
-            cand = candidates
-            if cand.dtype != torch.int32:
-                raise ValueError(f"candidates on the device must be int32, the ids a search returns (got {cand.dtype})")
-        else:
-            host = candidates.numpy() if isinstance(candidates, torch.Tensor) else np.asarray(candidates)
-            if host.dtype.kind not in "iu":
-                raise ValueError(f"candidates must be integers (got {host.dtype})")
-            if host.size and (int(host.min()) < -1 or int(host.max()) >= self._n):
-                raise ValueError(f"candidates must lie in [-1, {self._n}) (got {int(host.min())} .. {int(host.max())})")
-            cand = torch.as_tensor(np.ascontiguousarray(host.astype(np.int32))).to(qv.device)
-        if cand.dim() != 2 or cand.shape[0] != Q or cand.shape[1] < 1:
-            raise ValueError(f"candidates must be [{Q}, C] with C >= 1 (got {tuple(cand.shape)})")
-        if cand.stride(1) != 1:
-            cand = cand.contiguous()
-        spans = self.rerank_chunks(Q, cand.shape[1])
-        scratch = torch.empty((Q, max(b - a for a, b in spans)), dtype=torch.float32, device=qv.device)
-        top_val = torch.empty((Q, int(k)), dtype=torch.float32, device=qv.device)
-        top_id = torch.empty((Q, int(k)), dtype=torch.int32, device=qv.device)
-        reps, mask = self._reps[:self._n], self._mask[:self._n]
-        for a, b in spans:
-            s, c = scratch[:, :b - a], cand[:, a:b]
-            if self.storage == "fp8":
-                ops.maxsim_rerank_fp8(qv, reps, self._scale[:self._n], q.mask, mask, c, s)
-            elif self.storage == "residual":
-                ops.maxsim_rerank_res(qv, self._codes[:self._n], reps, self._centroids, self._weights, self.codec.nbits,
-                                      q.mask, mask, c, s)
-            else:
-                ops.maxsim_rerank(qv, reps, q.mask, mask, c, s)
-            ops.topk_merge(s, top_val, top_id, init=(a == 0), ids=c)
-        return top_val, top_id
+        Q, dev = q.values.shape[0], q.values.device
+        cand = check_candidates(candidates, Q, self._n, dev)
+        return topk_scan(Q, k, self.rerank_chunks(Q, cand.shape[1]), dev, self._kind.reranker(q, cand), ids=cand)
 
     # ------------------------------------------------------------ centroid-pruned search
     def _check_centroid_support(self):
-        if self.storage == "residual":
+        if self.codec is not None:
             raise ValueError("a residual index takes its centroids from its codec: the stored residuals belong to "
                              "them, so they cannot be set or fitted again")
         if self._n == 0:
@@ -465,9 +492,6 @@ class CorpusIndex:
         if not self.normalize:
             raise ValueError("centroids need a scorer that normalises (MaxSimScores(normalize=True)): the nearest "
                              "centroid by dot product means something on unit vectors only")
-
-    def _token_dtype(self):
-        return self._dtype if self.storage is not None else self._reps.dtype
 
     def _assign_rows(self, load, T, mask, codes, centroids):
         """codes[t] (int16 [T]) = the nearest row of `centroids` to token t, 0xFFFF where mask[t] == 0 (mask int32 [T]
@@ -494,14 +518,8 @@ class CorpusIndex:
     def _assign(self, a, b):
         """Codes of the stored documents a .. b from their stored representation (an FP8 index: the dequantised
         vectors) and the centroids: the same function in `add` and in `set_centroids`."""
-        Ld, E = self._ld, self._reps.shape[2]
-        reps = self._reps[a:b].view(-1, E)
-        if self.storage == "fp8":
-            scale = self._scale[a:b].view(-1)
-            load = lambda s, e, dst: ops.fp8_dequantize(reps[s:e], scale[s:e], dst)
-        else:
-            load = lambda s, e, dst: dst.copy_(reps[s:e])
-        self._assign_rows(load, (b - a) * Ld, self._mask[a:b].view(-1), self._codes[a:b].view(-1), self._centroids)
+        self._assign_rows(self._kind.loader(a, b), (b - a) * self._ld, self._mask[a:b].view(-1), self._codes[a:b].view(-1),
+                          self._centroids)
 
     def set_centroids(self, centroids):
         """Take `centroids` ([K, E] array or tensor, 1 <= K <= 65535, as given: cast to the index's dtype, not
@@ -514,10 +532,17 @@ class CorpusIndex:
         E = self._reps.shape[2]
         if c.dim() != 2 or c.shape[1] != E or not 1 <= c.shape[0] <= MAX_CENTROIDS:
             raise ValueError(f"centroids must be [K, {E}] with 1 <= K <= {MAX_CENTROIDS} (got {tuple(c.shape)})")
-        self._centroids = c.to(device=self._reps.device, dtype=self._token_dtype()).contiguous().clone()
-        self._codes = torch.full((self._reps.shape[0], self._ld), -1, dtype=torch.int16, device=self._reps.device)
+        self._centroids = c.to(device=self._reps.device, dtype=self._kind.dtype).contiguous().clone()
+        self._store.declare(codes=((self._ld,), torch.int16, -1))              # a fresh buffer, all 0xFFFF
         self._assign(0, self._n)
         self._lists_stale = True
+
+    def _sample_slots(self, sample, seed):
+        """The sampled token slots of fit_centroids and fit_codec (the rule is in fit_centroids' docstring)."""
+        S = self._n * self._ld
+        r = np.random.Generator(np.random.PCG64(int(seed)))
+        slots = r.permutation(S) if S <= int(sample) else r.choice(S, size=int(sample), replace=False)
+        return slots[self._mask[:self._n].reshape(-1).cpu().numpy()[slots] != 0]
 
     def fit_centroids(self, K, iters=4, sample=1 << 18, seed=0):
         """Spherical k-means on the device over a sample of the stored tokens, then set_centroids.
@@ -535,21 +560,12 @@ class CorpusIndex:
         K = int(K)
         if not 1 <= K <= MAX_CENTROIDS:
             raise ValueError(f"need 1 <= K <= {MAX_CENTROIDS} centroids (got {K})")
-        S, E = self._n * self._ld, self._reps.shape[2]
-        r = np.random.Generator(np.random.PCG64(int(seed)))
-        slots = r.permutation(S) if S <= int(sample) else r.choice(S, size=int(sample), replace=False)
-        slots = slots[self._mask[:self._n].reshape(-1).cpu().numpy()[slots] != 0]
+        slots = self._sample_slots(sample, seed)
         if len(slots) < K:
             raise ValueError(f"{K} centroids need at least as many valid sampled tokens (got {len(slots)})")
         dev = self._reps.device
-        at = torch.as_tensor(slots.astype(np.int64)).to(dev)
-        flat = self._reps[:self._n].view(-1, E)
-        if self.storage == "fp8":
-            x = torch.empty((len(slots), E), dtype=self._dtype, device=dev)
-            ops.fp8_dequantize(flat[at].contiguous(), self._scale[:self._n].view(-1)[at].contiguous(), x)
-        else:
-            x = flat[at].contiguous()
-        T = x.shape[0]
+        x = self._kind.gather(torch.as_tensor(slots.astype(np.int64)).to(dev))
+        (T, E) = x.shape
         cent, nxt = x[:K].clone(), torch.empty((K, E), dtype=x.dtype, device=dev)
         codes = torch.empty((T,), dtype=torch.int16, device=dev)
         counts = torch.empty((K,), dtype=torch.int32, device=dev)
@@ -574,19 +590,11 @@ class CorpusIndex:
         self._check_centroid_support()
         if self._centroids is None:
             raise ValueError("fit_codec needs centroids: call fit_centroids or set_centroids first")
-        S, E = self._n * self._ld, self._reps.shape[2]
-        r = np.random.Generator(np.random.PCG64(int(seed)))
-        slots = r.permutation(S) if S <= int(sample) else r.choice(S, size=int(sample), replace=False)
-        slots = slots[self._mask[:self._n].reshape(-1).cpu().numpy()[slots] != 0]
+        slots = self._sample_slots(sample, seed)
         if len(slots) == 0:
             raise ValueError("the sample holds no valid token")
         at = torch.as_tensor(slots.astype(np.int64)).to(self._reps.device)
-        flat = self._reps[:self._n].view(-1, E)
-        if self.storage == "fp8":
-            x = torch.empty((len(slots), E), dtype=self._dtype, device=self._reps.device)
-            ops.fp8_dequantize(flat[at].contiguous(), self._scale[:self._n].view(-1)[at].contiguous(), x)
-        else:
-            x = flat[at]
+        x = self._kind.gather(at)
         codes = self._codes[:self._n].view(-1)[at].cpu().numpy().view(np.uint16).astype(np.int64)
         cent = self._centroids.float().cpu().numpy()
         res = x.float().cpu().numpy() - cent[codes]
@@ -630,12 +638,9 @@ class CorpusIndex:
         if nprobe is not None:
             self._score_probed(q, table, int(nprobe), cand_val, cand_id)
             return self._rerank_encoded(q, cand_id, k)
-        spans = self.chunks(Q)
-        scratch = torch.empty((Q, max(b - a for a, b in spans)), dtype=torch.float32, device=qv.device)
-        for a, b in spans:
-            s = scratch[:, :b - a]
-            ops.centroid_scores(table, q.mask, self._codes[a:b], s, Q, Lq)
-            ops.topk_merge(s, cand_val, cand_id, id0=a, init=(a == 0))
+        codes = self._codes
+        topk_scan(Q, None, self.chunks(Q), qv.device,
+                  lambda a, b, s: ops.centroid_scores(table, q.mask, codes[a:b], s, Q, Lq), top=(cand_val, cand_id))
         return self._rerank_encoded(q, cand_id, k)
 
     # ------------------------------------------------------------ inverted lists and probed candidates
@@ -748,12 +753,9 @@ class CorpusIndex:
                 C, b = max(C, int(counts[b])), b + 1
             cand = torch.empty((b - a, C), dtype=torch.int32, device=count.device)
             ops.ivf_compact(bitmap[a:b], self._n, count[a:b], cand)
-            spans = self.rerank_chunks(b - a, C)
-            scratch = torch.empty((b - a, max(e - s for s, e in spans)), dtype=torch.float32, device=count.device)
-            for s, e in spans:
-                sc, c = scratch[:, :e - s], cand[:, s:e]
-                ops.centroid_scores_ids(table[:, a * Lq:], q.mask[a:b], codes, c, sc, b - a, Lq)
-                ops.topk_merge(sc, cand_val[a:b], cand_id[a:b], init=(s == 0), ids=c)
+            topk_scan(b - a, None, self.rerank_chunks(b - a, C), count.device,
+                      lambda s, e, sc: ops.centroid_scores_ids(table[:, a * Lq:], q.mask[a:b], codes, cand[:, s:e], sc, b - a, Lq),
+                      ids=cand, top=(cand_val[a:b], cand_id[a:b]))
             a = b
 
 
@@ -767,8 +769,8 @@ class SparseCorpusIndex:
     row of the representations one "query" of that kernel: weight descending, ties to the lower term id, and a
     document with fewer than `terms` entries (V < terms) is padded with (-inf, -1), slots ops.sparse_scores skips by
     their id.  Zero weights are kept when nothing better is left: they add nothing.
-    `search` scores chunks of documents with ops.sparse_scores and merges them with ops.topk_merge, the loop of
-    CorpusIndex.search.  `scratch_bytes` bounds the [Q, n] f32 score buffer of one chunk.
+    `search` scores chunks of documents with ops.sparse_scores and merges them with ops.topk_merge, the scan every index
+    shares (store.topk_scan).  `scratch_bytes` bounds the [Q, n] f32 score buffer of one chunk.
     `postings=True` searches block-inverted postings of `block_docs` documents per block instead (polus_amd/ir/postings.py):
     `add` marks them stale, `refresh_postings` (or the next search) rebuilds them from the stored slots, the dense
     queries become lists of at most `query_terms` non-zeros (ops.sparse_compact_rows; their counts are copied to the
@@ -788,11 +790,13 @@ class SparseCorpusIndex:
 
     def clear(self):
         """Empty the index (the storage is released)."""
-        self._ids = self._w = None
-        self._n = 0
+        self._store = RowStore()
+        self._store.declare(ids=((self.terms,), torch.int32, -1), w=((self.terms,), torch.float32, 0))
         if self._postings is not None:
             self._postings.clear()
-        self._postings_stale = False
+
+    _n, _ids, _w = stored_rows, stored("ids"), stored("w")
+    _postings_stale = property(lambda self: self._postings is not None and self._postings.stale)
 
     def refresh_postings(self):
         """Rebuild the postings from the stored (term id, weight) slots (polus_amd/ir/postings.py: count, offsets, one
@@ -801,8 +805,11 @@ class SparseCorpusIndex:
             raise ValueError("this index was made with postings=False")
         if self._n == 0:
             raise ValueError("the index is empty: add documents before refreshing")
-        self._postings.build(self._ids[:self._n], self._w[:self._n], self._V)
-        self._postings_stale = False
+        self._postings.build(*self._forward())
+
+    def _forward(self):
+        """What the postings are built from: the stored (term id, weight) slots."""
+        return self.term_ids, self.weights, self._V
 
     @property
     def postings(self):
@@ -810,9 +817,7 @@ class SparseCorpusIndex:
         stale; None without postings=True or on an empty index."""
         if self._postings is None or self._n == 0:
             return None
-        if self._postings_stale or not self._postings.built:
-            self.refresh_postings()
-        return self._postings.arrays()
+        return self._postings.update(self._forward).arrays()
 
     def __len__(self):
         return self._n
@@ -820,12 +825,12 @@ class SparseCorpusIndex:
     @property
     def term_ids(self):
         """int32 [N, terms]: a view of the stored term ids, -1 in unused slots."""
-        return None if self._ids is None else self._ids[:self._n]
+        return self._store.view("ids")
 
     @property
     def weights(self):
         """f32 [N, terms]: a view of the stored weights, -inf in unused slots."""
-        return None if self._w is None else self._w[:self._n]
+        return self._store.view("w")
 
     @property
     def nbytes(self):
@@ -834,18 +839,6 @@ class SparseCorpusIndex:
             return 0
         extra = 0 if self._postings is None else self._postings.nbytes
         return self._n * self.terms * (self._ids.element_size() + self._w.element_size()) + extra
-
-    def _grow(self, need, dev):
-        cap = 0 if self._ids is None else self._ids.shape[0]
-        if need <= cap:
-            return
-        cap = max(need, 2 * cap)
-        ids = torch.full((cap, self.terms), -1, dtype=torch.int32, device=dev)
-        w = torch.zeros((cap, self.terms), dtype=torch.float32, device=dev)
-        if self._n:
-            ids[:self._n].copy_(self._ids[:self._n])
-            w[:self._n].copy_(self._w[:self._n])
-        self._ids, self._w = ids, w
 
     def add(self, documents):
         """Encode a batch of documents, keep each one's `terms` best entries and append them; returns the batch's ids,
@@ -858,7 +851,7 @@ class SparseCorpusIndex:
         if getattr(self, "_V", V) != V and self._n:
             raise ValueError(f"the index holds representations over {self._V} terms, the batch has {V}")
         self._V = V
-        self._grow(self._n + n, rep.device)
+        self._store.reserve(self._n + n, rep.device)
         vals = torch.empty((n, self.terms), dtype=torch.float32, device=rep.device)
         ids = torch.empty((n, self.terms), dtype=torch.int32, device=rep.device)
         ops.topk_merge(rep, vals, ids, init=True)
@@ -866,7 +859,8 @@ class SparseCorpusIndex:
         self._w[self._n:self._n + n].copy_(vals)
         out = torch.arange(self._n, self._n + n, dtype=torch.int32, device=rep.device)
         self._n += n
-        self._postings_stale = True
+        if self._postings is not None:
+            self._postings.stale = True
         return out
 
     def query_lists(self, q):
@@ -883,12 +877,8 @@ class SparseCorpusIndex:
         return q_terms, q_w, q_count
 
     def chunks(self, Q):
-        """[(start, stop), ...]: the document ranges a search with Q queries scores, one launch each (CorpusIndex.chunks)."""
-        per = min(MAX_CHUNK, self.scratch_bytes // (4 * int(Q)))
-        if per < 1:
-            raise ValueError(f"scratch_bytes = {self.scratch_bytes} does not hold the scores of one document for "
-                             f"{Q} queries ({4 * int(Q)} bytes)")
-        return [(s, min(s + per, self._n)) for s in range(0, self._n, per)]
+        """[(start, stop), ...]: the document ranges a search with Q queries scores, one launch each (store.score_chunks)."""
+        return score_chunks(self._n, Q, self.scratch_bytes, "document")
 
     def encode_queries(self, queries):
         """The queries' dense f32 [Q, V] representations."""
@@ -905,24 +895,15 @@ class SparseCorpusIndex:
             if q.dim() != 2 or q.shape[1] != self._V:
                 raise ValueError(f"the index holds representations over {self._V} terms, the queries have {tuple(q.shape)}")
             lists = self.query_lists(q)
-            if self._postings_stale or not self._postings.built:
-                self.refresh_postings()
-            return self._postings.search(*lists, k, self.scratch_bytes)
+            return self._postings.update(self._forward).search(*lists, k, self.scratch_bytes)
         return self.search_forward(q, k)
 
     def search_forward(self, q, k):
         """`search` on the forward route for dense f32 [Q, V] query representations, whatever `postings` says
         (tools/postings_bench.py compares the two routes of one index with it)."""
-        Q = q.shape[0]
-        spans = self.chunks(Q)
-        scratch = torch.empty((Q, max(b - a for a, b in spans)), dtype=torch.float32, device=q.device)
-        top_val = torch.empty((Q, int(k)), dtype=torch.float32, device=q.device)
-        top_id = torch.empty((Q, int(k)), dtype=torch.int32, device=q.device)
-        for a, b in spans:
-            s = scratch[:, :b - a]
-            ops.sparse_scores(q, self._ids[a:b], self._w[a:b], s)
-            ops.topk_merge(s, top_val, top_id, id0=a, init=(a == 0))
-        return top_val, top_id
+        ids, w = self._ids, self._w
+        return topk_scan(q.shape[0], k, self.chunks(q.shape[0]), q.device,
+                         lambda a, b, s: ops.sparse_scores(q, ids[a:b], w[a:b], s))
 
 
 class TwoStageSearch:

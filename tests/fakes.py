@@ -36,6 +36,28 @@ class RecordingLib:
         return [n for n, _ in self.calls]
 
 
+def recording_lib(real, monkeypatch, stream):
+    """A generator for a fixture to `yield from`: the recording library installed over `real`, the dummy `stream` handle cached
+    (so ops._st() needs no device), fresh workspaces; the cached handle is put back afterwards."""
+    from polus_amd import _lib, ops
+    proxy = RecordingLib(real)
+    monkeypatch.setattr(_lib, "load", lambda: proxy)
+    monkeypatch.setattr(ops, "_WS", {})
+    monkeypatch.setattr(ops, "_HAS_GPU", False)
+    prev = _lib._CUR_STREAM[0]
+    _lib._CUR_STREAM[0] = stream
+    try:
+        yield proxy
+    finally:
+        _lib._CUR_STREAM[0] = prev
+
+
+def disable_device_check(monkeypatch):
+    """Let the wrappers of polus_amd.ops take CPU tensors: for runs against the recording library only."""
+    from polus_amd import ops
+    monkeypatch.setattr(ops, "_req_cuda", lambda *ts: None)
+
+
 class FakeArena:
     def __init__(self, n):
         self.grads = torch.zeros(n, dtype=torch.float32)

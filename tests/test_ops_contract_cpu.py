@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from tests import ops_contract_cases as oc
-from tests.fakes import RecordingLib
+from tests.fakes import disable_device_check, recording_lib
 
 
 @pytest.fixture(scope="module")
@@ -25,23 +25,12 @@ def real_lib():
 @pytest.fixture
 def rec(real_lib, monkeypatch):
     """The recording library installed, a dummy stream handle cached (so ops._st() needs no device), fresh workspaces."""
-    from polus_amd import _lib, ops
-    proxy = RecordingLib(real_lib)
-    monkeypatch.setattr(_lib, "load", lambda: proxy)
-    monkeypatch.setattr(ops, "_WS", {})
-    monkeypatch.setattr(ops, "_HAS_GPU", False)
-    prev = _lib._CUR_STREAM[0]
-    _lib._CUR_STREAM[0] = oc.STREAM
-    try:
-        yield proxy
-    finally:
-        _lib._CUR_STREAM[0] = prev
+    yield from recording_lib(real_lib, monkeypatch, oc.STREAM)
 
 
 @pytest.fixture
 def no_device_check(monkeypatch):
-    from polus_amd import ops
-    monkeypatch.setattr(ops, "_req_cuda", lambda *ts: None)
+    disable_device_check(monkeypatch)
 
 
 # ------------------------------------------------------------------------------------------------- the table itself
