@@ -11,8 +11,8 @@ import torch
 
 from .. import ops
 from ..layers import Dense
-from ..models import (BertConfig, BertForMaskedLM, BertModel, PolusModel, SavableModel, COMPUTE_DTYPES, from_config,
-                      _BERT_CFG_KEYS)
+from ..models import (BertForMaskedLM, ModelShell, PolusModel, COMPUTE_DTYPES, from_config, new_encoder, shell_config,
+                      shell_from_keywords, stashed, unpack_inputs)
 from ..tensor import ParamArena, to_device
 
 
@@ -87,12 +87,13 @@ class LateInteractionDualEncoder(DualEncoder):
         return TokenReps(self.dp.forward(to_device(rep.values, self.compute_dtype, self.arena.device), training), rep.mask)
 
 
-class SpladeEncoder(SavableModel):
+class SpladeEncoder(ModelShell):
     """Learned sparse retrieval (SPLADE): a text becomes one non-negative f32 vector over the vocabulary,
     rep[v] = max over its valid tokens s of log(1 + relu(logit[s, v])), from the masked-LM logits of ALL its tokens.
 
     Built over a BertForMaskedLM and sharing its arena: one bucketed reducer and one fused AdamW cover encoder and head,
-    and the encoder reports its gradient windows as it does under masked-LM training.  `call` runs `mlm.bert`, passes the
+    and the encoder reports its gradient windows as it does under masked-LM training (a ModelShell over a ModelShell: the
+    hook and the step state set here are those of `mlm.bert`).  `call` runs `mlm.bert`, passes the
     B S hidden rows through `mlm.head_forward`, pools them (ops.splade_pool_fwd) and returns rep [B, V]; the pooling's
     maxima and winning tokens are kept for `backward`.  `backward(drep)` writes the pooled gradient in place into the
     logits buffer (ops.splade_pool_bwd), then follows BertForMaskedLM.backward: head_backward (the decoder's share goes
@@ -108,74 +109,17 @@ class SpladeEncoder(SavableModel):
     `splade_encoder`."""
 
     def __init__(self, mlm, name="splade_encoder"):
-        super().__init__(name)
         self.mlm = mlm
-        self.arena = mlm.arena
-        self.config = mlm.config
-        self.compute_dtype = mlm.compute_dtype
+        super().__init__(mlm, name)
         self.savable_config = {"func_name": "splade_encoder", "model": dict(mlm.savable_config["model"])}
-        self.mlm.grad_ready_hook = self.__dict__.get("_hook")
-        self._bufs = {}
-        self._stash = None
-
-    # the trainer sets these on the model it holds; the encoder inside reads them
-    @property
-    def grad_ready_hook(self):
-        return self.__dict__.get("_hook")
-
-    @grad_ready_hook.setter
-    def grad_ready_hook(self, hook):
-        self.__dict__["_hook"] = hook
-        if "mlm" in self.__dict__:
-            self.mlm.grad_ready_hook = hook
-
-    @property
-    def dropout_step(self):
-        return self.mlm.bert.dropout_step
-
-    @dropout_step.setter
-    def dropout_step(self, step):
-        self.mlm.bert.dropout_step = step
-
-    @property
-    def overlap_dw(self):
-        return self.mlm.bert.overlap_dw
-
-    @overlap_dw.setter
-    def overlap_dw(self, on):
-        self.mlm.bert.overlap_dw = on
-
-    @property
-    def graph_seeds(self):
-        return getattr(self.mlm.bert, "graph_seeds", False)
-
-    @graph_seeds.setter
-    def graph_seeds(self, on):
-        self.mlm.bert.graph_seeds = on
-
-    def site_seed(self, layer, site, step=None):
-        return self.mlm.bert.site_seed(layer, site, step)
-
-    def load_numpy_params(self, params):
-        self.mlm.load_numpy_params(params)
-
-    def _buf(self, key, shape, dtype):
-        t = self._bufs.get(key)
-        if t is None or t.shape != tuple(shape) or t.dtype != dtype:
-            t = self._bufs[key] = torch.empty(tuple(shape), dtype=dtype, device=self.arena.device)
-        return t
 
     def call(self, input_ids=None, attention_mask=None, token_type_ids=None, training=False, **kw):
-        if isinstance(input_ids, dict):
-            d = input_ids
-            input_ids, attention_mask = d.get("input_ids"), d.get("attention_mask", attention_mask)
-            token_type_ids = d.get("token_type_ids", token_type_ids)
+        input_ids, attention_mask, token_type_ids = unpack_inputs(input_ids, attention_mask, token_type_ids)
         mlm, V, H = self.mlm, self.config.vocab_size, self.config.hidden_size
         if attention_mask is not None:
             attention_mask = to_device(attention_mask, torch.int32, self.arena.device)
         out = mlm.bert(input_ids=input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids, training=training)
-        B, S = mlm.bert._shape
-        self.tokens_per_step = mlm.bert.tokens_per_step
+        B, S = self._shape
         logits = mlm.head_forward(out.last_hidden_state.view(B * S, H), training)
         rep, xmax = self._buf("rep", (B, V), torch.float32), self._buf("xmax", (B, V), torch.float32)
         arg = self._buf("arg", (B, V), torch.int32)
@@ -186,16 +130,13 @@ class SpladeEncoder(SavableModel):
     def backward(self, drep, accumulate=False):
         """drep f32 [B, V]: the gradient wrt the representations of the last training forward pass.  Parameter
         gradients land in the arena, overwritten or, with `accumulate`, added to."""
-        if self._stash is None:
-            raise RuntimeError("SpladeEncoder.backward: the last forward pass ran with training=False (nothing was kept for backward)")
-        logits, xmax, arg, B, S = self._stash
+        logits, xmax, arg, B, S = stashed(self)
         mlm, H = self.mlm, self.config.hidden_size
         if drep.dtype != torch.float32 or tuple(drep.shape) != tuple(xmax.shape):
             raise TypeError(f"SpladeEncoder.backward: drep must be float32 {tuple(xmax.shape)}, got {drep.dtype} {tuple(drep.shape)}")
         ops.splade_pool_bwd(drep, xmax, arg, logits, B, S)            # in place: backward needs nothing of the logits
         dh = mlm.head_backward(logits, accumulate)
         self._notify(mlm.head_variables())                            # emb.word still waits for the embedding's share
-        mlm.bert.deterministic = self.deterministic
         return mlm.bert.backward(dh.view(B, S, H), accumulate=accumulate, word_grad_holds_tied_share=True)
 
     def encode_query(self, x, training=False):
@@ -213,7 +154,7 @@ class SpladeEncoder(SavableModel):
 CROSS_DROPOUT_SITE = 3        # BertModel's own sites are 0..2 of layers -1..L-1; the head's dropout is site 3 of layer L-1
 
 
-class CrossEncoder(SavableModel):
+class CrossEncoder(ModelShell):
     """A cross-encoder reranker, HF BertForSequenceClassification(num_labels=1): the pair row `[CLS] query [SEP]
     document [SEP]` goes through BERT as ONE sequence and score = classifier(dropout(pooler_output)), one f32 number
     per pair.  The teacher the distillation losses of polus_amd/ir/training.py fit a retriever to, and the last stage
@@ -222,77 +163,25 @@ class CrossEncoder(SavableModel):
     One arena: BertModel(add_pooling_layer=True)'s variables, then classifier.{w,b} (Dense(1), f32 out, the
     polus_dense_thin kernels) with the highest offsets, reported final first.  The dropout between pooler and
     classifier is hidden_dropout_prob in training only (polus_dropout, regenerated in backward), seeded by
-    `site_seed(last layer, 3)`, which no site of the encoder uses.
+    `site_seed(last layer, 3)`, which no site of the encoder uses.  A ModelShell: the hook and the step state set here
+    are `bert`'s.
 
     `call(input_ids, attention_mask, token_type_ids, training)` returns f32 [P]; `backward(dscore)` takes f32 [P] (or
     [P, 1]).  Savable through `cross_encoder`."""
 
     def __init__(self, cfg, compute_dtype="bf16", seed=1234, name="cross_encoder"):
-        super().__init__(name)
-        self.config = cfg
-        self.compute_dtype = COMPUTE_DTYPES[compute_dtype]
-        mode = "bf16" if self.compute_dtype == torch.bfloat16 else "f32"
-        self.savable_config = {"func_name": "cross_encoder", "model": dict(cfg.to_dict(), compute_dtype=mode, seed=seed)}
-        self.arena = ParamArena(self.compute_dtype)
-        self.bert = BertModel(cfg, compute_dtype=mode, seed=seed, arena=self.arena, add_pooling_layer=True)
-        self.bert.grad_ready_hook = self.__dict__.get("_hook")
+        self.bert = new_encoder(cfg, compute_dtype, seed, add_pooling_layer=True)
+        super().__init__(self.bert, name)
+        self.savable_config = shell_config("cross_encoder", self.bert)
         self.classifier = Dense(1, out_dtype=torch.float32, name="classifier")
         self.classifier.build(self.arena, cfg.hidden_size, "classifier")
         self.arena.finalize()
-        self._bufs = {}
-        self._stash = None
-
-    # the trainer sets these on the model it holds; the encoder inside reads them
-    @property
-    def grad_ready_hook(self):
-        return self.__dict__.get("_hook")
-
-    @grad_ready_hook.setter
-    def grad_ready_hook(self, hook):
-        self.__dict__["_hook"] = hook
-        if "bert" in self.__dict__:
-            self.bert.grad_ready_hook = hook
-
-    @property
-    def dropout_step(self):
-        return self.bert.dropout_step
-
-    @dropout_step.setter
-    def dropout_step(self, step):
-        self.bert.dropout_step = step
-
-    @property
-    def overlap_dw(self):
-        return self.bert.overlap_dw
-
-    @overlap_dw.setter
-    def overlap_dw(self, on):
-        self.bert.overlap_dw = on
-
-    def site_seed(self, layer, site, step=None):
-        return self.bert.site_seed(layer, site, step)
-
-    def load_numpy_params(self, params):
-        """params: dict in the emb.* / layer{i}.* / pooler.* / classifier.* naming; names it lacks keep their values."""
-        for v in self.arena.vars:
-            if v.name in params:
-                v.assign(params[v.name])
-
-    def _buf(self, key, shape, dtype):
-        t = self._bufs.get(key)
-        if t is None or t.shape != tuple(shape) or t.dtype != dtype:
-            t = self._bufs[key] = torch.empty(tuple(shape), dtype=dtype, device=self.arena.device)
-        return t
 
     def call(self, input_ids=None, attention_mask=None, token_type_ids=None, training=False, **kw):
-        if isinstance(input_ids, dict):
-            d = input_ids
-            input_ids, attention_mask = d.get("input_ids"), d.get("attention_mask", attention_mask)
-            token_type_ids = d.get("token_type_ids", token_type_ids)
+        input_ids, attention_mask, token_type_ids = unpack_inputs(input_ids, attention_mask, token_type_ids)
         L =self.config.num_hidden_layers - 1
         seed = self.site_seed(L, CROSS_DROPOUT_SITE) if training else 0      # before the encoder advances dropout_step
         out = self.bert(input_ids=input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids, training=training)
-        self.tokens_per_step = self.bert.tokens_per_step
         pooled = out.pooler_output
         p = self.config.hidden_dropout_prob if training else 0.0
         if p > 0.0:
@@ -306,10 +195,8 @@ class CrossEncoder(SavableModel):
     def backward(self, dscore, accumulate=False):
         """dscore f32 [P] or [P, 1]: the gradient wrt the scores of the last training forward pass.  Parameter gradients
         land in the arena, overwritten or, with `accumulate`, added to."""
-        if self._stash is None:
-            raise RuntimeError("CrossEncoder.backward: the last forward pass ran with training=False (nothing was kept for backward)")
-        p, seed = self._stash
-        P = self.bert._shape[0]
+        p, seed = stashed(self)
+        P = self._shape[0]
         if dscore.dtype != torch.float32 or dscore.numel() != P:
             raise TypeError(f"CrossEncoder.backward: dscore must be float32 with {P} elements, got {dscore.dtype} {tuple(dscore.shape)}")
         dpooled = self.classifier.backward(dscore.reshape(P, 1), accumulate)
@@ -318,19 +205,16 @@ class CrossEncoder(SavableModel):
             d = self._buf("ddropped", dpooled.shape, dpooled.dtype)
             ops.dropout(dpooled, d, p, seed)
             dpooled = d
-        self.bert.deterministic = self.deterministic
         return self.bert.backward(None, accumulate=accumulate, dpooled=dpooled)
 
 
 @from_config
 def cross_encoder(**kw):
     """Builder behind CrossEncoder.save / load_model: the BertConfig fields + compute_dtype, seed."""
-    cfg = BertConfig(**{k: kw[k] for k in _BERT_CFG_KEYS if k in kw})
-    return CrossEncoder(cfg, compute_dtype=kw.get("compute_dtype", "bf16"), seed=kw.get("seed", 1234))
+    return shell_from_keywords(CrossEncoder, kw)
 
 
 @from_config
 def splade_encoder(**kw):
     """Builder behind SpladeEncoder.save / load_model: the BertForMaskedLM's BertConfig fields + compute_dtype, seed."""
-    cfg = BertConfig(**{k: kw[k] for k in _BERT_CFG_KEYS if k in kw})
-    return SpladeEncoder(BertForMaskedLM(cfg, compute_dtype=kw.get("compute_dtype", "bf16"), seed=kw.get("seed", 1234)))
+    return SpladeEncoder(shell_from_keywords(BertForMaskedLM, kw))

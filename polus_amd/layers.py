@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .tensor import DeviceScalar, to_device
+from .tensor import DeviceScalar, cached_buffer, to_device
 
 
 class Layer:
@@ -33,11 +33,7 @@ class Layer:
         raise NotImplementedError
 
     def _buf(self, key, shape, dtype, dev):
-        cache = self.__dict__.setdefault("_bufs", {})
-        t = cache.get(key)
-        if t is None or t.shape != tuple(shape) or t.dtype != dtype:
-            t = cache[key] = torch.empty(tuple(shape), dtype=dtype, device=dev)
-        return t
+        return cached_buffer(self.__dict__.setdefault("_bufs", {}), key, shape, dtype, dev)
 
 
 def dw_split_k(out_rows, out_cols, contraction):

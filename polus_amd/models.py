@@ -17,7 +17,7 @@ import torch
 
 from . import _lib, ops
 from .layers import CRF, Dense, Dropout, Flatten, Layer, dense_bwd_params_group, dw_split_k, gemm_dx
-from .tensor import ParamArena, to_device, device
+from .tensor import ParamArena, cached_buffer, to_device, device
 from .utils import complex_json_deserializer, complex_json_serializer, flatten_dict, merge_dicts
 
 COMPUTE_DTYPES = {"f32": torch.float32, "float32": torch.float32, torch.float32: torch.float32,
@@ -76,6 +76,11 @@ def from_config(func):
     return function_wrapper
 
 
+_BERT_CFG_KEYS = ("vocab_size", "hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size",
+                  "max_position_embeddings", "type_vocab_size", "layer_norm_eps", "hidden_dropout_prob",
+                  "attention_probs_dropout_prob", "_name_or_path")
+
+
 class BertConfig:
     """Hyper-parameters of HF BertConfig that the encoder math depends on."""
 
@@ -94,6 +99,11 @@ class BertConfig:
         self._name_or_path = _name_or_path
 
     @classmethod
+    def from_keywords(cls, kw):
+        """The config out of a builder's keywords (what a saved .cfg holds); the other keywords are the builder's own."""
+        return cls(**{k: kw[k] for k in _BERT_CFG_KEYS if k in kw})
+
+    @classmethod
     def bert_base(cls, **kw):
         return cls(**kw)
 
@@ -102,7 +112,7 @@ class BertConfig:
         return cls(hidden_size=1024, num_hidden_layers=24, num_attention_heads=16, intermediate_size=4096, **kw)
 
     def to_dict(self):
-        return {k: v for k, v in self.__dict__.items()}
+        return dict(vars(self))
 
 
 class BaseModelOutputWithPooling:
@@ -144,6 +154,25 @@ def _trunc_normal(rng, shape, std=0.02):
     return (np.clip(rng.standard_normal(shape), -2.0, 2.0) * std).astype(np.float32)
 
 
+_INPUT_NAMES = ("input_ids", "attention_mask", "token_type_ids", "masked_positions")
+
+
+def unpack_inputs(*given):
+    """`given`: input_ids, attention_mask, token_type_ids (and masked_positions) as a `call` received them.  The first may
+    be the dict of all of them (``model(x)`` beside ``model(**x)``); the others then only fill what the dict lacks."""
+    d = given[0]
+    if not isinstance(d, dict):
+        return given
+    return (d.get("input_ids"),) + tuple(d.get(k, v) for k, v in zip(_INPUT_NAMES[1:], given[1:]))
+
+
+def stashed(obj):
+    """What the last training forward pass of `obj` kept for its backward pass."""
+    if obj._stash is None:
+        raise RuntimeError(f"{type(obj).__name__}.backward: the last forward pass ran with training=False (nothing was kept for backward)")
+    return obj._stash
+
+
 # ------------------------------------------------------------------------------------ BERT pieces
 class BertLayer:
     """One post-LN transformer block: 4 MFMA GEMMs + fused attention + 2 LayerNorms forward,
@@ -172,19 +201,13 @@ class BertLayer:
         return [self.qkv_w, self.qkv_b, self.out_w, self.out_b, self.ln1_g, self.ln1_b,
                 self.ffn1_w, self.ffn1_b, self.ffn2_w, self.ffn2_b, self.ln2_g, self.ln2_b]
 
-    def _buf(self, key, shape, dtype, dev):
-        t = self._bufs.get(key)
-        if t is None or t.shape != tuple(shape) or t.dtype != dtype:
-            t = self._bufs[key] = torch.empty(tuple(shape), dtype=dtype, device=dev)
-        return t
-
     def forward(self, x, mask, B, S, p_hid=0.0, p_att=0.0, seeds=(0, 0, 0), for_backward=True):
         """`for_backward=False` (inference, the frozen encoders of the dual-encoder trainer): the GELU pre-activation is
         not written -- half of FFN1's output bytes, a launch that is bound by exactly those."""
         cfg = self.cfg
         H, I, A = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads
         T, dt, dev = B * S, x.dtype, x.device
-        b = lambda k, shape, d=dt: self._buf(k, shape, d, dev)
+        b = lambda k, shape, d=dt: cached_buffer(self._bufs, k, shape, d, dev)
         qkv, ctx, lse = b("qkv", (T, 3 * H)), b("ctx", (T, H)), b("lse", (B, A, S), torch.float32)
         z1, a1 = b("z1", (T, H)), b("a1", (T, H))
         m1, r1 = b("m1", (T,), torch.float32), b("r1", (T,), torch.float32)
@@ -212,9 +235,7 @@ class BertLayer:
         layers later)."""
         cfg = self.cfg
         H, I, A = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads
-        if self._stash is None:
-            raise RuntimeError("BertLayer.backward: the last forward pass ran with training=False (nothing was kept for backward)")
-        x, mask, B, S, p_hid, p_att, seeds = self._stash
+        x, mask, B, S, p_hid, p_att, seeds = stashed(self)
         T = B * S
         bb = self._bufs
         par = "" if side is None else str(self.index & 1)
@@ -385,6 +406,50 @@ class SavableModel(PolusModel):
         np.savez(path + ".npz", **{f"weight{i}": a for i, a in enumerate(w)})
         return path
 
+    def load_numpy_params(self, params):
+        """params: dict by variable name (oracle/bert.py and checkpoint.hf_state_to_params naming: emb.*, layer{i}.*,
+        pooler.*, mlm.*, classifier.*); names it lacks keep their values."""
+        for v in self.arena.vars:
+            if v.name in params:
+                v.assign(params[v.name])
+
+
+STEP_STATE = ("dropout_step", "overlap_dw", "graph_seeds", "deterministic", "identical_dropout_across_ranks")
+
+
+def _of_inner(name, settable=True):
+    return property(lambda self: getattr(self.inner, name),
+                    (lambda self, value: setattr(self.inner, name, value)) if settable else None)
+
+
+class ModelShell(SavableModel):
+    """A model built around another one (`inner`: a BertModel, or a shell around one) in the same arena, adding a head.
+
+    The trainer, GraphedStep and checkpoint.py set the step's state on the model they hold, and the BertModel at the
+    bottom of the chain is what reads it.  So a shell stores none of it: every name of STEP_STATE, and the gradient
+    hook, is a property that reads and writes `inner`'s, through as many shells as there are; `site_seed`,
+    `tokens_per_step` and the (B, S) of the last call are read through the same way.  A name added to STEP_STATE is
+    forwarded by every shell."""
+
+    def __init__(self, inner, name=None):
+        self.inner = inner                      # first: the initialisers above assign forwarded names
+        super().__init__(name)
+        self.arena, self.config, self.compute_dtype = inner.arena, inner.config, inner.compute_dtype
+        self._bufs = {}
+        self._stash = None
+
+    def site_seed(self, layer, site, step=None):
+        return self.inner.site_seed(layer, site, step)
+
+    def _buf(self, key, shape, dtype):
+        return cached_buffer(self._bufs, key, shape, dtype, self.arena.device)
+
+
+for _name in STEP_STATE + ("grad_ready_hook",):
+    setattr(ModelShell, _name, _of_inner(_name))
+for _name in ("tokens_per_step", "_shape"):
+    setattr(ModelShell, _name, _of_inner(_name, settable=False))
+
 
 class PolusClassifier(SavableModel):
     def inference(self, x):
@@ -484,20 +549,16 @@ class BertModel(SavableModel):
         self.dropout_base_seed = seed
         self.dropout_step = 0     # advanced once per training forward: fresh masks every step
         self.overlap_dw = os.environ.get("POLUS_OVERLAP_DW", "1") != "0"
+        self.graph_seeds = False                        # set by GraphedStep while it captures: see site_seed
+        self.identical_dropout_across_ranks = False
         self._side = None
 
     def scratch(self, key, shape, dtype=None):
-        dtype = dtype or self.compute_dtype
-        t = self._scratch.get(key)
-        if t is None or t.shape != tuple(shape) or t.dtype != dtype:
-            t = self._scratch[key] = torch.empty(tuple(shape), dtype=dtype, device=self.arena.device)
-        return t
+        return cached_buffer(self._scratch, key, shape, dtype or self.compute_dtype, self.arena.device)
 
     def load_numpy_params(self, params, head_w=None, head_b=None):
         """params: dict in oracle/bert.py naming (emb.*, layer{i}.*)."""
-        for v in self.arena.vars:
-            if v.name in params:
-                v.assign(params[v.name])
+        super().load_numpy_params(params)
         if self.head is not None and head_w is not None:
             self.head.w.assign(head_w)
             self.head.b.assign(head_b)
@@ -507,11 +568,11 @@ class BertModel(SavableModel):
         (Horovod/TF ranks have independent RNG streams): the rank is folded into the base seed unless
         `identical_dropout_across_ranks` is set (exact-mask parity tests)."""
         base = self.dropout_base_seed
-        if not getattr(self, "identical_dropout_across_ranks", False):
+        if not self.identical_dropout_across_ranks:
             from . import comm
             if comm.size() > 1:
                 base = (base ^ (comm.rank() * 0x9E3779B1)) & 0xFFFFFFFF
-        if getattr(self, "graph_seeds", False):     # the step term comes from device memory (polus_amd/graph.py)
+        if self.graph_seeds:                        # the step term comes from device memory (polus_amd/graph.py)
             return dropout_seed_static(base, layer, site)
         return dropout_seed(base, self.dropout_step if step is None else step, layer, site)
 
@@ -526,10 +587,7 @@ class BertModel(SavableModel):
 
     def call(self, input_ids=None, attention_mask=None, token_type_ids=None, training=False, hidden_states=None, **kw):
         dev = self.arena.device
-        if isinstance(input_ids, dict):
-            d = input_ids
-            input_ids, attention_mask = d.get("input_ids"), d.get("attention_mask", attention_mask)
-            token_type_ids = d.get("token_type_ids", token_type_ids)
+        input_ids, attention_mask, token_type_ids = unpack_inputs(input_ids, attention_mask, token_type_ids)
         if attention_mask is not None:
             attention_mask = to_device(attention_mask, torch.int32, dev)
         if hidden_states is None:
@@ -627,20 +685,27 @@ def _identity(n, dtype, dev):
 def bert_model(**kw):
     """Builder behind BertModel.save / load_model: BertConfig fields + compute_dtype, num_labels, seed,
     add_pooling_layer."""
-    cfg_keys = ("vocab_size", "hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size",
-                "max_position_embeddings", "type_vocab_size", "layer_norm_eps", "hidden_dropout_prob",
-                "attention_probs_dropout_prob", "_name_or_path")
-    cfg = BertConfig(**{k: kw[k] for k in cfg_keys if k in kw})
-    return BertModel(cfg, compute_dtype=kw.get("compute_dtype", "bf16"), num_labels=kw.get("num_labels"),
+    return BertModel(BertConfig.from_keywords(kw), compute_dtype=kw.get("compute_dtype", "bf16"), num_labels=kw.get("num_labels"),
                      seed=kw.get("seed", 1234), add_pooling_layer=kw.get("add_pooling_layer", False))
 
 
-_BERT_CFG_KEYS = ("vocab_size", "hidden_size", "num_hidden_layers", "num_attention_heads", "intermediate_size",
-                  "max_position_embeddings", "type_vocab_size", "layer_norm_eps", "hidden_dropout_prob",
-                  "attention_probs_dropout_prob", "_name_or_path")
+def new_encoder(cfg, compute_dtype, seed, **kw):
+    """The BertModel of a shell, in a fresh arena that the shell adds its head to and then finalizes."""
+    return BertModel(cfg, compute_dtype=compute_dtype, seed=seed, arena=ParamArena(COMPUTE_DTYPES[compute_dtype]), **kw)
 
 
-class BertForMaskedLM(SavableModel):
+def shell_config(func_name, bert):
+    """savable_config of a shell around `bert`: its config, compute_dtype and seed, under the shell's builder."""
+    own = ("num_labels", "add_pooling_layer")
+    return {"func_name": func_name, "model": {k: v for k, v in bert.savable_config["model"].items() if k not in own}}
+
+
+def shell_from_keywords(cls, kw):
+    """What the builders of the shells share: `cls(config, compute_dtype, seed)` out of a saved .cfg's keywords."""
+    return cls(BertConfig.from_keywords(kw), compute_dtype=kw.get("compute_dtype", "bf16"), seed=kw.get("seed", 1234))
+
+
+class BertForMaskedLM(ModelShell):
     """BERT with the masked-LM head of HF BertForMaskedLM (cls.predictions): Dense(H -> H, gelu) -> LayerNorm -> decoder
     against the WORD-EMBEDDING TABLE (tied: there is no second matrix) + a vocabulary bias.  The step before every
     fine-tuning task of this engine: continued pre-training of a checkpoint on the user's own corpus.
@@ -651,7 +716,8 @@ class BertForMaskedLM(SavableModel):
     the sequence, -1 = unused slot; P fixed per dataset, BERT's max_predictions_per_seq, so every buffer is static)
     picks [B P, H] rows out of the encoder output (polus_gather_rows), and the call returns logits [B, P, V] in the
     compute dtype, a view of a buffer whose rows start on 16-byte boundaries.  Unused slots see a zero hidden row; their
-    labels must be negative (polus_amd.data.mask_tokens pads both with -1).
+    labels must be negative (polus_amd.data.mask_tokens pads both with -1).  The gradient hook and the step state set
+    on this model are `bert`'s own (ModelShell): the encoder reports its windows to the trainer's hook itself.
 
     backward(dlogits): the decoder's weight gradient dlogits^T . t goes straight into emb.word's gradient window, then
     the embedding backward ADDS its scatter to it, and only then is the window reported final.
@@ -659,14 +725,9 @@ class BertForMaskedLM(SavableModel):
     decoder reads a model-owned bf16 copy of the table, re-cast from the f32 master at every forward pass."""
 
     def __init__(self, cfg, compute_dtype="bf16", seed=1234, name="bert_for_masked_lm"):
-        super().__init__(name)
-        self.config = cfg
-        self.compute_dtype = COMPUTE_DTYPES[compute_dtype]
-        mode = "bf16" if self.compute_dtype == torch.bfloat16 else "f32"
-        self.savable_config = {"func_name": "bert_for_masked_lm", "model": dict(cfg.to_dict(), compute_dtype=mode, seed=seed)}
-        self.arena = ParamArena(self.compute_dtype)
-        self.bert = BertModel(cfg, compute_dtype=mode, seed=seed, arena=self.arena, with_embeddings=True)
-        self.bert.grad_ready_hook = self.__dict__.get("_hook")
+        self.bert = new_encoder(cfg, compute_dtype, seed)
+        super().__init__(self.bert, name)
+        self.savable_config = shell_config("bert_for_masked_lm", self.bert)
         H, V = cfg.hidden_size, cfg.vocab_size
         self.dense = Dense(H, activation="gelu", name="mlm.dense")
         self.dense.build(self.arena, H, "mlm.dense")
@@ -674,48 +735,15 @@ class BertForMaskedLM(SavableModel):
         self.ln_b = self.arena.add("mlm.ln.b", (H,), np.zeros(H, np.float32), decay=False)
         self.bias = self.arena.add("mlm.bias", (V,), np.zeros(V, np.float32), decay=False)
         self.arena.finalize()
-        self._bufs = {}
         self._table = None
-
-    # the trainer sets the hook on the model it holds; the encoder inside reports its own windows
-    @property
-    def grad_ready_hook(self):
-        return self.__dict__.get("_hook")
-
-    @grad_ready_hook.setter
-    def grad_ready_hook(self, hook):
-        self.__dict__["_hook"] = hook
-        if "bert" in self.__dict__:
-            self.bert.grad_ready_hook = hook
-
-    @property
-    def dropout_step(self):
-        return self.bert.dropout_step
-
-    @dropout_step.setter
-    def dropout_step(self, step):
-        self.bert.dropout_step = step
 
     def head_variables(self):
         return self.dense.variables() + [self.ln_g, self.ln_b, self.bias]
-
-    def load_numpy_params(self, params):
-        """params: dict in the emb.* / layer{i}.* / mlm.* naming (checkpoint.hf_state_to_params); names it lacks keep
-        their values."""
-        for v in self.arena.vars:
-            if v.name in params:
-                v.assign(params[v.name])
 
     def encoder_params(self):
         """The encoder's weights as the dict BertModel.load_numpy_params takes (emb.*, layer{i}.*): the pre-trained
         encoder goes straight into a BertModel(num_labels=...), a DualEncoder or split_bert_model."""
         return {v.name: v.numpy() for v in self.arena.vars if v.name.startswith(("emb.", "layer"))}
-
-    def _buf(self, key, shape, dtype):
-        t = self._bufs.get(key)
-        if t is None or t.shape != tuple(shape) or t.dtype != dtype:
-            t = self._bufs[key] = torch.empty(tuple(shape), dtype=dtype, device=self.arena.device)
-        return t
 
     def _flat_positions(self, masked_positions, B, S):
         """[B P] int32 rows of the [B S, H] encoder output, -1 for unused slots.  Host arrays are checked: a position
@@ -749,18 +777,13 @@ class BertForMaskedLM(SavableModel):
         return self._table
 
     def call(self, input_ids=None, attention_mask=None, token_type_ids=None, masked_positions=None, training=False, **kw):
-        if isinstance(input_ids, dict):
-            d = input_ids
-            input_ids, attention_mask = d.get("input_ids"), d.get("attention_mask", attention_mask)
-            token_type_ids = d.get("token_type_ids", token_type_ids)
-            masked_positions = d.get("masked_positions", masked_positions)
+        input_ids, attention_mask, token_type_ids, masked_positions = unpack_inputs(input_ids, attention_mask, token_type_ids, masked_positions)
         if masked_positions is None:
             raise ValueError("BertForMaskedLM needs masked_positions [B, P] (polus_amd.data.mask_tokens makes them)")
         cfg, dt = self.config, self.compute_dtype
         H, V = cfg.hidden_size, cfg.vocab_size
         out = self.bert(input_ids=input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids, training=training)
-        B, S = self.bert._shape
-        self.tokens_per_step = self.bert.tokens_per_step
+        B, S = self._shape
         hidden = out.last_hidden_state.view(B * S, H)
         flat = self._flat_positions(masked_positions, B, S)
         R = flat.numel()
@@ -803,9 +826,7 @@ class BertForMaskedLM(SavableModel):
     def backward(self, dlogits, accumulate=False):
         """dlogits [B, P, V] in the compute dtype (the in-place gradient of MaskedSparseCategoricalCrossentropy: the
         logits buffer itself).  Parameter gradients land in the arena, overwritten or, with `accumulate`, added to."""
-        if self._stash is None:
-            raise RuntimeError("BertForMaskedLM.backward: the last forward pass ran with training=False (nothing was kept for backward)")
-        flat, B, S, P = self._stash
+        flat, B, S, P = stashed(self)
         cfg, dt = self.config, self.compute_dtype
         H, V, R = cfg.hidden_size, cfg.vocab_size, B * P
         if dlogits.dtype != dt:
@@ -823,15 +844,13 @@ class BertForMaskedLM(SavableModel):
         inv = ops.inverse_map(flat, self._buf("inv", (B * S,), torch.int32))
         dh = ops.gather_rows(dhm, inv, self._buf("dh", (B * S, H), dt))
         # 7. the encoder; its last report (the embeddings) carries both shares of emb.word
-        self.bert.deterministic = self.deterministic
         return self.bert.backward(dh.view(B, S, H), accumulate=accumulate, word_grad_holds_tied_share=True)
 
 
 @from_config
 def bert_for_masked_lm(**kw):
     """Builder behind BertForMaskedLM.save / load_model: BertConfig fields + compute_dtype, seed."""
-    cfg = BertConfig(**{k: kw[k] for k in _BERT_CFG_KEYS if k in kw})
-    return BertForMaskedLM(cfg, compute_dtype=kw.get("compute_dtype", "bf16"), seed=kw.get("seed", 1234))
+    return shell_from_keywords(BertForMaskedLM, kw)
 
 
 class TFBertSplited(PolusModel):
@@ -848,6 +867,7 @@ class TFBertSplited(PolusModel):
         self.compute_dtype = arena.compute_dtype
         self._scratch = {}
         self.dropout_base_seed, self.dropout_step = 4321, 0
+        self.graph_seeds = self.identical_dropout_across_ranks = False
 
     scratch = BertModel.scratch
     site_seed = BertModel.site_seed

@@ -32,6 +32,16 @@ def to_device(x, dtype=None, dev=None):
     return t.contiguous()
 
 
+def cached_buffer(cache, key, shape, dtype, dev):
+    """`cache[key]`, allocated anew only when its shape or dtype changed: the activation / scratch caches of layers and
+    models (plain dicts: backward passes index them, a captured step graph keeps their tensors alive).  The same call
+    hands out the same memory step after step, which a replayed graph relies on."""
+    t = cache.get(key)
+    if t is None or t.shape != tuple(shape) or t.dtype != dtype:
+        t = cache[key] = torch.empty(tuple(shape), dtype=dtype, device=dev)
+    return t
+
+
 class DeviceScalar:
     """A one-element device tensor that only synchronises when a host value is needed
     (callbacks format the loss with ``f"{loss:.3f}"``, polus/callbacks.py:603)."""
