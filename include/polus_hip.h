@@ -970,6 +970,66 @@ int polus_fuse_lists(const int32_t* ids, long lsi, long ldi, const float* scores
                      int n_docs, int mode, const float* weights, float rrf_k, int32_t* out_id, long ldoi, float* out_val,
                      long ldov, int32_t* count, void* stream);
 
+/* ---- product quantisation of single ([CLS]) vectors and its asymmetric-distance scan (pq.hip; Jegou, Douze, Schmid:
+ * "Product quantization for nearest neighbor search", 2011; no counterpart in the reference).
+ *
+ * Format.  A vector of E = m * dsub elements is cut into m consecutive sub-vectors of dsub elements.  The codebook is
+ * f32 [m, ksub, dsub], contiguous: codebook[(j*ksub + c)*dsub + t] is element t of codeword c of sub-space j.  A stored
+ * vector is m bytes uint8, byte j naming a codeword of sub-space j.  A byte >= ksub (a foreign or stale code) is never
+ * out of bounds anywhere: see each function.
+ * Arithmetic.  Every f32 operation below is one IEEE rounding, never an fma, in the order stated, so NumPy float32
+ * reproduces every bit (tests/pq_ref.py).  bf16 inputs are widened to f32 first (exact).
+ * Limits of every function (refused before any launch, with a message): m a multiple of 4 in [4, 160]; 1 <= ksub <= 256;
+ * 1 <= dsub <= 32; row counts >= 1 (Q and N of the scan also <= 65535); every leading dimension at least the row
+ * width; dtype f32 or bf16; non-null pointers.
+ *
+ * polus_pq_encode:  x [rows, E] in `dtype`, row stride ldx >= E;  codes uint8 [rows, m], row stride ldc >= m
+ *   dist(c)     = sum over t = 0 .. dsub-1, ascending, from +0.0, of  fl(fl(x_t - cb_t) * fl(x_t - cb_t))
+ *   codes[r, j] = the lowest c < ksub that minimises dist by IEEE comparison, a NaN distance counting as +inf: a NaN
+ *                 never wins over a number, and a sub-vector whose distances are all NaN (or +inf) gets code 0.
+ *   The result depends on that sub-vector and the codebook only.  One thread per (row, sub-space), the sub-space's
+ *   codewords in LDS.
+ * polus_pq_update, one Lloyd update:  x [T, E] in `dtype`, row stride ldx;  codes uint8 [T, m], row stride ldc;  prev, out
+ *   f32 [m, ksub, dsub] (out must not alias prev);  counts int32 [m, ksub]
+ *   counts[j, c] = the number of rows t with codes[t, j] == c (codes >= ksub belong to no codeword and are skipped)
+ *   out[j, c, :] = fl(sum / f32(counts[j, c])), one division per element, where counts[j, c] > 0;  prev[j, c, :] otherwise
+ *   The sum is f32 in an order that is a function of T alone: with P = ceil(T / 64), partial l = 0 .. 63 adds, from +0.0,
+ *   the sub-vectors of the rows t in [l*P, min((l+1)*P, T)) whose code is c, in ascending t; then six rounds
+ *   p_l = fl(p_l + p_(l xor o)) for o = 32, 16, 8, 4, 2, 1 (every l at once) leave the sum in every p_l.  One wave per
+ *   (j, c), lane l holding partial l.  No atomics, no workspace, bitwise reproducible.  Index-build time work: m * ksub
+ *   reads of a code column.
+ * polus_pq_decode:  y [rows, E] in `dtype`, row stride ldy >= E
+ *   y[r, j*dsub + t] = codebook[j, codes[r, j], t] rounded once to `dtype`;  a code >= ksub decodes to zeros.
+ * polus_pq_lut, the table of one search:  q [Q, E] in `dtype`, row stride ldq >= E;  lut f32 [Q, m, ksub], contiguous
+ *   lut[b, j, c] = sum over t = 0 .. dsub-1, ascending, from +0.0, of  fl(q[b, j*dsub + t] * codebook[j, c, t])
+ * polus_pq_scores, the scan:  lut as above;  codes uint8 [N, m], row stride ldc;  score f32 [Q, N], row stride lds >= N
+ *   score[b, n] = sum over j = 0 .. m-1, ascending, from +0.0, of  lut[b, j, codes[n, j]]
+ *   A byte >= ksub reads -inf, so its document scores -inf (or NaN beside a +inf or NaN entry), which polus_topk_merge
+ *   drops.  The table may hold NaN and +-inf; they propagate by IEEE rules.  Columns past N and rows past Q of score are
+ *   not written.  The bits of a pair depend on that query's table and that document's codes only: not on Q, N, the
+ *   chunking of a corpus or how many queries a workgroup serves.  No atomics, no workspace.
+ *   One workgroup (1024 threads) serves qt consecutive queries and a contiguous range of documents.  It copies the qt
+ *   tables into dynamic LDS interleaved as [m][256][qt] floats, every sub-space padded to 256 entries with -inf:
+ *   qt * m * 1024 bytes.  A thread owns a document from its first look-up to the store: it reads the m code bytes in
+ *   16-byte pieces (codes, ldc and m multiples of 16), else in 4-byte pieces (multiples of 4), else byte by byte, and
+ *   one LDS read of 4 * qt bytes per code fetches the entry of all qt queries.  qt is the largest of 4, 2, 1 that is
+ *   <= Q and keeps qt * m * 1024 <= 163840 (one CU's LDS: m = 160 at qt = 1 fills it, whence the limit on m); the last
+ *   group of a Q that is no multiple of qt repeats query Q - 1 in its spare slots and stores nothing for them.
+ * polus_pq_scores_route (host only, no HIP call) applies the limits and reports out[0] = qt, out[1] = the dynamic LDS
+ * bytes. */
+#define POLUS_PQ_ROUTE_INTS 2
+int polus_pq_encode(int dtype, const void* x, long ldx, const float* codebook, uint8_t* codes, long ldc, int rows, int m,
+                    int ksub, int dsub, void* stream);
+int polus_pq_update(int dtype, const void* x, long ldx, const uint8_t* codes, long ldc, const float* prev, float* out,
+                    int32_t* counts, int T, int m, int ksub, int dsub, void* stream);
+int polus_pq_decode(const uint8_t* codes, long ldc, const float* codebook, int dtype, void* y, long ldy, int rows, int m,
+                    int ksub, int dsub, void* stream);
+int polus_pq_lut(int dtype, const void* q, long ldq, const float* codebook, float* lut, int Q, int m, int ksub, int dsub,
+                 void* stream);
+int polus_pq_scores(const float* lut, const uint8_t* codes, long ldc, float* score, long lds, int Q, int N, int m, int ksub,
+                    void* stream);
+int polus_pq_scores_route(int Q, int N, int m, int ksub, int* out);
+
 /* ---- argmax over the last axis (PolusClassifier.inference, polus/models.py:148-150) */
 int polus_argmax(const float* x, long ldx, int32_t* out, int rows, int C, void* stream);
 

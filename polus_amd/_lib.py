@@ -122,6 +122,12 @@ SIGNATURES = {
     "polus_postings_scores": (_i, [_vp, _l, _vp, _l, _vp, _i, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _vp, _l, _i, _vp]),
     "polus_mine_negatives": (_i, [_vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i, _f, _i, _u32, _vp, _vp, _vp, _vp]),
     "polus_fuse_lists": (_i, [_vp, _l, _l, _vp, _l, _l, _i, _i, _i, _i, _i, _c.POINTER(_f), _f, _vp, _l, _vp, _l, _vp, _vp]),
+    "polus_pq_encode": (_i, [_i, _vp, _l, _vp, _vp, _l, _i, _i, _i, _i, _vp]),
+    "polus_pq_update": (_i, [_i, _vp, _l, _vp, _l, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "polus_pq_decode": (_i, [_vp, _l, _vp, _i, _vp, _l, _i, _i, _i, _i, _vp]),
+    "polus_pq_lut": (_i, [_i, _vp, _l, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "polus_pq_scores": (_i, [_vp, _vp, _l, _vp, _l, _i, _i, _i, _i, _vp]),
+    "polus_pq_scores_route": (_i, [_i, _i, _i, _i, _c.POINTER(_i)]),
     "polus_argmax": (_i, [_vp, _l, _vp, _i, _i, _vp]),
     "polus_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64,
                              _f, _f, _f, _f, _f, _f, _f, _vp, _vp]),

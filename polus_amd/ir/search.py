@@ -59,6 +59,18 @@ a document it does not rerank, and with `nprobe` not even its codes, so there is
 bits).  All of the error is the quantiser's.  Recall and score error of 1-, 2- and 4-bit
 residuals have not been measured on any real collection here.
 
+A [CLS] index can be stored product-quantised (Jegou et al.): a vector of E = m * dsub features becomes m bytes, each
+naming one of ksub <= 256 codewords of its sub-space, 96 bytes against 1536 at E = 768 in bf16 with dsub = 8.
+
+    codec = index.fit_pq(96)                            # Lloyd rounds on the device, on a plain [CLS] "training" index
+    small = CorpusIndex(model, compute_scores, post_process_logits, storage="pq", codec=codec)
+    for docs in corpus_batches: small.add(docs)         # project, post-process, nearest codeword per sub-space
+
+`search` computes every query's dot products with all m * ksub codewords once (ops.pq_lut) and scores a document by m
+table look-ups (ops.pq_scores, the asymmetric-distance scan): the score is the dot product of the query with the
+DECODED vector, summed per sub-space first, so all of the error against a plain index is the quantiser's.  Order, ties
+and padding are `search`'s own.  Recall against the exact search has not been measured on any real collection.
+
 A learned sparse (SPLADE) first stage is a SparseCorpusIndex: per document its best (term id, weight) pairs, dense
 queries, every document scored for every query (ops.sparse_scores).  With `postings=True` it searches block-inverted
 postings instead (polus_amd/ir/postings.py has the format and the score rule): the dense queries become lists of their
@@ -71,7 +83,7 @@ representations wider than 40 960 columns are accepted.
 As in ir/training.py, arithmetic is hand-written HIP (ops.gemm / ops.maxsim_scores / ops.maxsim_rerank,
 ops.l2norm_fwd, ops.topk_merge, ops.centroid_scores / centroid_scores_ids / centroid_codes / centroid_update,
 ops.ivf_count / ivf_offsets / ivf_fill / ivf_mark / ivf_compact, ops.residual_compress /
-residual_decompress / maxsim_rerank_res); torch allocates, views and copies.  Data parallelism: every rank holds the whole
+residual_decompress / maxsim_rerank_res, ops.pq_encode / pq_update / pq_decode / pq_lut / pq_scores); torch allocates, views and copies.  Data parallelism: every rank holds the whole
 index and searches its own shard of the queries; ValidationDataCallback gathers the predictions."""
 import numpy as np
 import torch
@@ -85,6 +97,7 @@ from .store import RowStore, check_candidates, score_chunks, stored, stored_rows
 MAX_K = 1024                  # results per query: the limit of ops.topk_merge
 MAX_CENTROIDS = 65535         # codes are 16 bits and 0xFFFF is "no token"
 ASSIGN_ROWS = 16384           # tokens per nearest-centroid GEMM, at most (see CorpusIndex._assign_rows)
+PQ_MAX_M = 160                # bytes per product-quantised vector: one query's table of 160 sub-spaces fills a CU's LDS
 
 
 class ResidualCodec:
@@ -111,6 +124,24 @@ class ResidualCodec:
         if not bool((cut[1:] >= cut[:-1]).all()) or bool(torch.isnan(cut).any()):
             raise ValueError("cutoffs must be non-decreasing (and not NaN)")
         self.centroids, self.cutoffs, self.weights, self.nbits = c, cut, w, int(nbits)
+
+
+class PQCodec:
+    """What turns a single ([CLS]) vector of E = m * dsub elements into m bytes and back (product quantisation; the
+    format and rules are include/polus_hip.h polus_pq_encode): `codebooks` f32 [m, ksub, dsub], an array or a tensor,
+    codeword c of sub-space j in codebooks[j, c]; m a multiple of 4 in [4, 160], 1 <= ksub <= 256, 1 <= dsub <= 32.
+    CorpusIndex.fit_pq makes one from a sample of a corpus."""
+
+    def __init__(self, codebooks):
+        c = codebooks if isinstance(codebooks, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(codebooks))
+        if c.dim() != 3 or c.dtype != torch.float32:
+            raise ValueError(f"codebooks must be f32 [m, ksub, dsub] (got {c.dtype} {tuple(c.shape)})")
+        m, ksub, dsub = c.shape
+        if not 4 <= m <= PQ_MAX_M or m % 4 or not 1 <= ksub <= 256 or not 1 <= dsub <= 32:
+            raise ValueError(f"codebooks [m, ksub, dsub] need m a multiple of 4 in [4, {PQ_MAX_M}], 1 <= ksub <= 256 and "
+                             f"1 <= dsub <= 32 (got {tuple(c.shape)})")
+        self.codebooks = c.contiguous()
+        self.m, self.ksub, self.dsub, self.E = int(m), int(ksub), int(dsub), int(m * dsub)
 
 
 class _ClsVectors:
@@ -146,6 +177,36 @@ class _ClsVectors:
 
     def representations(self):
         return self.store.view("reps")
+
+
+class _PqVectors(_ClsVectors):
+    """The codec's codes uint8 [N, m] of [CLS] vectors.  `search` builds the queries' table once (ops.pq_lut) and a span is
+    one look-up scan (ops.pq_scores); `representations` decodes."""
+
+    def fields(self, v):
+        return dict(reps=((self.ix.codec.m,), torch.uint8, 0))
+
+    def write(self, v, m):
+        codec = self.ix.codec
+        if v.dim() != 2 or v.shape[1] != codec.E:
+            raise ValueError(f"the codec quantises vectors of {codec.E} features ({codec.m} x {codec.dsub}), the model's "
+                             f"have {tuple(v.shape[1:])}")
+        a, b = self._room(v)
+        self.cb = codec.codebooks.to(v.device)
+        ops.pq_encode(v if v.stride(1) == 1 else v.contiguous(), self.cb, self.store.bufs["reps"][a:b])
+
+    def scorer(self, q):
+        codec, codes = self.ix.codec, self.store.bufs["reps"]
+        lut = torch.empty((q.shape[0], codec.m, codec.ksub), dtype=torch.float32, device=q.device)
+        ops.pq_lut(q, self.cb, lut)
+        return lambda a, b, s: ops.pq_scores(lut, codes[a:b], s)
+
+    def representations(self):
+        codes = self.store.view("reps")
+        y = torch.empty((codes.shape[0], self.ix.codec.E), dtype=self.dtype, device=codes.device)
+        if codes.shape[0]:
+            ops.pq_decode(codes, self.cb, y)
+        return y
 
 
 class _Tokens(_ClsVectors):
@@ -298,16 +359,18 @@ class CorpusIndex:
     codes uint8 [N, Ld, E] and power-of-two scales f32 [N, Ld], include/polus_hip.h polus_fp8_quantize_rows) or
     "residual" (token representations under a scorer that normalises: the centroid codes int16 [N, Ld] of `codec`, a
     ResidualCodec, and uint8 [N, Ld, E * nbits / 8] residual bits, polus_residual_compress; on it `scratch_bytes` also
-    bounds the decoded vectors of one chunk of `search`)."""
+    bounds the decoded vectors of one chunk of `search`) or "pq" ([CLS] representations only: the m bytes uint8 [N, m] of
+    `codec`, a PQCodec, polus_pq_encode; `search` scores them by table look-ups, at most 65535 queries a call)."""
 
     def __init__(self, model, compute_scores, post_process_logits=None, scratch_bytes=256 << 20, storage=None, codec=None):
-        if storage not in (None, "fp8", "residual"):
-            raise ValueError(f"storage must be None or 'fp8' or 'residual' (got {storage!r})")
-        if (storage == "residual") != (codec is not None):
-            raise ValueError("storage='residual' needs a codec (ResidualCodec, see CorpusIndex.fit_codec), and only "
-                             "that storage takes one")
-        if codec is not None and not isinstance(codec, ResidualCodec):
-            raise ValueError(f"codec must be a ResidualCodec (got {type(codec).__name__})")
+        if storage not in (None, "fp8", "residual", "pq"):
+            raise ValueError(f"storage must be None or 'fp8' or 'residual' or 'pq' (got {storage!r})")
+        want = {"residual": ResidualCodec, "pq": PQCodec}.get(storage)
+        if (want is None) != (codec is None):
+            raise ValueError("storage='residual' needs a codec (ResidualCodec, see CorpusIndex.fit_codec) and storage='pq' "
+                             "one (PQCodec, see CorpusIndex.fit_pq), and only those storages take one")
+        if codec is not None and not isinstance(codec, want):
+            raise ValueError(f"storage={storage!r}: codec must be a {want.__name__} (got {type(codec).__name__})")
         if storage == "residual" and not bool(getattr(compute_scores, "normalize", False)):
             raise ValueError("storage='residual' needs a scorer that normalises (MaxSimScores(normalize=True)): the "
                              "nearest centroid by dot product means something on unit vectors only")
@@ -323,7 +386,7 @@ class CorpusIndex:
         """Empty the index (the storage is released; the next `add` fixes the document length again).  A residual
         index keeps its codec."""
         self._store = RowStore()
-        self._kind = {"fp8": _Fp8Tokens, "residual": _ResidualTokens}[self.storage](self) if self.storage else None
+        self._kind = {"fp8": _Fp8Tokens, "residual": _ResidualTokens, "pq": _PqVectors}[self.storage](self) if self.storage else None
         self._centroids = None                        # [K, E]; the codes are the store's int16 [cap, Ld] field
         self._cutoffs = self._weights = None          # a residual index: the codec's tables on the device
         self._lists, self._lists_stale = None, False  # inverted lists (offsets, docs) of refresh_lists
@@ -337,8 +400,15 @@ class CorpusIndex:
     @property
     def representations(self):
         """[N, E] or [N, Ld, E]: a view of the stored documents.  On an FP8 index a COPY: the codes dequantised into
-        a new tensor of the model's dtype (exactly codes * scales); writing to it does not change the index."""
+        a new tensor of the model's dtype (exactly codes * scales); writing to it does not change the index.  On a
+        PQ index a COPY as well: every vector decoded from its codes (ops.pq_decode), the vectors `search` scores up to
+        the rounding of its sums, not the ones that were added."""
         return None if self._reps is None else self._kind.representations()
+
+    @property
+    def pq_codes(self):
+        """uint8 [N, m]: a view of the stored product-quantisation codes (a PQ index; None otherwise)."""
+        return None if self.storage != "pq" else self._store.view("reps")
 
     @property
     def residuals(self):
@@ -393,16 +463,21 @@ class CorpusIndex:
                              "to the scorer (MaxSimScores(normalize=True))")
         if self.tokens is not None and tokens != self.tokens:
             raise ValueError("the index holds " + ("token" if self.tokens else "[CLS]") + " representations")
-        if self.storage is not None and not tokens:
+        if self.storage == "pq":
+            if tokens:
+                raise ValueError("storage='pq' holds single ([CLS]) vectors only: product quantisation is for one vector "
+                                 "per document, a token index has storage='fp8' and 'residual'")
+        elif self.storage is not None and not tokens:
             raise ValueError(f"storage={self.storage!r} holds token representations only; a [CLS] index stays in the "
-                             "model's dtype")
+                             "model's dtype or takes storage='pq'")
         return tokens
 
     def add(self, documents):
         """Encode, project (and normalise) a batch of documents and append it; returns its ids, the consecutive int32
         positions in the index.  Token documents are padded with masked tokens to the length of the first batch;
         a longer batch raises ValueError.  An FP8 index quantises the projected (and normalised) vectors here; a
-        residual index gives them their nearest centroid of the codec and compresses them."""
+        residual index gives them their nearest centroid of the codec and compresses them; a PQ index stores the codes
+        of the projected (and post-processed) vectors."""
         model = self.model
         rep = model.document_projection(model.encode_document(documents, training=False), training=False)
         if self._check_kind(rep):
@@ -481,7 +556,7 @@ class CorpusIndex:
 
     # ------------------------------------------------------------ centroid-pruned search
     def _check_centroid_support(self):
-        if self.codec is not None:
+        if self.storage == "residual":
             raise ValueError("a residual index takes its centroids from its codec: the stored residuals belong to "
                              "them, so they cannot be set or fitted again")
         if self._n == 0:
@@ -603,6 +678,49 @@ class CorpusIndex:
         cutoffs = np.quantile(flat64, np.arange(1, n) / n, method="linear").astype(np.float32)
         weights = np.quantile(flat64, (np.arange(n) + 0.5) / n, method="linear").astype(np.float32)
         return ResidualCodec(self._centroids.clone(), cutoffs, weights, nbits)
+
+    def _sample_rows(self, sample, seed):
+        """The sampled documents of fit_pq, in the order drawn (the rule is in fit_pq's docstring)."""
+        r = np.random.Generator(np.random.PCG64(int(seed)))
+        return r.permutation(self._n) if self._n <= int(sample) else r.choice(self._n, size=int(sample), replace=False)
+
+    def fit_pq(self, m, ksub=256, iters=8, sample=1 << 16, seed=0):
+        """A PQCodec of m sub-spaces with ksub codewords each from a sample of this index's stored vectors (a plain [CLS]
+        index: the "training" index over a sample of the corpus, as fit_codec's is for residuals).
+
+        Sample: with r = numpy.random.Generator(PCG64(seed)) the documents are r.permutation(N) when N <= sample and
+        r.choice(N, size=sample, replace=False) otherwise, in the order drawn; it depends on seed and N only.  Their
+        rows are gathered by a torch index copy.  The first ksub of them, widened to f32, are the initial codewords of
+        every sub-space; fewer than ksub raises ValueError.  Each of `iters` Lloyd rounds gives every sampled sub-vector
+        its nearest codeword (ops.pq_encode) and replaces a codeword by the mean of its sub-vectors (ops.pq_update; one
+        without any stays).  All sums run in a fixed order: the same index and seed give the same bits, so data-parallel
+        ranks holding the same corpus agree without communication."""
+        if self._n == 0:
+            raise ValueError("the index is empty: add documents before fitting a codec")
+        if self.tokens or self.storage is not None:
+            raise ValueError("fit_pq trains on a plain [CLS] index (storage=None): product quantisation is for one vector "
+                             "per document, and a compressed index no longer holds the vectors to learn from")
+        m, ksub, E = int(m), int(ksub), self._reps.shape[1]
+        if not 4 <= m <= PQ_MAX_M or m % 4 or not 1 <= ksub <= 256:
+            raise ValueError(f"need m a multiple of 4 in [4, {PQ_MAX_M}] and 1 <= ksub <= 256 (got m = {m}, ksub = {ksub})")
+        if E % m or E // m > 32:
+            raise ValueError(f"the index holds vectors of {E} features: m = {m} must divide that into sub-vectors of at "
+                             "most 32")
+        rows = self._sample_rows(sample, seed)
+        if len(rows) < ksub:
+            raise ValueError(f"{ksub} codewords need at least as many sampled documents (got {len(rows)})")
+        dev = self._reps.device
+        x = self._reps[:self._n][torch.as_tensor(rows.astype(np.int64)).to(dev)].contiguous()
+        T, dsub = x.shape[0], E // m
+        cb = x[:ksub].float().view(ksub, m, dsub).permute(1, 0, 2).contiguous()
+        nxt = torch.empty_like(cb)
+        codes = torch.empty((T, m), dtype=torch.uint8, device=dev)
+        counts = torch.empty((m, ksub), dtype=torch.int32, device=dev)
+        for _ in range(int(iters)):
+            ops.pq_encode(x, cb, codes)
+            ops.pq_update(x, codes, cb, nxt, counts)
+            cb, nxt = nxt, cb
+        return PQCodec(cb)
 
     def search_pruned(self, queries, k, candidates, nprobe=None):
         """`search` over the `candidates` documents per query that score best under the centroid approximation:
