@@ -1030,6 +1030,66 @@ int polus_pq_scores(const float* lut, const uint8_t* codes, long ldc, float* sco
                     void* stream);
 int polus_pq_scores_route(int Q, int N, int m, int ksub, int* out);
 
+/* ---- IVF-PQ of single ([CLS]) vectors (ivfpq.hip; Jegou, Douze, Schmid 2011, "IVFADC", the layout of FAISS' IVFPQ, here
+ * for inner products; no counterpart in the reference).  A coarse quantiser of K centroids splits the corpus into K
+ * lists; a document is stored as the id of its centroid and the product-quantisation codes of its RESIDUAL against that
+ * centroid, and a query scores only the documents of the lists it probes.
+ *
+ * Format.  Per document one unsigned 16-bit coarse code coarse[n], the id of its centroid; a value >= K (0xFFFF among
+ * them) is "no list".  Beside it m bytes uint8 of PQ codes, the format and limits of the section above (m a multiple of 4
+ * in [4, 160]; 1 <= ksub <= 256; 1 <= dsub <= 32; E = m * dsub), naming the codewords of the residual's sub-vectors.  The
+ * coarse centroids are [K, E], contiguous, in the index's dtype (f32 or bf16); 1 <= K <= 65535.
+ * Arithmetic.  As above: every f32 operation is one IEEE rounding, never an fma, in the order stated, so NumPy float32
+ * reproduces every bit (tests/ivfpq_ref.py); bf16 inputs are widened to f32 first (exact).
+ *
+ * polus_ivfpq_residual:  x [rows, E] in `dtype`, row stride ldx >= E;  cent [K, E] in `dtype`;  coarse uint16 [rows];
+ *   r f32 [rows, E], row stride ldr >= E
+ *   r[t, e] = fl(f32(x[t, e]) - f32(cent[coarse[t], e])), one rounding;  a row whose coarse code is >= K gives zeros and
+ *   reads no centroid.  The centroid is the one STORED in the index's dtype, so that <q, cent> from polus_gemm over the
+ *   same array and the stored residual refer to the same vector.  One thread per output.  1 <= E <= 5120.
+ * polus_ivfpq_coarse_update, one Lloyd step on whole vectors:  x [T, E] in `dtype`, row stride ldx;  coarse uint16 [T];
+ *   prev, out [K, E] in `dtype`, contiguous (out must not overlap prev);  counts int32 [K]
+ *   counts[k] = the number of rows t with coarse[t] == k (codes >= K belong to no centroid and are skipped)
+ *   out[k, :] = fl(sum / f32(counts[k])), one division per element, rounded once to `dtype`, where counts[k] > 0;
+ *               prev[k, :] otherwise
+ *   The sum follows polus_pq_update's order rule, a function of T alone: with P = ceil(T / 64), partial l = 0 .. 63 adds,
+ *   from +0.0, the rows t in [l*P, min((l+1)*P, T)) whose code is k, in ascending t; then six rounds
+ *   p_l = fl(p_l + p_(l xor o)) for o = 32, 16, 8, 4, 2, 1.  One workgroup of 4 waves per centroid, lane l holding partial
+ *   l for 16 features at a time.  No atomics, no workspace, bitwise reproducible.  Index-build time work: every
+ *   wave reads the code array once per 64 features, E / 16 reads per centroid.  1 <= E <= 5120.
+ * polus_ivfpq_scores_ids, the scan over candidate lists:  lut f32 [Q, m, ksub], contiguous (polus_pq_lut of the queries
+ *   with the RESIDUAL codebook);  cdot f32 [Q, K], row stride ldd >= K, cdot[b, c] = <q_b, cent_c>, an input (one
+ *   polus_gemm);  coarse uint16 [N];  codes uint8 [N, m], row stride ldc;  cand int32 [Q, C], row stride ldcand >= C, or
+ *   NULL;  score f32 [Q, C], row stride lds >= C
+ *   n           = cand[b, c], or c where cand == NULL (then C must equal N: the exhaustive route, for which the caller
+ *                 offsets coarse and codes per chunk of a corpus)
+ *   acc         = sum over j = 0 .. m-1, ascending, from +0.0, of  lut[b, j, codes[n, j]]     (polus_pq_scores' rule)
+ *   score[b, c] = fl(cdot[b, coarse[n]] + acc), one more rounding
+ *   coarse[n] >= K: score = -inf and nothing is read from cdot for it.  A code byte >= ksub reads -inf through the
+ *   table's padding, as in polus_pq_scores.  n outside [0, N): score = -inf and nothing is read for it (-inf is what
+ *   polus_topk_merge_ids drops).  A repeated id is scored once per copy.  Columns past C are not written.  lut and cdot
+ *   may hold NaN and +-inf; they propagate by IEEE rules.  The bits of a score depend on its (query, document) pair
+ *   only: not on Q, C, the order of the candidates, the chunking or the route.  No atomics, no workspace.
+ *   One workgroup (1024 threads) serves one query and a contiguous range of its candidate columns.  It copies that
+ *   query's table into dynamic LDS as [m][256] floats, every sub-space padded to 256 entries with -inf: m * 1024 bytes,
+ *   polus_pq_scores' layout at qt = 1 (candidate lists differ per query, so no code byte serves two queries).  A thread
+ *   owns a candidate from its first look-up to the store; it reads the code row at codes + n * ldc in 16-byte pieces
+ *   (codes, ldc and m multiples of 16), else in 4-byte pieces (multiples of 4), else byte by byte.  Each query's columns
+ *   are spread over the CUs (two workgroups per CU where two tables fit its LDS), at least 256 columns a workgroup.
+ *   Limits (refused before any launch): the PQ limits; 1 <= Q, C <= 65535; N >= 1; 1 <= K <= 65535; ldd >= K; ldc >= m;
+ *   ldcand >= C; lds >= C; C == N without cand; non-null pointers except cand.
+ * polus_ivfpq_scores_ids_route (launches nothing) applies the scan's shape limits and reports out[0] = the dynamic LDS
+ * bytes and out[1] = the columns per workgroup, which follow the CU count of the current device (256 without one). */
+#define POLUS_IVFPQ_ROUTE_INTS 2
+int polus_ivfpq_scores_ids(const float* lut, const float* cdot, long ldd, const uint16_t* coarse, const uint8_t* codes,
+                           long ldc, const int32_t* cand, long ldcand, float* score, long lds, int Q, int C, int N, int m,
+                           int ksub, int K, void* stream);
+int polus_ivfpq_scores_ids_route(int Q, int C, int m, int ksub, int* out);
+int polus_ivfpq_residual(int dtype, const void* x, long ldx, const void* cent, const uint16_t* coarse, float* r, long ldr,
+                         int rows, int K, int E, void* stream);
+int polus_ivfpq_coarse_update(int dtype, const void* x, long ldx, const uint16_t* coarse, const void* prev, void* out,
+                              int32_t* counts, int T, int K, int E, void* stream);
+
 /* ---- argmax over the last axis (PolusClassifier.inference, polus/models.py:148-150) */
 int polus_argmax(const float* x, long ldx, int32_t* out, int rows, int C, void* stream);
 

@@ -128,6 +128,10 @@ SIGNATURES = {
     "polus_pq_lut": (_i, [_i, _vp, _l, _vp, _vp, _i, _i, _i, _i, _vp]),
     "polus_pq_scores": (_i, [_vp, _vp, _l, _vp, _l, _i, _i, _i, _i, _vp]),
     "polus_pq_scores_route": (_i, [_i, _i, _i, _i, _c.POINTER(_i)]),
+    "polus_ivfpq_scores_ids": (_i, [_vp, _vp, _l, _vp, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i, _i, _i, _vp]),
+    "polus_ivfpq_scores_ids_route": (_i, [_i, _i, _i, _i, _c.POINTER(_i)]),
+    "polus_ivfpq_residual": (_i, [_i, _vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _vp]),
+    "polus_ivfpq_coarse_update": (_i, [_i, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "polus_argmax": (_i, [_vp, _l, _vp, _i, _i, _vp]),
     "polus_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64,
                              _f, _f, _f, _f, _f, _f, _f, _vp, _vp]),

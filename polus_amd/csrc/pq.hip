@@ -10,18 +10,9 @@
 // lanes of a step read sub-space j at columns chosen by the data: the kernel is bound by those LDS gathers, not by HBM.
 // The code bytes travel in 16-byte pieces, the next piece loaded while the current one is looked up.
 // The build-time kernels (encode, update, decode, lut) are plain: one thread per output, or one wave per codeword.
-#include <algorithm>
-
-#include "common.h"
+#include "pq_common.h"
 
 namespace {
-
-constexpr int PQ_MMAX = 160, PQ_KMAX = 256, PQ_DMAX = 32;
-constexpr size_t PQ_LDS_MAX = 160 * 1024;         // one CU's LDS
-constexpr int PQ_SCAN_THREADS = 1024;
-constexpr int PQ_ROWS_MAX = 65535;
-
-static inline size_t pq_lds_bytes(int qt, int m) { return (size_t)qt * m * 256 * sizeof(float); }
 
 // Queries per workgroup: from Q, m and the LDS budget alone.
 static inline int pq_qt(int Q, int m) {
@@ -30,37 +21,10 @@ static inline int pq_qt(int Q, int m) {
     return 1;
 }
 
-// Documents per workgroup: one workgroup per CU over the launch where the tables leave room for one, two where they
-// leave room for two (2048 threads per CU), never fewer than 256 documents unless N is smaller: the copy of the tables is
-// a fixed price per workgroup, and a CU without a workgroup pays nothing either.
-static int pq_docs_per_block(int groups, int N, size_t lds) {
-    const long per_cu = lds * 2 <= PQ_LDS_MAX ? 2 : 1;
-    const long per_group = std::max(1L, per_cu * polus_num_cus() / groups);
-    long dpb = ((long)N + per_group - 1) / per_group;
-    dpb = std::max((dpb + 63) / 64 * 64, 256L);
-    return (int)std::min(dpb, (long)N);
-}
-
 template <int QT> struct PqEntry;
 template <> struct PqEntry<1> { typedef float type; };
 template <> struct PqEntry<2> { typedef float2 type; };
 template <> struct PqEntry<4> { typedef float4 type; };
-
-// Four code bytes at p as one word (byte k in bits 8k .. 8k+7): one load where p is 4-byte aligned.
-template <bool ALIGNED> __device__ __forceinline__ uint32_t pq_word(const uint8_t* p) {
-    if constexpr (ALIGNED) return *reinterpret_cast<const uint32_t*>(p);
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-
-// PIECE: 16 (codes, ldc and m multiples of 16), 4 (multiples of 4) or 1 (anything: four byte loads per word).
-template <int PIECE> __device__ __forceinline__ void pq_piece(const uint8_t* p, uint32_t (&w)[PIECE == 16 ? 4 : 1]) {
-    if constexpr (PIECE == 16) {
-        const uint4 v = *reinterpret_cast<const uint4*>(p);
-        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-    } else {
-        w[0] = pq_word<PIECE == 4>(p);
-    }
-}
 
 template <int QT, int PIECE>
 __global__ __launch_bounds__(PQ_SCAN_THREADS) void pq_scores_kernel(const float* __restrict__ lut,
@@ -129,9 +93,10 @@ int pq_scores_launch(const float* lut, const uint8_t* codes, long ldc, float* sc
 template <int QT>
 int pq_scores_pieces(const float* lut, const uint8_t* codes, long ldc, float* score, long lds, int Q, int N, int m, int ksub,
                      hipStream_t st) {
-    const uintptr_t bits = (uintptr_t)codes | (uintptr_t)ldc | (uintptr_t)m;
-    if ((bits & 15) == 0) return pq_scores_launch<QT, 16>(lut, codes, ldc, score, lds, Q, N, m, ksub, st);
-    if ((bits & 3) == 0) return pq_scores_launch<QT, 4>(lut, codes, ldc, score, lds, Q, N, m, ksub, st);
+    switch (pq_piece_bytes(codes, ldc, m)) {
+        case 16: return pq_scores_launch<QT, 16>(lut, codes, ldc, score, lds, Q, N, m, ksub, st);
+        case 4: return pq_scores_launch<QT, 4>(lut, codes, ldc, score, lds, Q, N, m, ksub, st);
+    }
     return pq_scores_launch<QT, 1>(lut, codes, ldc, score, lds, Q, N, m, ksub, st);
 }
 
@@ -242,22 +207,12 @@ __global__ __launch_bounds__(256) void pq_lut_kernel(const T* __restrict__ q, lo
     lut[i] = s;
 }
 
-int pq_check_format(const char* what, int m, int ksub, int dsub) {
-    POLUS_REQUIRE(m >= 4 && m <= PQ_MMAX && m % 4 == 0, "%s: m must be a multiple of 4 in [4, %d] (got %d)", what, PQ_MMAX, m);
-    POLUS_REQUIRE(ksub >= 1 && ksub <= PQ_KMAX, "%s: need 1 <= ksub <= %d (got %d)", what, PQ_KMAX, ksub);
-    POLUS_REQUIRE(dsub >= 1 && dsub <= PQ_DMAX, "%s: need 1 <= dsub <= %d (got %d)", what, PQ_DMAX, dsub);
-    return POLUS_OK;
-}
-
 int pq_check_scan(const char* what, int Q, int N, int m, int ksub) {
     if (int rc = pq_check_format(what, m, ksub, 1)) return rc;
     POLUS_REQUIRE(Q >= 1 && Q <= PQ_ROWS_MAX, "%s: need 1 <= Q <= %d (got %d)", what, PQ_ROWS_MAX, Q);
     POLUS_REQUIRE(N >= 1 && N <= PQ_ROWS_MAX, "%s: need 1 <= N <= %d (got %d)", what, PQ_ROWS_MAX, N);
     return POLUS_OK;
 }
-
-#define PQ_CHECK_DTYPE(what, dtype) \
-    POLUS_REQUIRE(dtype == POLUS_F32 || dtype == POLUS_BF16, "%s: unknown dtype %d", what, dtype)
 
 }  // namespace
 

@@ -71,6 +71,22 @@ table look-ups (ops.pq_scores, the asymmetric-distance scan): the score is the d
 DECODED vector, summed per sub-space first, so all of the error against a plain index is the quantiser's.  Order, ties
 and padding are `search`'s own.  Recall against the exact search has not been measured on any real collection.
 
+A PQ index still scans every document.  An IVF-PQ index (Jegou et al., "IVFADC", FAISS' IVFPQ layout, here for inner
+products) does not have to: a coarse quantiser of K centroids splits the corpus into K lists, a document is stored as
+the 16-bit id of its L2-nearest centroid plus the m PQ bytes of its RESIDUAL against it (m + 2 bytes), and a search
+scores only the lists of the `nprobe` centroids with the largest dot product with the query.
+
+    codec = index.fit_ivfpq(1024, 96)                   # coarse Lloyd rounds, then PQ Lloyd rounds on the residuals
+    small = CorpusIndex(model, compute_scores, post_process_logits, storage="ivfpq", codec=codec, nprobe=16)
+    for docs in corpus_batches: small.add(docs)         # project, post-process, nearest centroid, residual, encode
+    scores, ids = small.search(queries, k=100)          # or search(queries, 100, nprobe=4); nprobe unset: every document
+
+The score of a document is <q, centroid> + the look-up sum over its residual codes (ops.ivfpq_scores_ids): the dot
+product with centroid + decoded residual, the same bits whether it is reached by a probe or by the exhaustive scan, so
+with nprobe = K the result is the exhaustive one, bit for bit.  What is approximate under `nprobe`: WHICH documents are
+scored.  Because `search(queries, k)` falls back to the index's own `nprobe`, TwoStageSearch, HybridSearch and
+mine_negatives get a probed first stage unchanged.  Recall on a real collection has not been measured.
+
 A learned sparse (SPLADE) first stage is a SparseCorpusIndex: per document its best (term id, weight) pairs, dense
 queries, every document scored for every query (ops.sparse_scores).  With `postings=True` it searches block-inverted
 postings instead (polus_amd/ir/postings.py has the format and the score rule): the dense queries become lists of their
@@ -83,7 +99,8 @@ representations wider than 40 960 columns are accepted.
 As in ir/training.py, arithmetic is hand-written HIP (ops.gemm / ops.maxsim_scores / ops.maxsim_rerank,
 ops.l2norm_fwd, ops.topk_merge, ops.centroid_scores / centroid_scores_ids / centroid_codes / centroid_update,
 ops.ivf_count / ivf_offsets / ivf_fill / ivf_mark / ivf_compact, ops.residual_compress /
-residual_decompress / maxsim_rerank_res, ops.pq_encode / pq_update / pq_decode / pq_lut / pq_scores); torch allocates, views and copies.  Data parallelism: every rank holds the whole
+residual_decompress / maxsim_rerank_res, ops.pq_encode / pq_update / pq_decode / pq_lut / pq_scores,
+ops.ivfpq_residual / ivfpq_coarse_update / ivfpq_scores_ids); torch allocates, views and copies.  Data parallelism: every rank holds the whole
 index and searches its own shard of the queries; ValidationDataCallback gathers the predictions."""
 import numpy as np
 import torch
@@ -142,6 +159,33 @@ class PQCodec:
                              f"1 <= dsub <= 32 (got {tuple(c.shape)})")
         self.codebooks = c.contiguous()
         self.m, self.ksub, self.dsub, self.E = int(m), int(ksub), int(dsub), int(m * dsub)
+
+
+def _half_norms(centroids):
+    """f32 [K] on the host: -|c|^2 / 2 per row of `centroids` (a tensor), summed in float64 and rounded once.  As the bias of
+    the similarity GEMM it turns the arg-max over centroids into the L2-nearest one: |x - c|^2 = |x|^2 - 2 (x.c - |c|^2 / 2)."""
+    c = centroids.detach().float().cpu().numpy().astype(np.float64)
+    return torch.as_tensor((-0.5 * (c * c).sum(axis=1)).astype(np.float32))
+
+
+class IVFPQCodec:
+    """What turns a single ([CLS]) vector into the 16-bit id of its L2-nearest coarse centroid plus the m PQ bytes of its
+    residual against that centroid, and back (the format and rules are include/polus_hip.h "IVF-PQ"): `centroids` [K, E],
+    an array or a tensor, 1 <= K <= 65535, cast to the index's dtype when the index stores them; `codebooks` f32
+    [m, ksub, dsub] with PQCodec's limits and m * dsub == E.  `half_norms` f32 [K] = -|c|^2 / 2, computed once on the
+    host in float64.  CorpusIndex.fit_ivfpq makes one from a sample of a corpus."""
+
+    def __init__(self, centroids, codebooks):
+        pq = PQCodec(codebooks)
+        c = centroids if isinstance(centroids, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(centroids))
+        if c.dim() != 2 or not 1 <= c.shape[0] <= MAX_CENTROIDS or not c.dtype.is_floating_point:
+            raise ValueError(f"centroids must be a floating-point [K, E] with 1 <= K <= {MAX_CENTROIDS} (got {c.dtype} "
+                             f"{tuple(c.shape)})")
+        if c.shape[1] != pq.E:
+            raise ValueError(f"centroids have {c.shape[1]} features, the codebooks quantise {pq.E} ({pq.m} x {pq.dsub})")
+        self.centroids, self.codebooks = c.contiguous(), pq.codebooks
+        self.m, self.ksub, self.dsub, self.E, self.K = pq.m, pq.ksub, pq.dsub, pq.E, int(c.shape[0])
+        self.half_norms = _half_norms(self.centroids)
 
 
 class _ClsVectors:
@@ -209,6 +253,58 @@ class _PqVectors(_ClsVectors):
         return y
 
 
+class _IvfPqVectors(_PqVectors):
+    """The codec's coarse codes int16 [N] (fill -1 = 0xFFFF, "no list") and the PQ codes uint8 [N, m] of the residuals.  A
+    span, or a list of candidate ids, is one look-up scan (ops.ivfpq_scores_ids) over the queries' table and their dot
+    products with the centroids; `representations` decodes centroid + residual."""
+
+    def fields(self, v):
+        return dict(reps=((self.ix.codec.m,), torch.uint8, 0), coarse=((), torch.int16, -1))
+
+    def write(self, v, m):
+        ix, codec = self.ix, self.ix.codec
+        if v.dim() != 2 or v.shape[1] != codec.E:
+            raise ValueError(f"the codec quantises vectors of {codec.E} features ({codec.m} x {codec.dsub}), the model's "
+                             f"have {tuple(v.shape[1:])}")
+        a, b = self._room(v)
+        if ix._centroids is None:
+            ix._centroids = codec.centroids.to(device=v.device, dtype=v.dtype).contiguous().clone()
+            self.cb, self.half_norms = codec.codebooks.to(v.device), codec.half_norms.to(v.device)
+        v = v if v.stride(1) == 1 else v.contiguous()
+        coarse = self.store.bufs["coarse"][a:b]
+        ix._assign_rows(lambda s, e, dst: dst.copy_(v[s:e]), b - a, None, coarse, ix._centroids, bias=self.half_norms)
+        r = torch.empty((b - a, codec.E), dtype=torch.float32, device=v.device)
+        ops.ivfpq_residual(v, ix._centroids, coarse, r)
+        ops.pq_encode(r, self.cb, self.store.bufs["reps"][a:b])
+
+    def tables(self, q):
+        """(lut f32 [Q, m, ksub], cdot f32 [Q, K]) of one search: the queries against the residual codewords and the centroids."""
+        codec, cent = self.ix.codec, self.ix._centroids
+        lut = torch.empty((q.shape[0], codec.m, codec.ksub), dtype=torch.float32, device=q.device)
+        ops.pq_lut(q, self.cb, lut)
+        cdot = torch.empty((q.shape[0], cent.shape[0]), dtype=torch.float32, device=q.device)
+        ops.gemm(q, cent, cdot)
+        return lut, cdot
+
+    def scorer(self, q):
+        lut, cdot = self.tables(q)
+        coarse, codes = self.store.bufs["coarse"], self.store.bufs["reps"]
+        return lambda a, b, s: ops.ivfpq_scores_ids(lut, cdot, coarse[a:b], codes[a:b], None, s)
+
+    def list_codes(self):
+        return self.store.view("coarse").view(-1, 1)             # the lists' CSR with one "token" per document
+
+    def representations(self):
+        """centroid + decoded residual, added in f32 and rounded once to the index's dtype (torch: an accessor, not a
+        search path)."""
+        codes, coarse = self.store.view("reps"), self.store.view("coarse")
+        res = torch.empty((codes.shape[0], self.ix.codec.E), dtype=torch.float32, device=codes.device)
+        if not codes.shape[0]:
+            return res.to(self.dtype)
+        ops.pq_decode(codes, self.cb, res)
+        return (self.ix._centroids[coarse.to(torch.int64) & 0xFFFF].float() + res).to(self.dtype)
+
+
 class _Tokens(_ClsVectors):
     """Token vectors [N, Ld, E] in the model's dtype with their int32 mask [N, Ld]."""
 
@@ -224,6 +320,9 @@ class _Tokens(_ClsVectors):
 
     def put(self, a, b, v):
         self.store.bufs["reps"][a:b, :v.shape[1]].copy_(v)
+
+    def list_codes(self):
+        return self.store.view("codes")
 
     def scorer(self, q):
         reps, mask = self.store.bufs["reps"], self.store.bufs["mask"]
@@ -360,21 +459,30 @@ class CorpusIndex:
     "residual" (token representations under a scorer that normalises: the centroid codes int16 [N, Ld] of `codec`, a
     ResidualCodec, and uint8 [N, Ld, E * nbits / 8] residual bits, polus_residual_compress; on it `scratch_bytes` also
     bounds the decoded vectors of one chunk of `search`) or "pq" ([CLS] representations only: the m bytes uint8 [N, m] of
-    `codec`, a PQCodec, polus_pq_encode; `search` scores them by table look-ups, at most 65535 queries a call)."""
+    `codec`, a PQCodec, polus_pq_encode; `search` scores them by table look-ups, at most 65535 queries a call) or "ivfpq"
+    ([CLS] representations only: per document the coarse code int16 and the m bytes of its residual under `codec`, an
+    IVFPQCodec; `nprobe`, which only this storage takes, is the number of lists `search` probes when the call names
+    none: None scores every document)."""
 
-    def __init__(self, model, compute_scores, post_process_logits=None, scratch_bytes=256 << 20, storage=None, codec=None):
-        if storage not in (None, "fp8", "residual", "pq"):
-            raise ValueError(f"storage must be None or 'fp8' or 'residual' or 'pq' (got {storage!r})")
-        want = {"residual": ResidualCodec, "pq": PQCodec}.get(storage)
+    def __init__(self, model, compute_scores, post_process_logits=None, scratch_bytes=256 << 20, storage=None, codec=None,
+                 nprobe=None):
+        if storage not in (None, "fp8", "residual", "pq", "ivfpq"):
+            raise ValueError(f"storage must be None or 'fp8' or 'residual' or 'pq' or 'ivfpq' (got {storage!r})")
+        want = {"residual": ResidualCodec, "pq": PQCodec, "ivfpq": IVFPQCodec}.get(storage)
         if (want is None) != (codec is None):
-            raise ValueError("storage='residual' needs a codec (ResidualCodec, see CorpusIndex.fit_codec) and storage='pq' "
-                             "one (PQCodec, see CorpusIndex.fit_pq), and only those storages take one")
+            raise ValueError("storage='residual' needs a codec (ResidualCodec, see CorpusIndex.fit_codec), storage='pq' "
+                             "one (PQCodec, see CorpusIndex.fit_pq) and storage='ivfpq' one (IVFPQCodec, see "
+                             "CorpusIndex.fit_ivfpq), and only those storages take one")
         if codec is not None and not isinstance(codec, want):
             raise ValueError(f"storage={storage!r}: codec must be a {want.__name__} (got {type(codec).__name__})")
         if storage == "residual" and not bool(getattr(compute_scores, "normalize", False)):
             raise ValueError("storage='residual' needs a scorer that normalises (MaxSimScores(normalize=True)): the "
                              "nearest centroid by dot product means something on unit vectors only")
+        if nprobe is not None and storage != "ivfpq":
+            raise ValueError(f"nprobe belongs to storage='ivfpq', whose search probes lists (got storage={storage!r}); a "
+                             "token index takes it per call, search_pruned(..., nprobe)")
         self.storage, self.codec = storage, codec
+        self.nprobe = None if nprobe is None else self._check_nprobe(nprobe, codec.K)
         self.model, self.compute_scores = model, compute_scores
         self.post_process_logits = post_process_logits
         self.scratch_bytes = int(scratch_bytes)
@@ -386,7 +494,7 @@ class CorpusIndex:
         """Empty the index (the storage is released; the next `add` fixes the document length again).  A residual
         index keeps its codec."""
         self._store = RowStore()
-        self._kind = {"fp8": _Fp8Tokens, "residual": _ResidualTokens, "pq": _PqVectors}[self.storage](self) if self.storage else None
+        self._kind = {"fp8": _Fp8Tokens, "residual": _ResidualTokens, "pq": _PqVectors, "ivfpq": _IvfPqVectors}[self.storage](self) if self.storage else None
         self._centroids = None                        # [K, E]; the codes are the store's int16 [cap, Ld] field
         self._cutoffs = self._weights = None          # a residual index: the codec's tables on the device
         self._lists, self._lists_stale = None, False  # inverted lists (offsets, docs) of refresh_lists
@@ -402,13 +510,21 @@ class CorpusIndex:
         """[N, E] or [N, Ld, E]: a view of the stored documents.  On an FP8 index a COPY: the codes dequantised into
         a new tensor of the model's dtype (exactly codes * scales); writing to it does not change the index.  On a
         PQ index a COPY as well: every vector decoded from its codes (ops.pq_decode), the vectors `search` scores up to
-        the rounding of its sums, not the ones that were added."""
+        the rounding of its sums, not the ones that were added; an IVF-PQ index adds the document's centroid to its decoded
+        residual in f32 and rounds once to the index's dtype."""
         return None if self._reps is None else self._kind.representations()
 
     @property
     def pq_codes(self):
-        """uint8 [N, m]: a view of the stored product-quantisation codes (a PQ index; None otherwise)."""
-        return None if self.storage != "pq" else self._store.view("reps")
+        """uint8 [N, m]: a view of the stored product-quantisation codes (a PQ index, or an IVF-PQ index: the codes of the
+        residuals; None otherwise)."""
+        return None if self.storage not in ("pq", "ivfpq") else self._store.view("reps")
+
+    @property
+    def coarse_codes(self):
+        """int16 [N]: a view of the stored coarse codes, the bits of the unsigned centroid id (an IVF-PQ index; None
+        otherwise)."""
+        return self._store.view("coarse")
 
     @property
     def residuals(self):
@@ -429,7 +545,7 @@ class CorpusIndex:
     def centroids(self):
         """[K, E] in the index's dtype: the centroids of set_centroids / fit_centroids (None before).  A residual
         index: its codec's (as the codec holds them until the first `add` moves them to the device)."""
-        if self._centroids is None and self.storage == "residual":
+        if self._centroids is None and self.storage in ("residual", "ivfpq"):
             return self.codec.centroids
         return self._centroids
 
@@ -442,7 +558,7 @@ class CorpusIndex:
     @property
     def nbytes(self):
         """Bytes of the stored representations, scales, mask and centroid codes of the len(index) documents, and of
-        the inverted lists once a probed search has built them (4 (K + 1) + 4 P)."""
+        the inverted lists once a probed search has built them (4 (K + 1) + 4 P; an IVF-PQ index: N (m + 2), and P = N)."""
         return sum(t[:self._n].numel() * t.element_size() for t in self._store.bufs.values()) + sum(
             t.numel() * t.element_size() for t in self._lists or ())
 
@@ -463,13 +579,13 @@ class CorpusIndex:
                              "to the scorer (MaxSimScores(normalize=True))")
         if self.tokens is not None and tokens != self.tokens:
             raise ValueError("the index holds " + ("token" if self.tokens else "[CLS]") + " representations")
-        if self.storage == "pq":
+        if self.storage in ("pq", "ivfpq"):
             if tokens:
-                raise ValueError("storage='pq' holds single ([CLS]) vectors only: product quantisation is for one vector "
-                                 "per document, a token index has storage='fp8' and 'residual'")
+                raise ValueError(f"storage={self.storage!r} holds single ([CLS]) vectors only: product quantisation is for "
+                                 "one vector per document, a token index has storage='fp8' and 'residual'")
         elif self.storage is not None and not tokens:
             raise ValueError(f"storage={self.storage!r} holds token representations only; a [CLS] index stays in the "
-                             "model's dtype or takes storage='pq'")
+                             "model's dtype or takes storage='pq' or 'ivfpq'")
         return tokens
 
     def add(self, documents):
@@ -477,7 +593,9 @@ class CorpusIndex:
         positions in the index.  Token documents are padded with masked tokens to the length of the first batch;
         a longer batch raises ValueError.  An FP8 index quantises the projected (and normalised) vectors here; a
         residual index gives them their nearest centroid of the codec and compresses them; a PQ index stores the codes
-        of the projected (and post-processed) vectors."""
+        of the projected (and post-processed) vectors; an IVF-PQ index gives them their L2-nearest coarse centroid
+        (ops.gemm with the bias -|c|^2 / 2, then ops.centroid_codes), takes the residual (ops.ivfpq_residual) and stores
+        its codes (ops.pq_encode)."""
         model = self.model
         rep = model.document_projection(model.encode_document(documents, training=False), training=False)
         if self._check_kind(rep):
@@ -517,11 +635,22 @@ class CorpusIndex:
             return TokenReps(self._l2norm(v) if self.normalize else v, q.mask.contiguous())
         return (q if self.post_process_logits is None else self.post_process_logits(q)).contiguous()
 
-    def search(self, queries, k):
+    def search(self, queries, k, nprobe=None):
         """(scores f32 [Q, k], ids int32 [Q, k]) on the device: per query the k best documents, score descending, ties
-        to the lower id; when the corpus holds fewer than k, the tail is (-inf, -1)."""
+        to the lower id; when the corpus holds fewer than k, the tail is (-inf, -1).
+
+        `nprobe` (an IVF-PQ index only; None: the index's own `nprobe`): 1 <= nprobe <= min(K, 1024) scores only the
+        documents in the lists of each query's nprobe best centroids by dot product (ties to the lower centroid), with the
+        bits the exhaustive scan gives them; with fewer than k such documents the tail is (-inf, -1).  Both unset: every
+        document is scored."""
+        if nprobe is not None and self.storage != "ivfpq":
+            raise ValueError(f"nprobe belongs to storage='ivfpq' (got storage={self.storage!r}); a token index takes it "
+                             "in search_pruned(..., nprobe)")
         if self._n == 0:
             raise ValueError("the index is empty: add documents before searching")
+        nprobe = self.nprobe if nprobe is None else nprobe
+        if nprobe is not None:
+            return self._search_probed(queries, k, self._check_nprobe(nprobe))
         q = self.encode_queries(queries)
         qv = q.values if self.tokens else q
         return topk_scan(qv.shape[0], k, self.chunks(qv.shape[0], decode=True), qv.device, self._kind.scorer(q))
@@ -568,9 +697,10 @@ class CorpusIndex:
             raise ValueError("centroids need a scorer that normalises (MaxSimScores(normalize=True)): the nearest "
                              "centroid by dot product means something on unit vectors only")
 
-    def _assign_rows(self, load, T, mask, codes, centroids):
+    def _assign_rows(self, load, T, mask, codes, centroids, bias=None):
         """codes[t] (int16 [T]) = the nearest row of `centroids` to token t, 0xFFFF where mask[t] == 0 (mask int32 [T]
-        or None); load(a, b, dst) writes tokens a .. b into dst [b - a, E].  Every GEMM of a call runs at the same
+        or None); load(a, b, dst) writes tokens a .. b into dst [b - a, E].  Nearest by dot product, or, with `bias`
+        (f32 [K] = -|c|^2 / 2, added by the GEMM's epilogue), by L2 distance: the IVF-PQ assignment of whole vectors.  Every GEMM of a call runs at the same
         shape [rows, E] x [K, E]^T, rows = the largest power of two with rows * K * 4 <= scratch_bytes, at most
         ASSIGN_ROWS, the last chunk's tail being zero rows: ops.gemm picks its kernel from the shape, and kernels may
         sum in different orders, so a token's similarities, and with them its code at a near tie, depend on nothing
@@ -587,7 +717,7 @@ class CorpusIndex:
         for a in range(0, T, rows):
             b = min(a + rows, T)
             load(a, b, x[:b - a])
-            ops.gemm(x, centroids, sim)
+            ops.gemm(x, centroids, sim, bias=bias)
             ops.centroid_codes(sim, None if mask is None else mask[a:b], codes[a:b], rows=b - a)
 
     def _assign(self, a, b):
@@ -695,10 +825,20 @@ class CorpusIndex:
         its nearest codeword (ops.pq_encode) and replaces a codeword by the mean of its sub-vectors (ops.pq_update; one
         without any stays).  All sums run in a fixed order: the same index and seed give the same bits, so data-parallel
         ranks holding the same corpus agree without communication."""
+        m, ksub = self._check_pq_fit("fit_pq", m, ksub)
+        rows = self._sample_rows(sample, seed)
+        if len(rows) < ksub:
+            raise ValueError(f"{ksub} codewords need at least as many sampled documents (got {len(rows)})")
+        x = self._reps[:self._n][torch.as_tensor(rows.astype(np.int64)).to(self._reps.device)].contiguous()
+        return PQCodec(self._pq_lloyd(x, m, ksub, iters))
+
+    def _check_pq_fit(self, what, m, ksub):
+        """(m, ksub) as ints once the index can train a product quantiser of that format: the refusals fit_pq and fit_ivfpq
+        share."""
         if self._n == 0:
             raise ValueError("the index is empty: add documents before fitting a codec")
         if self.tokens or self.storage is not None:
-            raise ValueError("fit_pq trains on a plain [CLS] index (storage=None): product quantisation is for one vector "
+            raise ValueError(f"{what} trains on a plain [CLS] index (storage=None): product quantisation is for one vector "
                              "per document, and a compressed index no longer holds the vectors to learn from")
         m, ksub, E = int(m), int(ksub), self._reps.shape[1]
         if not 4 <= m <= PQ_MAX_M or m % 4 or not 1 <= ksub <= 256:
@@ -706,12 +846,14 @@ class CorpusIndex:
         if E % m or E // m > 32:
             raise ValueError(f"the index holds vectors of {E} features: m = {m} must divide that into sub-vectors of at "
                              "most 32")
-        rows = self._sample_rows(sample, seed)
-        if len(rows) < ksub:
-            raise ValueError(f"{ksub} codewords need at least as many sampled documents (got {len(rows)})")
-        dev = self._reps.device
-        x = self._reps[:self._n][torch.as_tensor(rows.astype(np.int64)).to(dev)].contiguous()
-        T, dsub = x.shape[0], E // m
+        return m, ksub
+
+    @staticmethod
+    def _pq_lloyd(x, m, ksub, iters):
+        """The codebook f32 [m, ksub, dsub] after `iters` Lloyd rounds over the rows of x [T >= ksub, m * dsub] (f32 or
+        bf16, contiguous): the first ksub rows, widened to f32, are the initial codewords of every sub-space; a round is
+        ops.pq_encode then ops.pq_update."""
+        T, dsub, dev = x.shape[0], x.shape[1] // m, x.device
         cb = x[:ksub].float().view(ksub, m, dsub).permute(1, 0, 2).contiguous()
         nxt = torch.empty_like(cb)
         codes = torch.empty((T, m), dtype=torch.uint8, device=dev)
@@ -720,7 +862,45 @@ class CorpusIndex:
             ops.pq_encode(x, cb, codes)
             ops.pq_update(x, codes, cb, nxt, counts)
             cb, nxt = nxt, cb
-        return PQCodec(cb)
+        return cb
+
+    def fit_ivfpq(self, K, m, ksub=256, iters=8, pq_iters=8, sample=1 << 16, seed=0):
+        """An IVFPQCodec of K coarse centroids and m residual sub-spaces with ksub codewords each from a sample of this
+        index's stored vectors (a plain [CLS] index, as for fit_pq).
+
+        The sample is fit_pq's (seed and N only), gathered by a torch index copy; fewer than max(K, ksub) rows raise
+        ValueError.  The first K rows are the initial centroids, in the index's dtype.  Each of `iters` rounds gives every
+        sampled vector its L2-nearest centroid exactly as `add` does (ops.gemm with the bias -|c|^2 / 2, computed on the
+        host in float64, then ops.centroid_codes: ties to the lower id) and replaces a centroid by the mean of its vectors
+        (ops.ivfpq_coarse_update; one without any stays).  After a final assignment the f32 residuals
+        (ops.ivfpq_residual) go through `pq_iters` rounds of fit_pq's Lloyd loop, the first ksub residuals being the
+        initial codewords.  All sums run in a fixed order: the same index and seed give the same bits."""
+        m, ksub = self._check_pq_fit("fit_ivfpq", m, ksub)
+        K = int(K)
+        if not 1 <= K <= MAX_CENTROIDS:
+            raise ValueError(f"need 1 <= K <= {MAX_CENTROIDS} centroids (got {K})")
+        rows = self._sample_rows(sample, seed)
+        if len(rows) < max(K, ksub):
+            raise ValueError(f"{K} centroids and {ksub} codewords need at least max(K, ksub) = {max(K, ksub)} sampled "
+                             f"documents (got {len(rows)})")
+        dev = self._reps.device
+        x = self._reps[:self._n][torch.as_tensor(rows.astype(np.int64)).to(dev)].contiguous()
+        T, E = x.shape
+        cent, nxt = x[:K].clone(), torch.empty((K, E), dtype=x.dtype, device=dev)
+        coarse = torch.empty((T,), dtype=torch.int16, device=dev)
+        counts = torch.empty((K,), dtype=torch.int32, device=dev)
+
+        def assign():
+            self._assign_rows(lambda a, b, dst: dst.copy_(x[a:b]), T, None, coarse, cent, bias=_half_norms(cent).to(dev))
+
+        for _ in range(int(iters)):
+            assign()
+            ops.ivfpq_coarse_update(x, coarse, cent, nxt, counts)
+            cent, nxt = nxt, cent
+        assign()
+        res = torch.empty((T, E), dtype=torch.float32, device=dev)
+        ops.ivfpq_residual(x, cent, coarse, res)
+        return IVFPQCodec(cent, self._pq_lloyd(res, m, ksub, pq_iters))
 
     def search_pruned(self, queries, k, candidates, nprobe=None):
         """`search` over the `candidates` documents per query that score best under the centroid approximation:
@@ -738,6 +918,7 @@ class CorpusIndex:
         considered: on a corpus whose documents all have a present token the result is the scan's, bit for bit."""
         if self._n == 0:
             raise ValueError("the index is empty: add documents before searching")
+        self._check_token_lists("search_pruned")
         if self._centroids is None:
             raise ValueError("search_pruned needs centroids: call fit_centroids or set_centroids first")
         if not 1 <= int(candidates) <= MAX_K:
@@ -762,18 +943,24 @@ class CorpusIndex:
         return self._rerank_encoded(q, cand_id, k)
 
     # ------------------------------------------------------------ inverted lists and probed candidates
+    def _check_token_lists(self, what):
+        if self.storage == "ivfpq":
+            raise ValueError(f"{what} prunes a token (MaxSim) index; this index holds [CLS] representations in lists of "
+                             "their own: search(queries, k, nprobe) probes them")
+
     def refresh_lists(self):
         """Build the inverted lists from the codes of all stored documents (ops.ivf_count / ivf_offsets / ivf_fill):
         offsets int32 [K + 1] and docs int32 [P], docs[offsets[c] : offsets[c + 1]] the documents holding a present
         token of centroid c, each once, in no specified order.  One int (P) is copied to the host to size `docs`.
         `add`, `set_centroids` and `fit_centroids` only mark the lists stale; a search with `nprobe`, `probe` and
-        `lists` call this when they are."""
+        `lists` call this when they are.  An IVF-PQ index: the same CSR over its coarse codes as [N, 1], every document in
+        exactly one list, P = N."""
         if self._n == 0:
             raise ValueError("the index is empty: add documents before building the lists")
         if self._centroids is None:
             raise ValueError("refresh_lists needs centroids: call fit_centroids or set_centroids first")
-        K, dev = self._centroids.shape[0], self._codes.device
-        codes = self._codes[:self._n]
+        codes = self._kind.list_codes()
+        K, dev = self._centroids.shape[0], codes.device
         counts = torch.empty((K,), dtype=torch.int32, device=dev)
         offsets = torch.empty((K + 1,), dtype=torch.int32, device=dev)
         ops.ivf_count(codes, K, counts)
@@ -799,11 +986,12 @@ class CorpusIndex:
         self._fresh_lists()
         return self._lists
 
-    def _check_nprobe(self, nprobe):
-        most = min(self._centroids.shape[0], MAX_K)
+    def _check_nprobe(self, nprobe, K=None):
+        most = min(self._centroids.shape[0] if K is None else K, MAX_K)
         if not 1 <= int(nprobe) <= most:
             raise ValueError(f"need 1 <= nprobe <= min(K, {MAX_K}) = {most}, the centroids there are and the limit of "
                              f"ops.topk_merge, which keeps the probes (got {nprobe})")
+        return int(nprobe)
 
     def _mark_probed(self, q, nprobe):
         """(probes int32 [Q * Lq, nprobe], bitmap int32 [Q, ceil(N / 32)], count int32 [Q]) on the device for
@@ -826,12 +1014,18 @@ class CorpusIndex:
             b = min(a + per * Lq, Q * Lq)
             ops.gemm(flat[a:b], self._centroids, sim[:b - a])
             ops.topk_merge(sim[:b - a], val[:b - a], probes[a:b], init=True)
+        return (probes,) + self._mark(probes, q.mask, Q, Lq)
+
+    def _mark(self, probes, qmask, Q, Lq):
+        """(bitmap int32 [Q, ceil(N / 32)], count int32 [Q]) on the device: the union of the lists of probes int32
+        [Q * Lq, nprobe] as one bitmap row per query (ops.ivf_mark; qmask int32 [Q, Lq] or None) and its number of set bits
+        (ops.ivf_compact)."""
         offsets, docs = self._lists
-        bitmap = torch.empty((Q, (self._n + 31) // 32), dtype=torch.int32, device=dev)
-        count = torch.empty((Q,), dtype=torch.int32, device=dev)
-        ops.ivf_mark(probes, q.mask, offsets, docs, self._n, bitmap, Q, Lq)
+        bitmap = torch.empty((Q, (self._n + 31) // 32), dtype=torch.int32, device=probes.device)
+        count = torch.empty((Q,), dtype=torch.int32, device=probes.device)
+        ops.ivf_mark(probes, qmask, offsets, docs, self._n, bitmap, Q, Lq)
         ops.ivf_compact(bitmap, self._n, count)
-        return probes, bitmap, count
+        return bitmap, count
 
     def probe(self, queries, nprobe):
         """The candidate generation of `search_pruned(..., nprobe)` on its own: (probes int32 [Q, Lq, nprobe], cand
@@ -841,6 +1035,7 @@ class CorpusIndex:
         M = max(1, max count).  `cand` can go to `rerank`, or to another index holding the same documents."""
         if self._n == 0:
             raise ValueError("the index is empty: add documents before probing")
+        self._check_token_lists("probe")
         if self._centroids is None:
             raise ValueError("probe needs centroids: call fit_centroids or set_centroids first")
         self._check_nprobe(nprobe)
@@ -854,16 +1049,25 @@ class CorpusIndex:
 
     def _score_probed(self, q, table, nprobe, cand_val, cand_id):
         """The candidate stage of search_pruned under `nprobe`: the look-up scores of each query's probed documents
-        only (ops.centroid_scores_ids: the bits the scan gives those pairs) merged into cand_val / cand_id.  The
-        queries' candidate counts come to the host in one copy; the queries are taken in consecutive groups whose
-        [group, largest count] int32 candidate buffer stays within scratch_bytes."""
-        Q, Lq = q.values.shape[:2]
+        only (ops.centroid_scores_ids: the bits the scan gives those pairs) merged into cand_val / cand_id
+        (_scan_probed)."""
+        Lq = q.values.shape[1]
         _, bitmap, count = self._mark_probed(q, nprobe)
+        codes = self._codes[:self._n]
+        self._scan_probed(bitmap, count, (cand_val, cand_id), lambda a, b, cand: lambda s, e, sc: ops.centroid_scores_ids(
+            table[:, a * Lq:], q.mask[a:b], codes, cand[:, s:e], sc, b - a, Lq))
+
+    def _scan_probed(self, bitmap, count, top, scorer):
+        """The exact top-k (top = (top_val f32 [Q, k], top_id int32 [Q, k]), overwritten) over each query's own candidates,
+        the set bits of its row of `bitmap` (count int32 [Q] their numbers).  The counts come to the host in one copy; the
+        queries are taken in consecutive groups a .. b whose [group, largest count] int32 candidate buffer stays within
+        scratch_bytes; a group's candidates are written in ascending order (ops.ivf_compact) and scorer(a, b, cand) gives
+        the score(s, e, out) of store.topk_scan over its candidate columns."""
+        Q = count.shape[0]
         counts = np.maximum(count.cpu().numpy(), 1)           # a query without a candidate: one column of -1
         if 4 * int(counts.max()) > self.scratch_bytes:
             raise ValueError(f"scratch_bytes = {self.scratch_bytes} does not hold the {int(counts.max())} candidates "
                              f"of one query ({4 * int(counts.max())} bytes)")
-        codes = self._codes[:self._n]
         a = 0
         while a < Q:
             b, C = a + 1, int(counts[a])
@@ -871,10 +1075,29 @@ class CorpusIndex:
                 C, b = max(C, int(counts[b])), b + 1
             cand = torch.empty((b - a, C), dtype=torch.int32, device=count.device)
             ops.ivf_compact(bitmap[a:b], self._n, count[a:b], cand)
-            topk_scan(b - a, None, self.rerank_chunks(b - a, C), count.device,
-                      lambda s, e, sc: ops.centroid_scores_ids(table[:, a * Lq:], q.mask[a:b], codes, cand[:, s:e], sc, b - a, Lq),
-                      ids=cand, top=(cand_val[a:b], cand_id[a:b]))
+            topk_scan(b - a, None, self.rerank_chunks(b - a, C), count.device, scorer(a, b, cand), ids=cand,
+                      top=(top[0][a:b], top[1][a:b]))
             a = b
+
+    def _search_probed(self, queries, k, nprobe):
+        """`search` of an IVF-PQ index under `nprobe`: one GEMM gives every query's dot products with the centroids, which
+        are both the probe ranking (ops.topk_merge: descending, ties to the lower centroid) and the centroid term of the
+        scores; the probed lists become a bitmap and ascending candidate ids (_mark, _scan_probed), scored by
+        ops.ivfpq_scores_ids."""
+        if not 1 <= int(k) <= MAX_K:
+            raise ValueError(f"need 1 <= k <= {MAX_K}, the limit of ops.topk_merge (got {k})")
+        self._fresh_lists()
+        q = self.encode_queries(queries)
+        Q, dev = q.shape[0], q.device
+        lut, cdot = self._kind.tables(q)
+        probes = torch.empty((Q, nprobe), dtype=torch.int32, device=dev)
+        ops.topk_merge(cdot, torch.empty((Q, nprobe), dtype=torch.float32, device=dev), probes, init=True)
+        bitmap, count = self._mark(probes, None, Q, 1)
+        coarse, codes = self._store.view("coarse"), self._store.view("reps")
+        top = (torch.empty((Q, int(k)), dtype=torch.float32, device=dev), torch.empty((Q, int(k)), dtype=torch.int32, device=dev))
+        self._scan_probed(bitmap, count, top, lambda a, b, cand: lambda s, e, sc: ops.ivfpq_scores_ids(
+            lut[a:b], cdot[a:b], coarse, codes, cand[:, s:e], sc))
+        return top
 
 
 class SparseCorpusIndex:

@@ -12,7 +12,8 @@ from . import _lib
 from ._lib import (F32, BF16, K_CONTIG, K_STRIDED, ACT_NONE, ACT_GELU, ACT_SWISH, ACT_RELU, ACT_TANH,
                    GEMM_ACCUM_C, GEMM_ACT_FWD, GEMM_ACT_BWD, check, ptr, dtype_code)
 # the product-quantisation wrappers (csrc/pq.hip) live in a module of their own and are part of this namespace
-from .pq_ops import PqRoute, pq_decode, pq_encode, pq_lut, pq_scores, pq_scores_route, pq_update
+from .pq_ops import (IvfPqRoute, PqRoute, ivfpq_coarse_update, ivfpq_residual, ivfpq_scores_ids, ivfpq_scores_ids_route,
+                     pq_decode, pq_encode, pq_lut, pq_scores, pq_scores_route, pq_update)
 
 # bench.py instrumentation: when a list, every gemm launch appends (kind, flops, ev0, ev1)
 GEMM_PROFILE = None

@@ -131,3 +131,95 @@ def pq_scores_route(Q, N, m, ksub):
     r = (ctypes.c_int * 2)()
     check(_lib.load().polus_pq_scores_route(int(Q), int(N), int(m), int(ksub), r), "polus_pq_scores_route")
     return PqRoute(r[0], r[1])
+
+
+# ---------------------------------------------------------------- IVF-PQ (csrc/ivfpq.hip, include/polus_hip.h "IVF-PQ")
+IVFPQ_K_MAX, IVFPQ_E_MAX = 65535, 5120
+IvfPqRoute = collections.namedtuple("IvfPqRoute", "lds_bytes cols_per_block")
+_I16 = (torch.int16,)
+
+
+def _coarse(op, name, t, n):
+    """Coarse codes: contiguous int16 [n] holding the unsigned bits (0xFFFF, or any code >= K: no list)."""
+    assert t.dtype == torch.int16 and t.dim() == 1 and t.shape[0] == n and t.is_contiguous(), \
+        f"{op}: {name} must be contiguous int16 [{n}] (the bits of the unsigned code) {_got(t)}"
+
+
+def _centroids(op, name, c, dtype):
+    """(K, E) of contiguous centroids [K, E] of `dtype` within the format's limits."""
+    assert c.dtype == dtype and c.dim() == 2 and c.is_contiguous() and 1 <= c.shape[0] <= IVFPQ_K_MAX \
+        and 1 <= c.shape[1] <= IVFPQ_E_MAX, \
+        f"{op}: {name} must be contiguous {dtype} [K, E] with 1 <= K <= {IVFPQ_K_MAX} and 1 <= E <= {IVFPQ_E_MAX} {_got(c)}"
+    return c.shape
+
+
+def ivfpq_residual(x, cent, coarse, r):
+    """r[t, e] (f32 [rows, E], any row stride) = f32(x[t, e]) - f32(cent[coarse[t], e]), one rounding; zeros for a row whose
+    coarse code is >= K.  x f32 or bf16 [rows, E] (any row stride), cent [K, E] contiguous in x's dtype, coarse int16 [rows]
+    (include/polus_hip.h polus_ivfpq_residual)."""
+    _req_cuda(x, cent, coarse, r)
+    assert x.dtype in _VEC, f"ivfpq_residual: x must be f32 or bf16 {_got(x)}"
+    K, E = _centroids("ivfpq_residual", "cent", cent, x.dtype)
+    rows, ldx = _rows("ivfpq_residual", "x", x, _VEC, None, E)
+    _coarse("ivfpq_residual", "coarse", coarse, rows)
+    _, ldr = _rows("ivfpq_residual", "r", r, (torch.float32,), rows, E)
+    check(_lib.load().polus_ivfpq_residual(_lib.dtype_code(x.dtype), ptr(x), ldx, ptr(cent), ptr(coarse), ptr(r), ldr, rows, K, E,
+                                           _lib.current_stream()), "polus_ivfpq_residual")
+
+
+def ivfpq_coarse_update(x, coarse, prev, out, counts):
+    """One Lloyd update of whole vectors: out[k] = the f32 sum of the rows x[t] with coarse[t] == k divided by their number
+    counts[k] (int32 [K]), rounded once to x's dtype; prev[k] where there is none.  The sum's order is a function of T
+    alone.  x f32 or bf16 [T, E] (any row stride), coarse int16 [T], prev / out [K, E] contiguous in x's dtype, buffers
+    that do not overlap (include/polus_hip.h polus_ivfpq_coarse_update)."""
+    _req_cuda(x, coarse, prev, out, counts)
+    assert x.dtype in _VEC, f"ivfpq_coarse_update: x must be f32 or bf16 {_got(x)}"
+    K, E = _centroids("ivfpq_coarse_update", "prev", prev, x.dtype)
+    assert out.dtype == x.dtype and tuple(out.shape) == (K, E) and out.is_contiguous(), \
+        f"ivfpq_coarse_update: out must be contiguous {x.dtype} {[K, E]} like prev {_got(out)}"
+    T, ldx = _rows("ivfpq_coarse_update", "x", x, _VEC, None, E)
+    _coarse("ivfpq_coarse_update", "coarse", coarse, T)
+    assert counts.dtype == torch.int32 and tuple(counts.shape) == (K,) and counts.is_contiguous(), \
+        f"ivfpq_coarse_update: counts must be contiguous int32 {[K]} {_got(counts)}"
+    nbytes = prev.numel() * prev.element_size()
+    assert out.data_ptr() + nbytes <= prev.data_ptr() or prev.data_ptr() + nbytes <= out.data_ptr(), \
+        "ivfpq_coarse_update: out must not overlap prev"
+    check(_lib.load().polus_ivfpq_coarse_update(_lib.dtype_code(x.dtype), ptr(x), ldx, ptr(coarse), ptr(prev), ptr(out), ptr(counts),
+                                                T, K, E, _lib.current_stream()), "polus_ivfpq_coarse_update")
+
+
+def ivfpq_scores_ids(lut, cdot, coarse, codes, cand, score):
+    """score[b, c] (f32 [Q, C], any row stride) = cdot[b, coarse[n]] + sum over j of lut[b, j, codes[n, j]] for n = cand[b, c]
+    (int32 [Q, C], any row stride), the sum sequential in ascending j and one more rounding for the centroid's term; an id
+    outside [0, N), a coarse code >= K or a code byte >= ksub gives -inf.  cand=None: column c is document c and C = N.  lut
+    f32 [Q, m, ksub] contiguous (pq_lut with the residual codebook), cdot f32 [Q, K] (any row stride), coarse int16 [N], codes
+    uint8 [N, m] (any row stride); Q and C at most 65535 (include/polus_hip.h polus_ivfpq_scores_ids)."""
+    _req_cuda(lut, cdot, coarse, codes, score, *(() if cand is None else (cand,)))
+    assert lut.dtype == torch.float32 and lut.dim() == 3 and lut.is_contiguous(), \
+        f"ivfpq_scores_ids: lut must be contiguous f32 [Q, m, ksub] {_got(lut)}"
+    Q, m, ksub = lut.shape
+    N, ldc = _rows("ivfpq_scores_ids", "codes", codes, _U8, None, m)
+    assert cdot.dim() == 2 and 1 <= cdot.shape[1] <= IVFPQ_K_MAX, \
+        f"ivfpq_scores_ids: cdot must be f32 [{Q}, K] with 1 <= K <= {IVFPQ_K_MAX} {_got(cdot)}"
+    K = cdot.shape[1]
+    _, ldd = _rows("ivfpq_scores_ids", "cdot", cdot, (torch.float32,), Q, K)
+    _coarse("ivfpq_scores_ids", "coarse", coarse, N)
+    if cand is None:
+        C, ldcand = N, 0
+    else:
+        assert cand.dim() == 2 and cand.shape[1] >= 1, f"ivfpq_scores_ids: cand must be int32 [{Q}, C] with C >= 1 {_got(cand)}"
+        C = cand.shape[1]
+        _, ldcand = _rows("ivfpq_scores_ids", "cand", cand, (torch.int32,), Q, C)
+    _check_scan("ivfpq_scores_ids", Q, 1, m, ksub)              # the format and Q; the columns are checked here
+    assert C <= 65535, f"ivfpq_scores_ids: {'cand' if cand is not None else 'codes'} holds {C} columns, a launch takes 1 .. 65535"
+    _, lds = _rows("ivfpq_scores_ids", "score", score, (torch.float32,), Q, C)
+    check(_lib.load().polus_ivfpq_scores_ids(ptr(lut), ptr(cdot), ldd, ptr(coarse), ptr(codes), ldc, ptr(cand), ldcand, ptr(score),
+                                             lds, Q, C, N, m, ksub, K, _lib.current_stream()), "polus_ivfpq_scores_ids")
+
+
+def ivfpq_scores_ids_route(Q, C, m, ksub):
+    """What `ivfpq_scores_ids` runs for these shapes (polus_ivfpq_scores_ids_route): the dynamic LDS bytes of a workgroup and
+    the candidate columns it serves; launches nothing and refuses the shapes ivfpq_scores_ids refuses."""
+    r = (ctypes.c_int * 2)()
+    check(_lib.load().polus_ivfpq_scores_ids_route(int(Q), int(C), int(m), int(ksub), r), "polus_ivfpq_scores_ids_route")
+    return IvfPqRoute(r[0], r[1])
