@@ -123,10 +123,41 @@ def _vec(op, name, t, dtype, n, optional=False):
         f"{op}: {name} must be contiguous {dtype} with at least {n} elements {_got(t)}"
 
 
-def _mat(op, name, t, dtype, rows, cols):
-    """A pointer and a row stride: a 2-D tensor of `dtype` with at least rows x cols elements whose inner stride is one."""
+def _mat(op, name, t, dtype, rows, cols, exact=False):
+    """A pointer and a row stride: a 2-D tensor of `dtype` with at least (exact: exactly) rows x cols elements whose inner
+    stride is one."""
+    if exact:
+        assert t.dtype == dtype and tuple(t.shape) == (rows, cols) and (t.stride(1) == 1 or cols == 1), \
+            f"{op}: {name} must be {dtype} [{rows}, {cols}] with a unit inner stride {_got(t)}"
+        return
     assert t.dtype == dtype and t.dim() == 2 and t.shape[0] >= rows and t.shape[1] >= cols and (t.stride(1) == 1 or t.shape[1] == 1), \
         f"{op}: {name} must be {dtype} [>= {rows}, >= {cols}] with a unit inner stride {_got(t)}"
+
+
+def _ld(t, cols):
+    """The row stride of a checked matrix, legal for a single row too (whose stride torch leaves arbitrary)."""
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), cols)
+
+
+def _eng(op, name, t, dims):
+    """The dtype code of an f32 or bf16 tensor passed as a flat pointer: `dims`-D and contiguous."""
+    code = _dt(op, name, t)
+    assert t.dim() == dims and t.is_contiguous(), f"{op}: {name} must be a contiguous {dims}-D tensor {_got(t)}"
+    return code
+
+
+def _flat(op, name, t, dtype, shape):
+    """A flat pointer whose extent the call fixes: contiguous, of `dtype`, exactly `shape` (an int: that many elements)."""
+    ok = t.numel() == shape if isinstance(shape, int) else tuple(t.shape) == tuple(shape)
+    want = f"{shape} elements" if isinstance(shape, int) else f"{list(shape)}"
+    assert t.dtype == dtype and ok and t.is_contiguous(), f"{op}: {name} must be contiguous {dtype} with {want} {_got(t)}"
+
+
+def _disjoint(op, a_name, a, b_name, b):
+    """Two contiguous tensors the kernel treats as distinct buffers: their byte ranges must not meet."""
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    a1, b1 = a0 + a.numel() * a.element_size(), b0 + b.numel() * b.element_size()
+    assert a1 <= b0 or b1 <= a0, f"{op}: {a_name} must not overlap {b_name}"
 
 
 _AUTO_SPLIT = {}
@@ -605,37 +636,52 @@ def crf_viterbi(potentials, lengths, trans, out_tags):
           "polus_crf_viterbi")
 
 
-def _maxsim_mask(m, rows, L, name):
+def _maxsim_mask(op, name, m, rows, L):
     if m is None:
         return None
-    assert m.dtype == torch.int32 and m.is_contiguous() and m.numel() == rows * L, f"{name}: int32 [{rows}, {L}] expected"
+    assert m.dtype == torch.int32 and m.is_contiguous() and m.numel() == rows * L, \
+        f"{op}: {name} must be contiguous int32 [{rows}, {L}] {_got(m)}"
     return m
+
+
+def _maxsim_qd(op, q, d):
+    """The query and document token matrices of the MaxSim family: q [B, Lq, E], d [N, Ld, E], contiguous, one dtype."""
+    code = _eng(op, "q", q, 3)
+    B, Lq, E = q.shape
+    assert d.dtype == q.dtype and d.dim() == 3 and d.shape[2] == E and d.is_contiguous(), \
+        f"{op}: d must be contiguous [N, Ld, {E}] in q's dtype {q.dtype} {_got(d)}"
+    return code, B, Lq, E, d.shape[0], d.shape[1]
+
+
+def _cand(op, cand, B):
+    """A candidate list per query: int32 [B, C] with any row stride; returns C."""
+    assert cand.dtype == torch.int32 and cand.dim() == 2 and cand.shape[0] == B and (cand.stride(1) == 1 or cand.shape[1] == 1), \
+        f"{op}: cand must be int32 [{B}, C] with a unit inner stride {_got(cand)}"
+    return cand.shape[1]
 
 
 def maxsim_fwd(q, d, qmask, dmask, score, argmax):
     """score[b, c] (f32, any row stride >= N) = sum over valid i of max over valid j of <q[b, i], d[c, j]>, and
     argmax[b, c, i] (int32 [B, N, Lq]) the winning j; q [B, Lq, E], d [N, Ld, E] (include/polus_hip.h)."""
+    op = "maxsim_fwd"
     _req_cuda(q, d, qmask, dmask, score, argmax)
-    B, Lq, E = q.shape
-    N, Ld = d.shape[0], d.shape[1]
-    assert d.dim() == 3 and d.shape[2] == E and d.dtype == q.dtype and q.is_contiguous() and d.is_contiguous()
-    assert score.dtype == torch.float32 and score.dim() == 2 and score.shape[0] >= B and score.shape[1] >= N and score.stride(1) == 1
-    assert argmax.dtype == torch.int32 and argmax.is_contiguous() and argmax.numel() == B * N * Lq
-    check(_lib.load().polus_maxsim_fwd(dtype_code(q.dtype), ptr(q), ptr(d), ptr(_maxsim_mask(qmask, B, Lq, "qmask")),
-                                       ptr(_maxsim_mask(dmask, N, Ld, "dmask")), ptr(score), score.stride(0), ptr(argmax),
+    code, B, Lq, E, N, Ld = _maxsim_qd(op, q, d)
+    _mat(op, "score", score, _F32T, B, N)
+    _flat(op, "argmax", argmax, _I32T, B * N * Lq)
+    check(_lib.load().polus_maxsim_fwd(code, ptr(q), ptr(d), ptr(_maxsim_mask(op, "qmask", qmask, B, Lq)),
+                                       ptr(_maxsim_mask(op, "dmask", dmask, N, Ld)), ptr(score), _ld(score, N), ptr(argmax),
                                        B, N, Lq, Ld, E, _st()), "polus_maxsim_fwd")
 
 
 def maxsim_scores(q, d, qmask, dmask, score):
     """maxsim_fwd without the argmax (the same kernel body, bitwise the same scores): for scoring a corpus, where
     nothing runs backward.  No B*N*Lq limit."""
+    op = "maxsim_scores"
     _req_cuda(q, d, qmask, dmask, score)
-    B, Lq, E = q.shape
-    N, Ld = d.shape[0], d.shape[1]
-    assert d.dim() == 3 and d.shape[2] == E and d.dtype == q.dtype and q.is_contiguous() and d.is_contiguous()
-    assert score.dtype == torch.float32 and score.dim() == 2 and score.shape[0] >= B and score.shape[1] >= N and score.stride(1) == 1
-    check(_lib.load().polus_maxsim_scores(dtype_code(q.dtype), ptr(q), ptr(d), ptr(_maxsim_mask(qmask, B, Lq, "qmask")),
-                                          ptr(_maxsim_mask(dmask, N, Ld, "dmask")), ptr(score), score.stride(0),
+    code, B, Lq, E, N, Ld = _maxsim_qd(op, q, d)
+    _mat(op, "score", score, _F32T, B, N)
+    check(_lib.load().polus_maxsim_scores(code, ptr(q), ptr(d), ptr(_maxsim_mask(op, "qmask", qmask, B, Lq)),
+                                          ptr(_maxsim_mask(op, "dmask", dmask, N, Ld)), ptr(score), _ld(score, N),
                                           B, N, Lq, Ld, E, _st()), "polus_maxsim_scores")
 
 
@@ -643,95 +689,110 @@ def maxsim_rerank(q, d, qmask, dmask, cand, score):
     """score[b, c] (f32 [B, C], any row stride) = the MaxSim score of query b and document cand[b, c] (int32 [B, C],
     any row stride) of the corpus d [N, Ld, E], bit for bit what maxsim_scores gives that pair; -inf where cand[b, c]
     is outside [0, N) (include/polus_hip.h polus_maxsim_rerank)."""
+    op = "maxsim_rerank"
     _req_cuda(q, d, qmask, dmask, cand, score)
-    B, Lq, E = q.shape
-    assert d.dim() == 3 and d.shape[2] == E and d.dtype == q.dtype and q.is_contiguous() and d.is_contiguous()
-    N, Ld = d.shape[0], d.shape[1]
-    assert cand.dtype == torch.int32 and cand.dim() == 2 and cand.shape[0] == B and (cand.stride(1) == 1 or cand.shape[1] == 1)
-    C = cand.shape[1]
-    assert score.dtype == torch.float32 and tuple(score.shape) == (B, C) and (score.stride(1) == 1 or C == 1)
-    check(_lib.load().polus_maxsim_rerank(dtype_code(q.dtype), ptr(q), ptr(d), ptr(_maxsim_mask(qmask, B, Lq, "qmask")),
-                                          ptr(_maxsim_mask(dmask, N, Ld, "dmask")), ptr(cand), cand.stride(0), ptr(score),
+    code, B, Lq, E, N, Ld = _maxsim_qd(op, q, d)
+    C = _cand(op, cand, B)
+    _mat(op, "score", score, _F32T, B, C, exact=True)
+    check(_lib.load().polus_maxsim_rerank(code, ptr(q), ptr(d), ptr(_maxsim_mask(op, "qmask", qmask, B, Lq)),
+                                          ptr(_maxsim_mask(op, "dmask", dmask, N, Ld)), ptr(cand), cand.stride(0), ptr(score),
                                           score.stride(0), B, C, N, Lq, Ld, E, _st()), "polus_maxsim_rerank")
+
+
+def _fp8_rows(op, name, t, codes, scale):
+    """The three tensors of the row quantiser: t [..., E] f32 or bf16, codes uint8 of t's shape, one f32 scale per row."""
+    code = _dt(op, name, t)
+    assert t.dim() >= 1 and t.is_contiguous(), f"{op}: {name} must be contiguous [..., E] {_got(t)}"
+    E = t.shape[-1]
+    rows = t.numel() // E
+    _flat(op, "codes", codes, torch.uint8, tuple(t.shape))
+    _flat(op, "scale", scale, _F32T, rows)
+    return code, rows, E
 
 
 def fp8_quantize(x, codes, scale):
     """x [..., E] (f32 or bf16) -> codes uint8 [..., E] (OCP e4m3fn) and scale f32 [...], one power of two per row:
     the integer rule of include/polus_hip.h polus_fp8_quantize_rows; x ~ e4m3fn(codes) * scale."""
     _req_cuda(x, codes, scale)
-    E = x.shape[-1]
-    rows = x.numel() // E
-    assert x.is_contiguous() and codes.is_contiguous() and codes.dtype == torch.uint8 and codes.shape == x.shape
-    assert scale.dtype == torch.float32 and scale.numel() == rows and scale.is_contiguous()
-    check(_lib.load().polus_fp8_quantize_rows(dtype_code(x.dtype), ptr(x), ptr(codes), ptr(scale), rows, E, _st()),
+    code, rows, E = _fp8_rows("fp8_quantize", "x", x, codes, scale)
+    check(_lib.load().polus_fp8_quantize_rows(code, ptr(x), ptr(codes), ptr(scale), rows, E, _st()),
           "polus_fp8_quantize_rows")
 
 
 def fp8_dequantize(codes, scale, y):
     """y [..., E] (f32 or bf16) = e4m3fn(codes) * scale, exact (codes uint8 [..., E], scale f32 [...])."""
     _req_cuda(codes, scale, y)
-    E = y.shape[-1]
-    rows = y.numel() // E
-    assert y.is_contiguous() and codes.is_contiguous() and codes.dtype == torch.uint8 and codes.shape == y.shape
-    assert scale.dtype == torch.float32 and scale.numel() == rows and scale.is_contiguous()
-    check(_lib.load().polus_fp8_dequantize_rows(dtype_code(y.dtype), ptr(codes), ptr(scale), ptr(y), rows, E, _st()),
+    code, rows, E = _fp8_rows("fp8_dequantize", "y", y, codes, scale)
+    check(_lib.load().polus_fp8_dequantize_rows(code, ptr(codes), ptr(scale), ptr(y), rows, E, _st()),
           "polus_fp8_dequantize_rows")
 
 
-def _fp8_corpus(q, codes, scale):
+def _fp8_corpus(op, q, codes, scale):
+    code = _eng(op, "q", q, 3)
     B, Lq, E = q.shape
-    assert codes.dim() == 3 and codes.shape[2] == E and codes.dtype == torch.uint8 and q.is_contiguous() and codes.is_contiguous()
+    assert codes.dtype == torch.uint8 and codes.dim() == 3 and codes.shape[2] == E and codes.is_contiguous(), \
+        f"{op}: codes must be contiguous uint8 [N, Ld, {E}] {_got(codes)}"
     N, Ld = codes.shape[0], codes.shape[1]
-    assert scale.dtype == torch.float32 and tuple(scale.shape) == (N, Ld) and scale.is_contiguous()
-    return B, Lq, E, N, Ld
+    _flat(op, "scale", scale, _F32T, (N, Ld))
+    return code, B, Lq, E, N, Ld
 
 
 def maxsim_scores_fp8(q, codes, scale, qmask, dmask, score):
     """maxsim_scores over an FP8 corpus (codes uint8 [N, Ld, E], scale f32 [N, Ld]; q stays f32 or bf16): bit for bit
     maxsim_scores(q, dequantised corpus) (include/polus_hip.h polus_maxsim_scores_fp8)."""
+    op = "maxsim_scores_fp8"
     _req_cuda(q, codes, scale, qmask, dmask, score)
-    B, Lq, E, N, Ld = _fp8_corpus(q, codes, scale)
-    assert score.dtype == torch.float32 and score.dim() == 2 and score.shape[0] >= B and score.shape[1] >= N and score.stride(1) == 1
-    check(_lib.load().polus_maxsim_scores_fp8(dtype_code(q.dtype), ptr(q), ptr(codes), ptr(scale),
-                                              ptr(_maxsim_mask(qmask, B, Lq, "qmask")), ptr(_maxsim_mask(dmask, N, Ld, "dmask")),
-                                              ptr(score), score.stride(0), B, N, Lq, Ld, E, _st()), "polus_maxsim_scores_fp8")
+    code, B, Lq, E, N, Ld = _fp8_corpus(op, q, codes, scale)
+    _mat(op, "score", score, _F32T, B, N)
+    check(_lib.load().polus_maxsim_scores_fp8(code, ptr(q), ptr(codes), ptr(scale),
+                                              ptr(_maxsim_mask(op, "qmask", qmask, B, Lq)), ptr(_maxsim_mask(op, "dmask", dmask, N, Ld)),
+                                              ptr(score), _ld(score, N), B, N, Lq, Ld, E, _st()), "polus_maxsim_scores_fp8")
 
 
 def maxsim_rerank_fp8(q, codes, scale, qmask, dmask, cand, score):
     """maxsim_rerank over an FP8 corpus: score[b, c] is bit for bit what maxsim_scores_fp8 gives query b and document
     cand[b, c]; -inf where cand[b, c] is outside [0, N) (include/polus_hip.h polus_maxsim_rerank_fp8)."""
+    op = "maxsim_rerank_fp8"
     _req_cuda(q, codes, scale, qmask, dmask, cand, score)
-    B, Lq, E, N, Ld = _fp8_corpus(q, codes, scale)
-    assert cand.dtype == torch.int32 and cand.dim() == 2 and cand.shape[0] == B and (cand.stride(1) == 1 or cand.shape[1] == 1)
-    C = cand.shape[1]
-    assert score.dtype == torch.float32 and tuple(score.shape) == (B, C) and (score.stride(1) == 1 or C == 1)
-    check(_lib.load().polus_maxsim_rerank_fp8(dtype_code(q.dtype), ptr(q), ptr(codes), ptr(scale),
-                                              ptr(_maxsim_mask(qmask, B, Lq, "qmask")), ptr(_maxsim_mask(dmask, N, Ld, "dmask")),
+    code, B, Lq, E, N, Ld = _fp8_corpus(op, q, codes, scale)
+    C = _cand(op, cand, B)
+    _mat(op, "score", score, _F32T, B, C, exact=True)
+    check(_lib.load().polus_maxsim_rerank_fp8(code, ptr(q), ptr(codes), ptr(scale),
+                                              ptr(_maxsim_mask(op, "qmask", qmask, B, Lq)), ptr(_maxsim_mask(op, "dmask", dmask, N, Ld)),
                                               ptr(cand), cand.stride(0), ptr(score), score.stride(0), B, C, N, Lq, Ld, E, _st()),
           "polus_maxsim_rerank_fp8")
 
 
-def _residual_codec(centroids, table, nbits, E, name):
+def _residual_codec(op, centroids, dtype, table, nbits, E, name):
     """Checks of a residual codec's device tensors; `table` is the cutoffs (2^nbits - 1) or the weights (2^nbits)."""
-    assert nbits in (1, 2, 4), f"nbits must be 1, 2 or 4 (got {nbits})"
-    assert centroids.dim() == 2 and centroids.shape[1] == E and centroids.is_contiguous() and 1 <= centroids.shape[0] <= 65535
-    n = (1 << nbits) - (1 if name == "cutoffs" else 0)
-    assert table.dtype == torch.float32 and table.is_contiguous() and table.numel() == n, f"{name}: f32 [{n}] expected"
+    assert nbits in (1, 2, 4), f"{op}: nbits must be 1, 2 or 4 (got {nbits})"
+    assert centroids.dtype == dtype and centroids.dim() == 2 and centroids.shape[1] == E and centroids.is_contiguous() \
+        and 1 <= centroids.shape[0] <= 65535, f"{op}: centroids must be contiguous {dtype} [1 <= K <= 65535, {E}] {_got(centroids)}"
+    _flat(op, name, table, _F32T, (1 << nbits) - (1 if name == "cutoffs" else 0))
     return centroids.shape[0]
+
+
+def _residual_rows(op, name, t, codes, packed, nbits):
+    """t [..., E] f32 or bf16 with one int16 code and E * nbits / 8 packed bytes per row."""
+    code = _dt(op, name, t)
+    assert t.dim() >= 1 and t.is_contiguous(), f"{op}: {name} must be contiguous [..., E] {_got(t)}"
+    E = t.shape[-1]
+    rows = t.numel() // E
+    _flat(op, "codes", codes, torch.int16, rows)
+    _flat(op, "packed", packed, torch.uint8, rows * E * nbits // 8)
+    return code, rows, E
 
 
 def residual_compress(x, codes, centroids, cutoffs, nbits, packed):
     """x [..., E] (f32 or bf16) and its centroid codes int16 [...] (the bits of the unsigned code; >= K: no token) ->
     packed uint8 [..., E * nbits / 8], the bucket of every residual element x - centroids[code] among the cutoffs
     f32 [2^nbits - 1] (include/polus_hip.h polus_residual_compress); centroids [K, E] in x's dtype."""
+    op = "residual_compress"
     _req_cuda(x, codes, centroids, cutoffs, packed)
-    E = x.shape[-1]
-    rows = x.numel() // E
-    K = _residual_codec(centroids, cutoffs, nbits, E, "cutoffs")
-    assert x.is_contiguous() and centroids.dtype == x.dtype
-    assert codes.dtype == torch.int16 and codes.is_contiguous() and codes.numel() == rows
-    assert packed.dtype == torch.uint8 and packed.is_contiguous() and packed.numel() == rows * E * nbits // 8
-    check(_lib.load().polus_residual_compress(dtype_code(x.dtype), ptr(x), ptr(codes), ptr(centroids), K, ptr(cutoffs),
+    assert nbits in (1, 2, 4), f"{op}: nbits must be 1, 2 or 4 (got {nbits})"
+    code, rows, E = _residual_rows(op, "x", x, codes, packed, nbits)
+    K = _residual_codec(op, centroids, x.dtype, cutoffs, nbits, E, "cutoffs")
+    check(_lib.load().polus_residual_compress(code, ptr(x), ptr(codes), ptr(centroids), K, ptr(cutoffs),
                                               int(nbits), ptr(packed), rows, E, _st()), "polus_residual_compress")
 
 
@@ -739,14 +800,12 @@ def residual_decompress(codes, packed, centroids, weights, nbits, y):
     """y [..., E] (f32 or bf16) = centroids[code] + weights[bucket], one f32 addition rounded once to y's dtype; rows
     whose code is >= K are zeros (codes int16 [...], packed uint8 [..., E * nbits / 8], weights f32 [2^nbits];
     include/polus_hip.h polus_residual_decompress)."""
+    op = "residual_decompress"
     _req_cuda(codes, packed, centroids, weights, y)
-    E = y.shape[-1]
-    rows = y.numel() // E
-    K = _residual_codec(centroids, weights, nbits, E, "weights")
-    assert y.is_contiguous() and centroids.dtype == y.dtype
-    assert codes.dtype == torch.int16 and codes.is_contiguous() and codes.numel() == rows
-    assert packed.dtype == torch.uint8 and packed.is_contiguous() and packed.numel() == rows * E * nbits // 8
-    check(_lib.load().polus_residual_decompress(dtype_code(y.dtype), ptr(codes), ptr(packed), ptr(centroids), K, ptr(weights),
+    assert nbits in (1, 2, 4), f"{op}: nbits must be 1, 2 or 4 (got {nbits})"
+    code, rows, E = _residual_rows(op, "y", y, codes, packed, nbits)
+    K = _residual_codec(op, centroids, y.dtype, weights, nbits, E, "weights")
+    check(_lib.load().polus_residual_decompress(code, ptr(codes), ptr(packed), ptr(centroids), K, ptr(weights),
                                                 int(nbits), ptr(y), rows, E, _st()), "polus_residual_decompress")
 
 
@@ -755,19 +814,20 @@ def maxsim_rerank_res(q, codes, packed, centroids, weights, nbits, qmask, dmask,
     centroids [K, E] in q's dtype, weights f32 [2^nbits]): score[b, c] is bit for bit what maxsim_rerank gives over the
     corpus residual_decompress writes; -inf where cand[b, c] is outside [0, N) (include/polus_hip.h
     polus_maxsim_rerank_res)."""
+    op = "maxsim_rerank_res"
     _req_cuda(q, codes, packed, centroids, weights, qmask, dmask, cand, score)
+    code = _eng(op, "q", q, 3)
     B, Lq, E = q.shape
-    K = _residual_codec(centroids, weights, nbits, E, "weights")
-    assert q.is_contiguous() and centroids.dtype == q.dtype
-    assert codes.dim() == 2 and codes.dtype == torch.int16 and codes.is_contiguous()
+    K = _residual_codec(op, centroids, q.dtype, weights, nbits, E, "weights")
+    assert codes.dtype == torch.int16 and codes.dim() == 2 and codes.is_contiguous(), \
+        f"{op}: codes must be contiguous int16 [N, Ld] {_got(codes)}"
     N, Ld = codes.shape
-    assert packed.dtype == torch.uint8 and tuple(packed.shape) == (N, Ld, E * nbits // 8) and packed.is_contiguous()
-    assert cand.dtype == torch.int32 and cand.dim() == 2 and cand.shape[0] == B and (cand.stride(1) == 1 or cand.shape[1] == 1)
-    C = cand.shape[1]
-    assert score.dtype == torch.float32 and tuple(score.shape) == (B, C) and (score.stride(1) == 1 or C == 1)
-    check(_lib.load().polus_maxsim_rerank_res(dtype_code(q.dtype), ptr(q), ptr(codes), ptr(packed), ptr(centroids), K,
-                                              ptr(weights), int(nbits), ptr(_maxsim_mask(qmask, B, Lq, "qmask")),
-                                              ptr(_maxsim_mask(dmask, N, Ld, "dmask")), ptr(cand), cand.stride(0), ptr(score),
+    _flat(op, "packed", packed, torch.uint8, (N, Ld, E * nbits // 8))
+    C = _cand(op, cand, B)
+    _mat(op, "score", score, _F32T, B, C, exact=True)
+    check(_lib.load().polus_maxsim_rerank_res(code, ptr(q), ptr(codes), ptr(packed), ptr(centroids), K,
+                                              ptr(weights), int(nbits), ptr(_maxsim_mask(op, "qmask", qmask, B, Lq)),
+                                              ptr(_maxsim_mask(op, "dmask", dmask, N, Ld)), ptr(cand), cand.stride(0), ptr(score),
                                               score.stride(0), B, C, N, Lq, Ld, E, _st()), "polus_maxsim_rerank_res")
 
 
@@ -778,15 +838,18 @@ def topk_merge(scores, top_val, top_id, id0=0, init=False, ids=None):
     (include/polus_hip.h polus_topk_merge).  With `ids` (int32 [rows, n], any row stride; not together with an id0)
     column c of row r is document ids[r, c] and a negative id drops the column (polus_topk_merge_ids); exact for distinct
     ids, while of a repeated id an undefined number of copies returns."""
+    op = "topk_merge"
     _req_cuda(scores, top_val, top_id, ids)
+    assert scores.dim() == 2, f"{op}: scores must be f32 [rows, n] {_got(scores)}"
     rows, n = scores.shape
+    _mat(op, "scores", scores, _F32T, rows, n, exact=True)
+    assert top_val.dim() == 2, f"{op}: top_val must be f32 [{rows}, k] {_got(top_val)}"
     k = top_val.shape[1]
-    assert scores.dtype == torch.float32 and scores.dim() == 2 and (scores.stride(1) == 1 or n == 1)
-    assert top_val.dtype == torch.float32 and top_id.dtype == torch.int32 and top_val.is_contiguous() and top_id.is_contiguous()
-    assert tuple(top_val.shape) == (rows, k) and tuple(top_id.shape) == (rows, k)
+    _flat(op, "top_val", top_val, _F32T, (rows, k))
+    _flat(op, "top_id", top_id, _I32T, (rows, k))
     if ids is not None:
-        assert int(id0) == 0, "ids and a non-zero id0 exclude each other"
-        assert ids.dtype == torch.int32 and tuple(ids.shape) == (rows, n) and (ids.stride(1) == 1 or n == 1)
+        assert int(id0) == 0, f"{op}: ids and a non-zero id0 exclude each other"
+        _mat(op, "ids", ids, _I32T, rows, n, exact=True)
         check(_lib.load().polus_topk_merge_ids(ptr(scores), scores.stride(0), ptr(ids), ids.stride(0), rows, n,
                                                ptr(top_val), ptr(top_id), k, 1 if init else 0, _st()),
               "polus_topk_merge_ids")
@@ -797,6 +860,20 @@ def topk_merge(scores, top_val, top_id, id0=0, init=False, ids=None):
 
 CENTROID_ROUTES = (None, "lds", "global")
 CentroidRoute = collections.namedtuple("CentroidRoute", "route lds_bytes")
+
+
+def _centroid_table(op, table, B, Lq):
+    """The look-up table of the centroid scorers: f32 [K, >= B * Lq] with any row stride; returns K."""
+    assert table.dim() == 2, f"{op}: table must be f32 [K, >= {B * Lq}] {_got(table)}"
+    _mat(op, "table", table, _F32T, table.shape[0], B * Lq)
+    return table.shape[0]
+
+
+def _codes2d(op, codes):
+    """The centroid codes of a corpus: contiguous int16 [N, Ld] (the bits of the unsigned code); returns (N, Ld)."""
+    assert codes.dtype == torch.int16 and codes.dim() == 2 and codes.is_contiguous(), \
+        f"{op}: codes must be contiguous int16 [N, Ld] {_got(codes)}"
+    return codes.shape
 
 
 def centroid_scores_route(B, N, Lq, Ld, K):
@@ -812,25 +889,26 @@ def centroid_scores(table, qmask, codes, score, B, Lq):
     MaxSim approximated by look-ups.  table f32 [K, >= B * Lq] (any row stride) holds <centroid c, query token (b, i)>;
     codes int16 [N, Ld] (the bits are the unsigned code; 0xFFFF or any code >= K: no token); qmask int32 [B, Lq] or
     None (include/polus_hip.h polus_centroid_scores)."""
+    op = "centroid_scores"
     _req_cuda(table, qmask, codes, score)
-    K = table.shape[0]
-    N, Ld = codes.shape
-    assert table.dtype == torch.float32 and table.dim() == 2 and table.shape[1] >= B * Lq and (table.stride(1) == 1 or table.shape[1] == 1)
-    assert codes.dtype == torch.int16 and codes.is_contiguous()
-    assert score.dtype == torch.float32 and score.dim() == 2 and score.shape[0] >= B and score.shape[1] >= N and (score.stride(1) == 1 or score.shape[1] == 1)
-    check(_lib.load().polus_centroid_scores(ptr(table), table.stride(0), ptr(_maxsim_mask(qmask, B, Lq, "qmask")), ptr(codes),
+    K = _centroid_table(op, table, B, Lq)
+    N, Ld = _codes2d(op, codes)
+    _mat(op, "score", score, _F32T, B, N)
+    check(_lib.load().polus_centroid_scores(ptr(table), table.stride(0), ptr(_maxsim_mask(op, "qmask", qmask, B, Lq)), ptr(codes),
                                             ptr(score), score.stride(0), int(B), N, int(Lq), Ld, K, _st()), "polus_centroid_scores")
 
 
 def centroid_codes(sim, mask, codes, rows=None, K=None):
     """codes[r] (int16, the bits of the unsigned code) = 0xFFFF where mask[r] == 0, else the first column maximising
     sim[r] (f32 [rows, K], any row stride); NaN never wins (include/polus_hip.h polus_centroid_codes)."""
+    op = "centroid_codes"
     _req_cuda(sim, mask, codes)
+    assert sim.dim() == 2, f"{op}: sim must be f32 [rows, K] {_got(sim)}"
     rows = sim.shape[0] if rows is None else rows
     K = sim.shape[1] if K is None else K
-    assert sim.dtype == torch.float32 and sim.dim() == 2 and sim.shape[0] >= rows and sim.shape[1] >= K and (sim.stride(1) == 1 or sim.shape[1] == 1)
-    assert codes.dtype == torch.int16 and codes.is_contiguous() and codes.numel() >= rows
-    assert mask is None or (mask.dtype == torch.int32 and mask.is_contiguous() and mask.numel() >= rows)
+    _mat(op, "sim", sim, _F32T, rows, K)
+    _vec(op, "codes", codes, torch.int16, rows)
+    _vec(op, "mask", mask, _I32T, rows, optional=True)
     check(_lib.load().polus_centroid_codes(ptr(sim), sim.stride(0), ptr(mask), ptr(codes), rows, K, _st()), "polus_centroid_codes")
 
 
@@ -838,14 +916,18 @@ def centroid_update(x, codes, prev, out, counts, eps=1e-12):
     """One spherical k-means update: out[k] = the normalised f32 sum of the rows x[t] with codes[t] == k, rounded once to
     x's dtype, or prev[k] where no row has code k or the sum's norm is <= eps; counts[k] (int32) = how many rows.
     x [T, E], codes int16 [T], prev / out [K, E] (distinct buffers) (include/polus_hip.h polus_centroid_update)."""
+    op = "centroid_update"
     _req_cuda(x, codes, prev, out, counts)
+    code = _eng(op, "x", x, 2)
     T, E = x.shape
+    assert prev.dtype == x.dtype and prev.dim() == 2 and prev.shape[1] == E and prev.is_contiguous(), \
+        f"{op}: prev must be contiguous [K, {E}] in x's dtype {x.dtype} {_got(prev)}"
     K = prev.shape[0]
-    assert x.is_contiguous() and prev.is_contiguous() and out.is_contiguous() and out.data_ptr() != prev.data_ptr()
-    assert prev.dtype == x.dtype and out.dtype == x.dtype and tuple(prev.shape) == (K, E) and tuple(out.shape) == (K, E)
-    assert codes.dtype == torch.int16 and codes.is_contiguous() and codes.numel() == T
-    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == K
-    check(_lib.load().polus_centroid_update(dtype_code(x.dtype), ptr(x), ptr(codes), ptr(prev), ptr(out), ptr(counts), T, K, E,
+    _flat(op, "out", out, x.dtype, (K, E))
+    _disjoint(op, "out", out, "prev", prev)
+    _flat(op, "codes", codes, torch.int16, T)
+    _flat(op, "counts", counts, _I32T, K)
+    check(_lib.load().polus_centroid_update(code, ptr(x), ptr(codes), ptr(prev), ptr(out), ptr(counts), T, K, E,
                                             float(eps), _st()), "polus_centroid_update")
 
 
@@ -853,52 +935,66 @@ def centroid_scores_ids(table, qmask, codes, cand, score, B, Lq):
     """score[b, c] (f32, any row stride) = the bits `centroid_scores` gives the pair (b, cand[b, c]); cand int32 [B, C]
     (any row stride), an id outside [0, N) gives -inf and reads nothing; table, qmask and codes (int16 [N, Ld]) as for
     `centroid_scores` (include/polus_hip.h polus_centroid_scores_ids)."""
+    op = "centroid_scores_ids"
     _req_cuda(table, qmask, codes, cand, score)
-    K = table.shape[0]
-    N, Ld = codes.shape
+    K = _centroid_table(op, table, B, Lq)
+    N, Ld = _codes2d(op, codes)
+    assert cand.dim() == 2, f"{op}: cand must be int32 [>= {B}, C] {_got(cand)}"
     C = cand.shape[1]
-    assert table.dtype == torch.float32 and table.dim() == 2 and table.shape[1] >= B * Lq and (table.stride(1) == 1 or table.shape[1] == 1)
-    assert codes.dtype == torch.int16 and codes.is_contiguous()
-    assert cand.dtype == torch.int32 and cand.dim() == 2 and cand.shape[0] >= B and (cand.stride(1) == 1 or C == 1)
-    assert score.dtype == torch.float32 and score.dim() == 2 and score.shape[0] >= B and score.shape[1] >= C and (score.stride(1) == 1 or score.shape[1] == 1)
-    check(_lib.load().polus_centroid_scores_ids(ptr(table), table.stride(0), ptr(_maxsim_mask(qmask, B, Lq, "qmask")), ptr(codes),
+    _mat(op, "cand", cand, _I32T, B, C)
+    _mat(op, "score", score, _F32T, B, C)
+    check(_lib.load().polus_centroid_scores_ids(ptr(table), table.stride(0), ptr(_maxsim_mask(op, "qmask", qmask, B, Lq)), ptr(codes),
                                                 ptr(cand), cand.stride(0), ptr(score), score.stride(0), int(B), C, N, int(Lq), Ld,
                                                 K, _st()), "polus_centroid_scores_ids")
 
 
-def _ivf_codes(codes, K):
-    assert codes.dtype == torch.int16 and codes.dim() == 2 and codes.is_contiguous() and 1 <= int(K) <= 65535
-    return codes.shape
+def _ivf_codes(op, codes, K, k_name):
+    N, Ld = _codes2d(op, codes)
+    assert 1 <= int(K) <= 65535, f"{op}: {k_name} must give 1 <= K <= 65535 centroids (got {K})"
+    return N, Ld
+
+
+def _bitmap(op, bitmap, B, N):
+    """The candidate bitmap: int32 words [>= B, >= ceil(N / 32)] with any row stride."""
+    _mat(op, "bitmap", bitmap, _I32T, B, (int(N) + 31) // 32)
+
+
+def _docs(op, docs):
+    """The document ids of the inverted lists: contiguous int32 [P]; P = offsets[K] lives on the device."""
+    assert docs.dtype == torch.int32 and docs.dim() == 1 and docs.is_contiguous(), f"{op}: docs must be contiguous int32 [P] {_got(docs)}"
 
 
 def ivf_count(codes, K, counts):
     """counts[c] (int32 [K], zeroed here) = the documents of codes (int16 [N, Ld], the bits of the unsigned code; >= K: no
     token) that hold at least one token coded c (include/polus_hip.h polus_ivf_count)."""
+    op = "ivf_count"
     _req_cuda(codes, counts)
-    N, Ld = _ivf_codes(codes, K)
-    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == K
+    N, Ld = _ivf_codes(op, codes, K, "K")
+    _flat(op, "counts", counts, _I32T, int(K))
     check(_lib.load().polus_ivf_count(ptr(codes), N, Ld, int(K), ptr(counts), _st()), "polus_ivf_count")
 
 
 def ivf_offsets(counts, offsets):
     """offsets (int32 [K + 1]) = the exclusive scan of counts (int32 [K]); offsets[K] = P, the number of (centroid,
     document) pairs, or -1 when P >= 2^31 (include/polus_hip.h polus_ivf_offsets)."""
+    op = "ivf_offsets"
     _req_cuda(counts, offsets)
     K = counts.numel()
-    assert counts.dtype == torch.int32 and counts.is_contiguous() and offsets.dtype == torch.int32 and offsets.is_contiguous()
-    assert offsets.numel() == K + 1
+    _flat(op, "counts", counts, _I32T, K)
+    _flat(op, "offsets", offsets, _I32T, K + 1)
     check(_lib.load().polus_ivf_offsets(ptr(counts), K, ptr(offsets), _st()), "polus_ivf_offsets")
 
 
 def ivf_fill(codes, offsets, cursor, docs):
     """docs[offsets[c] .. offsets[c + 1]) (int32 [P]) = the ids of the documents counted for centroid c, each once, in
     no specified order; cursor int32 [K] is scratch (include/polus_hip.h polus_ivf_fill)."""
+    op = "ivf_fill"
     _req_cuda(codes, offsets, cursor, docs)
     K = cursor.numel()
-    N, Ld = _ivf_codes(codes, K)
-    assert offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.numel() == K + 1
-    assert cursor.dtype == torch.int32 and cursor.is_contiguous()
-    assert docs.dtype == torch.int32 and docs.dim() == 1 and docs.is_contiguous()
+    _flat(op, "cursor", cursor, _I32T, K)
+    N, Ld = _ivf_codes(op, codes, K, "cursor")
+    _flat(op, "offsets", offsets, _I32T, K + 1)
+    _docs(op, docs)
     check(_lib.load().polus_ivf_fill(ptr(codes), N, Ld, K, ptr(offsets), docs.numel(), ptr(cursor),
                                      ptr(docs) if docs.numel() else None, _st()), "polus_ivf_fill")
 
@@ -908,14 +1004,16 @@ def ivf_mark(probes, qmask, offsets, docs, N, bitmap, B, Lq):
     gets bit d of row b for every document d in the list of every probe of query b: probes int32 [B * Lq, nprobe] (any
     row stride; an id outside [0, K) is skipped), qmask int32 [B, Lq] or None, lists (offsets int32 [K + 1], docs int32
     [P]) (include/polus_hip.h polus_ivf_mark)."""
+    op = "ivf_mark"
     _req_cuda(probes, qmask, offsets, docs, bitmap)
     K = offsets.numel() - 1
+    assert probes.dim() == 2, f"{op}: probes must be int32 [>= {B * Lq}, nprobe] {_got(probes)}"
     nprobe = probes.shape[1]
-    assert probes.dtype == torch.int32 and probes.dim() == 2 and probes.shape[0] >= B * Lq and (probes.stride(1) == 1 or nprobe == 1)
-    assert offsets.dtype == torch.int32 and offsets.is_contiguous() and docs.dtype == torch.int32 and docs.dim() == 1 and docs.is_contiguous()
-    assert bitmap.dtype == torch.int32 and bitmap.dim() == 2 and bitmap.shape[0] >= B and (bitmap.stride(1) == 1 or bitmap.shape[1] == 1)
-    assert bitmap.shape[1] >= (int(N) + 31) // 32
-    check(_lib.load().polus_ivf_mark(ptr(probes), probes.stride(0), ptr(_maxsim_mask(qmask, B, Lq, "qmask")), ptr(offsets),
+    _mat(op, "probes", probes, _I32T, B * Lq, nprobe)
+    _flat(op, "offsets", offsets, _I32T, K + 1)
+    _docs(op, docs)
+    _bitmap(op, bitmap, B, N)
+    check(_lib.load().polus_ivf_mark(ptr(probes), probes.stride(0), ptr(_maxsim_mask(op, "qmask", qmask, B, Lq)), ptr(offsets),
                                      ptr(docs) if docs.numel() else None, docs.numel(), K, int(N), ptr(bitmap), bitmap.stride(0),
                                      int(B), int(Lq), nprobe, _st()), "polus_ivf_mark")
 
@@ -924,14 +1022,15 @@ def ivf_compact(bitmap, N, count, cand=None):
     """count[b] (int32 [B]) = the set bits of row b of bitmap (int32 [B, >= ceil(N / 32)] words) among bits [0, N); with
     cand (int32 [B, cap], any row stride) its row gets the first cap set positions in ascending order, then -1
     (include/polus_hip.h polus_ivf_compact)."""
+    op = "ivf_compact"
     _req_cuda(bitmap, count, cand)
     B = count.numel()
-    assert bitmap.dtype == torch.int32 and bitmap.dim() == 2 and bitmap.shape[0] >= B and (bitmap.stride(1) == 1 or bitmap.shape[1] == 1)
-    assert bitmap.shape[1] >= (int(N) + 31) // 32
-    assert count.dtype == torch.int32 and count.is_contiguous()
+    _flat(op, "count", count, _I32T, B)
+    _bitmap(op, bitmap, B, N)
     cap = ldc = 0
     if cand is not None:
-        assert cand.dtype == torch.int32 and cand.dim() == 2 and cand.shape[0] >= B and (cand.stride(1) == 1 or cand.shape[1] == 1)
+        assert cand.dim() == 2, f"{op}: cand must be int32 [>= {B}, cap] {_got(cand)}"
+        _mat(op, "cand", cand, _I32T, B, cand.shape[1])
         cap, ldc = cand.shape[1], cand.stride(0)
     check(_lib.load().polus_ivf_compact(ptr(bitmap), bitmap.stride(0), B, int(N), ptr(cand), ldc, cap, ptr(count), _st()),
           "polus_ivf_compact")
@@ -1230,49 +1329,56 @@ def fuse_lists(ids, scores, out_id, out_val, count, n_docs, mode, weights=None, 
 def maxsim_bwd(q, d, dscore, argmax, dq, dd):
     """dq [B, Lq, E] and dd [N, Ld, E] from dscore (f32 [B, N], row stride free) and the forward's argmax; every
     element is written."""
+    op = "maxsim_bwd"
     _req_cuda(q, d, dscore, argmax, dq, dd)
-    B, Lq, E = q.shape
-    N, Ld = d.shape[0], d.shape[1]
-    assert d.dim() == 3 and d.shape[2] == E and d.dtype == q.dtype and q.is_contiguous() and d.is_contiguous()
-    assert dscore.dtype == torch.float32 and dscore.shape[0] >= B and dscore.shape[1] >= N and dscore.stride(1) == 1
-    assert argmax.dtype == torch.int32 and argmax.is_contiguous() and argmax.numel() == B * N * Lq
-    assert dq.shape == q.shape and dd.shape == d.shape and dq.dtype == q.dtype and dd.dtype == d.dtype
-    assert dq.is_contiguous() and dd.is_contiguous()
-    check(_lib.load().polus_maxsim_bwd(dtype_code(q.dtype), ptr(q), ptr(d), ptr(dscore), dscore.stride(0), ptr(argmax),
+    code, B, Lq, E, N, Ld = _maxsim_qd(op, q, d)
+    _mat(op, "dscore", dscore, _F32T, B, N)
+    _flat(op, "argmax", argmax, _I32T, B * N * Lq)
+    _flat(op, "dq", dq, q.dtype, tuple(q.shape))
+    _flat(op, "dd", dd, d.dtype, tuple(d.shape))
+    check(_lib.load().polus_maxsim_bwd(code, ptr(q), ptr(d), ptr(dscore), _ld(dscore, N), ptr(argmax),
                                        ptr(dq), ptr(dd), B, N, Lq, Ld, E, _st()), "polus_maxsim_bwd")
+
+
+def _norm_rows(op, name, t, rnorm):
+    """The rows of a normalisation: t [..., E] f32 or bf16, contiguous, with one f32 rnorm per row."""
+    code = _dt(op, name, t)
+    assert t.dim() >= 1 and t.is_contiguous(), f"{op}: {name} must be contiguous [..., E] {_got(t)}"
+    E = t.shape[-1]
+    rows = t.numel() // E
+    _flat(op, "rnorm", rnorm, _F32T, rows)
+    return code, rows, E
 
 
 def l2norm_fwd(x, y, rnorm, eps=1e-12):
     """y = x / max(|x|, eps) over the last axis, rnorm (f32, one per row) = 1 / max(|x|, eps)."""
+    op = "l2norm_fwd"
     _req_cuda(x, y, rnorm)
-    E = x.shape[-1]
-    rows = x.numel() // E
-    assert x.is_contiguous() and y.is_contiguous() and y.shape == x.shape and y.dtype == x.dtype
-    assert rnorm.dtype == torch.float32 and rnorm.numel() == rows and rnorm.is_contiguous()
-    check(_lib.load().polus_l2norm_fwd(dtype_code(x.dtype), ptr(x), ptr(y), ptr(rnorm), rows, E, float(eps), _st()),
+    code, rows, E = _norm_rows(op, "x", x, rnorm)
+    _flat(op, "y", y, x.dtype, tuple(x.shape))
+    check(_lib.load().polus_l2norm_fwd(code, ptr(x), ptr(y), ptr(rnorm), rows, E, float(eps), _st()),
           "polus_l2norm_fwd")
 
 
 def l2norm_bwd(y, rnorm, dy, dx, eps=1e-12):
-    """dx = (dy - y <y, dy>) * rnorm where |x| > eps, dy / eps otherwise (y, rnorm: the forward's outputs)."""
+    """dx = (dy - y <y, dy>) * rnorm where |x| > eps, dy / eps otherwise (y, rnorm: the forward's outputs; rnorm
+    contiguous f32, one per row)."""
+    op = "l2norm_bwd"
     _req_cuda(y, rnorm, dy, dx)
-    E = y.shape[-1]
-    rows = y.numel() // E
-    assert y.is_contiguous() and dy.is_contiguous() and dx.is_contiguous()
-    assert dy.shape == y.shape and dx.shape == y.shape and dy.dtype == y.dtype and dx.dtype == y.dtype
-    assert rnorm.dtype == torch.float32 and rnorm.numel() == rows
-    check(_lib.load().polus_l2norm_bwd(dtype_code(y.dtype), ptr(y), ptr(rnorm), ptr(dy), ptr(dx), rows, E, float(eps), _st()),
+    code, rows, E = _norm_rows(op, "y", y, rnorm)
+    _flat(op, "dy", dy, y.dtype, tuple(y.shape))
+    _flat(op, "dx", dx, y.dtype, tuple(y.shape))
+    check(_lib.load().polus_l2norm_bwd(code, ptr(y), ptr(rnorm), ptr(dy), ptr(dx), rows, E, float(eps), _st()),
           "polus_l2norm_bwd")
 
 
 SLOT_MAJOR, QUERY_MAJOR = 0, 1          # tuple layouts: document (b, j) at row j*B + b / b*n + j
 
 
-def _tuple_shapes(q, d, name):
-    B, Lq, E = q.shape
-    assert d.dim() == 3 and d.shape[2] == E and d.dtype == q.dtype and q.is_contiguous() and d.is_contiguous()
-    assert d.shape[0] % B == 0, f"{name}: {d.shape[0]} documents are not n per query for {B} queries"
-    return B, d.shape[0] // B, Lq, d.shape[1], E
+def _tuple_shapes(op, q, d):
+    code, B, Lq, E, docs, Ld = _maxsim_qd(op, q, d)
+    assert B >= 1 and docs % B == 0, f"{op}: d holds {docs} documents, which is not n per query for {B} queries"
+    return code, B, docs // B, Lq, Ld, E
 
 
 def maxsim_tuples_fwd(q, d, qmask, dmask, score, argmax, layout=SLOT_MAJOR):
@@ -1280,48 +1386,51 @@ def maxsim_tuples_fwd(q, d, qmask, dmask, score, argmax, layout=SLOT_MAJOR):
     argmax[b, j, i] (int32 [B, n, Lq]) the winning document token: bit for bit what maxsim_fwd gives that pair.
     q [B, Lq, E], d [B n, Ld, E]; document (b, j) is row j*B + b (layout SLOT_MAJOR) or b*n + j (QUERY_MAJOR)
     (include/polus_hip.h polus_maxsim_tuples_fwd)."""
+    op = "maxsim_tuples_fwd"
     _req_cuda(q, d, qmask, dmask, score, argmax)
-    B, n, Lq, Ld, E = _tuple_shapes(q, d, "maxsim_tuples_fwd")
-    assert score.dtype == torch.float32 and score.dim() == 2 and score.shape[0] >= B and score.shape[1] >= n
-    assert score.stride(1) == 1 or score.shape[1] == 1
-    assert argmax.dtype == torch.int32 and argmax.is_contiguous() and argmax.numel() == B * n * Lq
-    lds = score.stride(0) if score.shape[0] > 1 else max(score.stride(0), n)
-    check(_lib.load().polus_maxsim_tuples_fwd(dtype_code(q.dtype), ptr(q), ptr(d), ptr(_maxsim_mask(qmask, B, Lq, "qmask")),
-                                              ptr(_maxsim_mask(dmask, B * n, Ld, "dmask")), ptr(score), lds, ptr(argmax),
+    code, B, n, Lq, Ld, E = _tuple_shapes(op, q, d)
+    _mat(op, "score", score, _F32T, B, n)
+    _flat(op, "argmax", argmax, _I32T, B * n * Lq)
+    check(_lib.load().polus_maxsim_tuples_fwd(code, ptr(q), ptr(d), ptr(_maxsim_mask(op, "qmask", qmask, B, Lq)),
+                                              ptr(_maxsim_mask(op, "dmask", dmask, B * n, Ld)), ptr(score), _ld(score, n), ptr(argmax),
                                               B, n, int(layout), Lq, Ld, E, _st()), "polus_maxsim_tuples_fwd")
 
 
 def maxsim_tuples_bwd(q, d, dscore, argmax, dq, dd, layout=SLOT_MAJOR):
     """dq [B, Lq, E] and dd [B n, Ld, E] from dscore (f32 [B, n], row stride free) and the forward's argmax; every
     element is written, with the bits maxsim_bwd gives for the dscore scattered into a zero [B, B n] matrix."""
+    op = "maxsim_tuples_bwd"
     _req_cuda(q, d, dscore, argmax, dq, dd)
-    B, n, Lq, Ld, E = _tuple_shapes(q, d, "maxsim_tuples_bwd")
-    assert dscore.dtype == torch.float32 and dscore.dim() == 2 and dscore.shape[0] >= B and dscore.shape[1] >= n
-    assert dscore.stride(1) == 1 or dscore.shape[1] == 1
-    assert argmax.dtype == torch.int32 and argmax.is_contiguous() and argmax.numel() == B * n * Lq
-    assert dq.shape == q.shape and dd.shape == d.shape and dq.dtype == q.dtype and dd.dtype == d.dtype
-    assert dq.is_contiguous() and dd.is_contiguous()
-    lds = dscore.stride(0) if dscore.shape[0] > 1 else max(dscore.stride(0), n)
-    check(_lib.load().polus_maxsim_tuples_bwd(dtype_code(q.dtype), ptr(q), ptr(d), ptr(dscore), lds, ptr(argmax),
+    code, B, n, Lq, Ld, E = _tuple_shapes(op, q, d)
+    _mat(op, "dscore", dscore, _F32T, B, n)
+    _flat(op, "argmax", argmax, _I32T, B * n * Lq)
+    _flat(op, "dq", dq, q.dtype, tuple(q.shape))
+    _flat(op, "dd", dd, d.dtype, tuple(d.shape))
+    check(_lib.load().polus_maxsim_tuples_bwd(code, ptr(q), ptr(d), ptr(dscore), _ld(dscore, n), ptr(argmax),
                                               ptr(dq), ptr(dd), B, n, int(layout), Lq, Ld, E, _st()),
           "polus_maxsim_tuples_bwd")
 
 
-def _dot_tuple_shapes(q, d, name):
-    assert q.dim() == 2 and d.dim() == 2 and d.dtype == q.dtype and d.shape[1] == q.shape[1], f"{name}: q [B, W], d [B n, W]"
+def _dot_tuple_shapes(op, q, d):
+    """q [B, W] and d [B n, W] of one f32 or bf16 dtype with free row strides; returns (dtype code, B, n, W)."""
+    code = _dt(op, "q", q)
+    assert q.dim() == 2 and q.shape[0] >= 1, f"{op}: q must be [B, W] {_got(q)}"
     B, W = q.shape
-    assert d.shape[0] % B == 0, f"{name}: {d.shape[0]} documents are not n per query for {B} queries"
-    return B, d.shape[0] // B, W
+    _mat(op, "q", q, q.dtype, B, W, exact=True)
+    assert d.dim() == 2, f"{op}: d must be [B n, {W}] in q's dtype {_got(d)}"
+    _mat(op, "d", d, q.dtype, d.shape[0], W, exact=True)
+    assert d.shape[0] % B == 0, f"{op}: d holds {d.shape[0]} documents, which is not n per query for {B} queries"
+    return code, B, d.shape[0] // B, W
 
 
 def dot_tuples_fwd(q, d, score, layout=SLOT_MAJOR):
     """score[b, j] (f32, any row stride >= n) = <q[b], d[doc(b, j)]>, accumulated in f32 in a fixed order; q [B, W] and
     d [B n, W] f32 or bf16 with free row strides (include/polus_hip.h polus_dot_tuples_fwd)."""
+    op = "dot_tuples_fwd"
     _req_cuda(q, d, score)
-    B, n, W = _dot_tuple_shapes(q, d, "dot_tuples_fwd")
-    ldq, ldd = _rows2d(q, q.dtype, B, W, "q"), _rows2d(d, q.dtype, B * n, W, "d")
-    lds = _rows2d(score, torch.float32, B, n, "score")
-    check(_lib.load().polus_dot_tuples_fwd(dtype_code(q.dtype), ptr(q), ldq, ptr(d), ldd, ptr(score), lds, B, n, int(layout),
+    code, B, n, W = _dot_tuple_shapes(op, q, d)
+    _mat(op, "score", score, _F32T, B, n)
+    check(_lib.load().polus_dot_tuples_fwd(code, ptr(q), _ld(q, W), ptr(d), _ld(d, W), ptr(score), _ld(score, n), B, n, int(layout),
                                            W, _st()), "polus_dot_tuples_fwd")
     return score
 
@@ -1329,40 +1438,43 @@ def dot_tuples_fwd(q, d, score, layout=SLOT_MAJOR):
 def dot_tuples_bwd(q, d, dscore, dq, dd, layout=SLOT_MAJOR):
     """dq[b] = sum over j ascending of dscore[b, j] d[doc(b, j)] and dd[doc(b, j)] = dscore[b, j] q[b], f32 arithmetic
     rounded once; dscore f32 [B, n]; every element of dq and dd (free row strides) is written."""
+    op = "dot_tuples_bwd"
     _req_cuda(q, d, dscore, dq, dd)
-    B, n, W = _dot_tuple_shapes(q, d, "dot_tuples_bwd")
-    ldq, ldd = _rows2d(q, q.dtype, B, W, "q"), _rows2d(d, q.dtype, B * n, W, "d")
-    lddq, lddd = _rows2d(dq, q.dtype, B, W, "dq"), _rows2d(dd, q.dtype, B * n, W, "dd")
-    lds = _rows2d(dscore, torch.float32, B, n, "dscore")
-    check(_lib.load().polus_dot_tuples_bwd(dtype_code(q.dtype), ptr(q), ldq, ptr(d), ldd, ptr(dscore), lds, ptr(dq), lddq,
-                                           ptr(dd), lddd, B, n, int(layout), W, _st()), "polus_dot_tuples_bwd")
+    code, B, n, W = _dot_tuple_shapes(op, q, d)
+    _mat(op, "dq", dq, q.dtype, B, W)
+    _mat(op, "dd", dd, q.dtype, B * n, W)
+    _mat(op, "dscore", dscore, _F32T, B, n)
+    check(_lib.load().polus_dot_tuples_bwd(code, ptr(q), _ld(q, W), ptr(d), _ld(d, W), ptr(dscore), _ld(dscore, n), ptr(dq), _ld(dq, W),
+                                           ptr(dd), _ld(dd, W), B, n, int(layout), W, _st()), "polus_dot_tuples_bwd")
 
 
-def _distill(fn, student, teacher, loss, dstudent):
+def _distill(op, student, teacher, loss, dstudent):
     lib = _lib.load()
     _req_cuda(student, teacher, loss, dstudent)
+    assert student.dim() == 2, f"{op}: student must be f32 [rows, n] {_got(student)}"
     rows, n = student.shape
-    lds, ldt = _rows2d(student, torch.float32, rows, n, "student"), _rows2d(teacher, torch.float32, rows, n, "teacher")
-    ldd = _rows2d(dstudent, torch.float32, rows, n, "dstudent")
-    assert teacher.shape == student.shape and dstudent.shape == student.shape
-    assert loss.dtype == torch.float32 and loss.numel() >= 1
+    _mat(op, "student", student, _F32T, rows, n, exact=True)
+    _mat(op, "teacher", teacher, _F32T, rows, n, exact=True)
+    _mat(op, "dstudent", dstudent, _F32T, rows, n, exact=True)
+    assert loss.dtype == torch.float32 and loss.numel() >= 1, f"{op}: loss must be f32 with at least one element {_got(loss)}"
     nb = lib.polus_distill_workspace_bytes(rows)
     ws = workspace(student.device).get(nb)
-    check(getattr(lib, fn)(ptr(student), lds, ptr(teacher), ldt, ptr(loss), ptr(dstudent), ldd, rows, n, ptr(ws), nb, _st()),
-          fn)
+    fn = "polus_" + op
+    check(getattr(lib, fn)(ptr(student), _ld(student, n), ptr(teacher), _ld(teacher, n), ptr(loss), ptr(dstudent), _ld(dstudent, n),
+                           rows, n, ptr(ws), nb, _st()), fn)
 
 
 def distill_kl(student, teacher, loss, dstudent):
     """loss (f32 [1]) = mean over the rows of KL(softmax(teacher) || softmax(student)) over the present columns, and
     dstudent its gradient; student, teacher, dstudent f32 [rows, n] with free row strides; a column whose teacher score
     is -inf is absent (include/polus_hip.h polus_distill_kl)."""
-    _distill("polus_distill_kl", student, teacher, loss, dstudent)
+    _distill("distill_kl", student, teacher, loss, dstudent)
 
 
 def margin_mse(student, teacher, loss, dstudent):
     """loss (f32 [1]) = mean over the present negatives j >= 1 of every row of ((s_0 - s_j) - (t_0 - t_j))^2, column 0
     the positive, and dstudent its gradient; same arguments as distill_kl (include/polus_hip.h polus_margin_mse)."""
-    _distill("polus_margin_mse", student, teacher, loss, dstudent)
+    _distill("margin_mse", student, teacher, loss, dstudent)
 
 
 def _pair_rows(rows, B, n, distinct=False):

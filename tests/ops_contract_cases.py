@@ -1,7 +1,7 @@
-"""The contract between a caller and the training-step wrappers of polus_amd/ops.py, stated once.
+"""The contract between a caller and the training-step and token-retrieval wrappers of polus_amd/ops.py, stated once.
 
 The kernels take raw pointers, so a wrapper is the only place that can see a tensor's dtype, length and strides.  For every
-wrapper of CORE_OPS this table holds
+wrapper of CORE_OPS and RETRIEVAL_OPS this table holds
 
   good()    the arguments of the smallest legal call, as CPU tensors (every optional tensor present), every extent exactly
             what the call touches (include/polus_hip.h): the rule a wrapper enforces is "at least this much", never "equal",
@@ -14,7 +14,8 @@ wrapper of CORE_OPS this table holds
 Families: "dtype" (f32 given as bf16, int32 as int64, the int64 tables as int32, tensors that must share a dtype given
 different ones, an either-engine-dtype tensor given as float64), "extent" (one row, column or element fewer than the call
 touches), "layout" (a non-unit inner stride where the entry point takes one row stride; a non-contiguous view where it takes a
-flat pointer and a count), "count", and "device" (a host tensor).  A bad call must raise AssertionError or PolusHipError
+flat pointer and a count), "count", "overlap" (two parameters the header calls distinct buffers given as overlapping views
+of one allocation) and "device" (a host tensor).  A bad call must raise AssertionError or PolusHipError
 before any entry point is reached, and the message must start with "<wrapper>: <parameter>" naming the mutated parameter or
 one of the parameters its spec blames (the partner of a mismatch).  The device family keeps the shared `_req_cuda`, whose
 message names neither.
@@ -27,8 +28,11 @@ import inspect
 import numpy as np
 import torch
 
+from tests import fp8_ref, ivf_ref, maxsim_ref, residual_ref, search_ref, tuple_ref
+
 F32, BF16, I32, I64, F64 = torch.float32, torch.bfloat16, torch.int32, torch.int64, torch.float64
-SWAP = {F32: BF16, BF16: F32, I32: I64, I64: I32}
+I16, U8, I8 = torch.int16, torch.uint8, torch.int8
+SWAP = {F32: BF16, BF16: F32, I32: I64, I64: I32, I16: I32, U8: I8, I8: U8}
 STREAM = 0xD00D                     # the dummy stream handle the recording library sees
 
 
@@ -50,18 +54,27 @@ CORE_OPS = ("gemm", "dense_bwd_params", "dense_bwd_params_grouped", "dense_thin_
             "clip_scale", "cast", "scale_", "act_bwd", "transpose_bf16", "transpose_bf16_batched", "dropout",
             "set_dynamic_params")
 
-# every other public function of ops.py: the retrieval wrappers, the host-only route reports and the helpers
+# the token-retrieval wrappers: MaxSim and normalisation, the FP8 and the residual index, top-k, centroids, inverted lists,
+# tuples and distillation
+RETRIEVAL_OPS = ("maxsim_fwd", "maxsim_bwd", "maxsim_scores", "maxsim_rerank", "l2norm_fwd", "l2norm_bwd",
+                 "fp8_quantize", "fp8_dequantize", "maxsim_scores_fp8", "maxsim_rerank_fp8",
+                 "residual_compress", "residual_decompress", "maxsim_rerank_res", "topk_merge",
+                 "centroid_scores", "centroid_codes", "centroid_update", "centroid_scores_ids",
+                 "ivf_count", "ivf_offsets", "ivf_fill", "ivf_mark", "ivf_compact",
+                 "maxsim_tuples_fwd", "maxsim_tuples_bwd", "dot_tuples_fwd", "dot_tuples_bwd", "distill_kl", "margin_mse")
+
+# every other public function of ops.py, none of them in this table: first the host-only route reports and the helpers, then
+# the families left out so far
 OTHER_OPS = ("workspace", "set_env", "reserve_cus", "gemm_route", "dense_bwd_params_route", "dense_bwd_params_grouped_route",
-             "rowwise_route", "layernorm_bwd_partial_floats", "softmax_xent_wide_route", "softmax_xent_wide", "gather_rows",
-             "inverse_map", "crf_nll", "crf_viterbi", "maxsim_fwd", "maxsim_scores", "maxsim_rerank", "fp8_quantize",
-             "fp8_dequantize", "maxsim_scores_fp8", "maxsim_rerank_fp8", "residual_compress", "residual_decompress",
-             "maxsim_rerank_res", "topk_merge", "centroid_scores_route", "centroid_scores", "centroid_codes", "centroid_update",
-             "centroid_scores_ids", "ivf_count", "ivf_offsets", "ivf_fill", "ivf_mark", "ivf_compact", "splade_pool_fwd",
-             "splade_pool_bwd", "flops_reg", "sparse_scores", "bm25_term_counts", "bm25_weights", "bm25_query",
+             "rowwise_route", "layernorm_bwd_partial_floats", "centroid_scores_route", "dense_thin_supported", "dropout_mask",
+             # the wide masked-LM loss and the CRF wrappers
+             "softmax_xent_wide_route", "softmax_xent_wide", "gather_rows", "inverse_map", "crf_nll", "crf_viterbi",
+             # the sparse, lexical, postings, fusion, mining, pair and BIO wrappers: they name their parameters through _rows2d
+             "splade_pool_fwd", "splade_pool_bwd", "flops_reg", "sparse_scores", "bm25_term_counts", "bm25_weights", "bm25_query",
              "postings_count", "postings_offsets", "postings_fill", "sparse_compact_rows", "bm25_query_lists",
-             "postings_scores", "mine_negatives", "fuse_lists", "maxsim_bwd", "l2norm_fwd", "l2norm_bwd", "maxsim_tuples_fwd",
-             "maxsim_tuples_bwd", "dot_tuples_fwd", "dot_tuples_bwd", "distill_kl", "margin_mse", "pair_lengths", "pair_pack",
-             "pair_scatter_scores", "bio_entity_counts", "bio_spans", "dense_thin_supported", "dropout_mask")
+             "postings_scores", "mine_negatives", "fuse_lists", "pair_lengths", "pair_pack",
+             "pair_scatter_scores", "bio_entity_counts", "bio_spans")
+# (the product-quantisation wrappers live in polus_amd/pq_ops.py and state their own contract there)
 
 
 def public_functions(ops):
@@ -96,8 +109,9 @@ def free(**kw):
 
 
 class Case:
-    def __init__(self, good, entry, tensors, scalars=(), counts=(), expect=None):
+    def __init__(self, good, entry, tensors, scalars=(), counts=(), expect=None, overlaps=()):
         self.good, self.entry, self.tensors, self.scalars, self.counts, self.expect = good, tuple(entry), tensors, tuple(scalars), tuple(counts), expect
+        self.overlaps = tuple(overlaps)         # (a, b): two parameters the header calls distinct buffers
 
 
 def _rng(seed):
@@ -331,6 +345,280 @@ def _dyn_block():
     return dict(block=torch.zeros(4, dtype=I32))
 
 
+# ------------------------------------------------------------------------------------------------- good calls: token retrieval
+# B queries of Lq tokens, N documents of Ld tokens, E features, K centroids, C candidates per query, T rows, P probes per
+# token: pairwise different, so that an argument in the wrong slot changes what the library is handed and what it computes
+R_B, R_N, R_K, R_LD, R_LQ, R_C, R_T, R_P, R_E = 2, 3, 4, 5, 6, 7, 9, 8, 32
+R_NBITS = 2
+SLOT_MAJOR, QUERY_MAJOR = 0, 1      # polus_amd/ops.py
+
+
+def _byte(*shape):
+    return torch.full(shape, 0xAA, dtype=U8)
+
+
+def _ms_in(seed, docs=R_N):
+    """q [B, Lq, E], d [docs, Ld, E], masks with holes; masked positions hold large values, so counting one shows."""
+    r = _rng(seed)
+    q, d = r.standard_normal((R_B, R_LQ, R_E)), r.standard_normal((docs, R_LD, R_E))
+    qm, dm = np.ones((R_B, R_LQ), np.int32), np.ones((docs, R_LD), np.int32)
+    qm[0, 2], qm[1, 4:] = 0, 0
+    dm[0, 1], dm[docs - 1, 3:], dm[1, 0] = 0, 0, 0
+    q[qm == 0] *= 4.0
+    d[dm == 0] *= 4.0
+    return dict(q=_f(q), d=_f(d), qmask=_f(qm, I32), dmask=_f(dm, I32)), r
+
+
+def _cand_ids():
+    """int32 [B, C] names of documents, with one id on each side of [0, N)."""
+    return _f([[2, 0, 1, -1, 1, 2, 0], [0, R_N, 2, 1, 0, 0, 2]], I32)
+
+
+def _maxsim_fwd():
+    p, _ = _ms_in(30)
+    p.update(score=_nan(R_B, R_N), argmax=_neg(R_B, R_N, R_LQ))
+    return p
+
+
+def _maxsim_scores():
+    p, _ = _ms_in(30)
+    p.update(score=_nan(R_B, R_N))
+    return p
+
+
+def _maxsim_bwd():
+    p, r = _ms_in(30)
+    am = maxsim_ref.maxsim_fwd(p["q"].double().numpy(), p["d"].double().numpy(), p["qmask"].numpy(), p["dmask"].numpy())[1]
+    return dict(q=p["q"], d=p["d"], dscore=_f(r.standard_normal((R_B, R_N))), argmax=_f(am, I32), dq=_nan(R_B, R_LQ, R_E),
+                dd=_nan(R_N, R_LD, R_E))
+
+
+def _maxsim_rerank():
+    p, _ = _ms_in(30)
+    p.update(cand=_cand_ids(), score=_nan(R_B, R_C))
+    return p
+
+
+def _l2_x():
+    return _f(_rng(31).standard_normal((R_B, R_LQ, R_E)) * 3)
+
+
+def _l2norm_fwd():
+    return dict(x=_l2_x(), y=_nan(R_B, R_LQ, R_E), rnorm=_nan(R_B, R_LQ), eps=1e-12)
+
+
+def _l2norm_bwd():
+    # y and rnorm are the forward's outputs; the GPU test fills them by running l2norm_fwd
+    y, rn = maxsim_ref.l2norm_fwd(_l2_x().double().numpy())
+    return dict(y=_f(y), rnorm=_f(rn), dy=_f(_rng(32).standard_normal((R_B, R_LQ, R_E))), dx=_nan(R_B, R_LQ, R_E), eps=1e-12)
+
+
+def _fp8_x():
+    r = _rng(33)
+    return _f(r.standard_normal((R_N, R_LD, R_E)) * np.exp2(r.integers(-6, 6, size=(R_N, R_LD, 1))))
+
+
+def _fp8_quantize():
+    return dict(x=_fp8_x(), codes=_byte(R_N, R_LD, R_E), scale=_nan(R_N, R_LD))
+
+
+def _fp8_corpus():
+    codes, scale, _ = fp8_ref.quantize(_fp8_x().numpy())
+    return dict(codes=_f(codes, U8), scale=_f(scale))
+
+
+def _fp8_dequantize():
+    return dict(y=_nan(R_N, R_LD, R_E), **_fp8_corpus())
+
+
+def _maxsim_scores_fp8():
+    p, _ = _ms_in(30)
+    p.pop("d")
+    p.update(score=_nan(R_B, R_N), **_fp8_corpus())
+    return p
+
+
+def _maxsim_rerank_fp8():
+    p = _maxsim_scores_fp8()
+    p.update(cand=_cand_ids(), score=_nan(R_B, R_C))
+    return p
+
+
+def _tok_codes():
+    """int16 [N, Ld] centroid codes (the bits of the unsigned code): 0xFFFF and 9 (>= K) are no token.  The lists:
+    centroid 0 {0, 2}, 1 {0, 1}, 2 {1}, 3 {2}."""
+    return _f(np.array([[0, 1, 1, 0xFFFF, 9], [1, 2, 0xFFFF, 2, 1], [3, 3, 0, 0xFFFF, 0xFFFF]], np.uint16).view(np.int16), I16)
+
+
+def _res_codec():
+    r = _rng(34)
+    cent = r.standard_normal((R_K, R_E))
+    cent /= np.linalg.norm(cent, axis=1, keepdims=True)
+    return dict(centroids=_f(cent), cutoffs=_f([-0.3, 0.05, 0.4]), weights=_f([-0.6, -0.1, 0.2, 0.7])), r
+
+
+def _res_x(c, r):
+    codes = residual_ref.codes_u16(_tok_codes().numpy())
+    x = c["centroids"].numpy()[np.where(codes < R_K, codes, 0)] + 0.5 * r.standard_normal((R_N, R_LD, R_E)).astype(np.float32)
+    return _f(x)
+
+
+def _residual_compress():
+    c, r = _res_codec()
+    return dict(x=_res_x(c, r), codes=_tok_codes(), centroids=c["centroids"], cutoffs=c["cutoffs"], nbits=R_NBITS,
+                packed=_byte(R_N, R_LD, R_E * R_NBITS // 8))
+
+
+def _res_corpus():
+    c, r = _res_codec()
+    x, codes = _res_x(c, r), _tok_codes()
+    packed = residual_ref.compress(x.numpy().reshape(-1, R_E), codes.numpy().reshape(-1), c["centroids"].numpy(), c["cutoffs"].numpy(), R_NBITS)
+    return dict(codes=codes, packed=_f(packed.reshape(R_N, R_LD, -1), U8), centroids=c["centroids"], weights=c["weights"], nbits=R_NBITS)
+
+
+def _residual_decompress():
+    return dict(y=_nan(R_N, R_LD, R_E), **_res_corpus())
+
+
+def _maxsim_rerank_res():
+    p, _ = _ms_in(30)
+    p.pop("d")
+    p.update(cand=_cand_ids(), score=_nan(R_B, R_C), **_res_corpus())
+    return p
+
+
+def _topk_scores():
+    s = _rng(35).standard_normal((R_B, R_C)).astype(np.float32)
+    s[0, 1], s[0, 4], s[1, 2] = np.nan, -np.inf, s[1, 5]             # dropped, dropped, a tie (to the lower id)
+    return s
+
+
+TOPK_ID0 = 5
+
+
+def _topk_merge():
+    # the state of an earlier call over documents [0, TOPK_ID0), with one padding slot in row 1
+    first = _rng(36).standard_normal((R_B, TOPK_ID0)).astype(np.float32)
+    first[1, 1:3] = -np.inf
+    val, idx = search_ref.topk(first, R_K)
+    return dict(scores=_f(_topk_scores()), top_val=_f(val), top_id=_f(idx, I32), id0=TOPK_ID0, init=False)
+
+
+def _topk_merge_ids():
+    ids = np.array([[40, 3, 17, 9, 28, -1, 5], [6, 2, 31, 30, 8, 12, 1]], np.int32)
+    return dict(scores=_f(_topk_scores()), top_val=_nan(R_B, R_K), top_id=torch.full((R_B, R_K), 12345, dtype=I32), init=True,
+                ids=_f(ids, I32))
+
+
+def _cs_in():
+    qm = np.ones((R_B, R_LQ), np.int32)
+    qm[0, 2], qm[1, 4:] = 0, 0
+    return dict(table=_f(_rng(37).standard_normal((R_K, R_B * R_LQ))), qmask=_f(qm, I32), codes=_tok_codes())
+
+
+def _centroid_scores():
+    return dict(score=_nan(R_B, R_N), B=R_B, Lq=R_LQ, **_cs_in())
+
+
+def _centroid_scores_ids():
+    return dict(cand=_cand_ids(), score=_nan(R_B, R_C), B=R_B, Lq=R_LQ, **_cs_in())
+
+
+def _centroid_codes():
+    sim = _rng(38).standard_normal((R_T, R_K)).astype(np.float32)
+    sim[2, 1], sim[4] = np.nan, np.nan                               # NaN never wins; a row of NaN codes 0
+    mask = np.ones(R_T, np.int32)
+    mask[5] = 0
+    return dict(sim=_f(sim), mask=_f(mask, I32), codes=torch.full((R_T,), 1234, dtype=I16))
+
+
+def _centroid_update():
+    r = _rng(39)
+    # centroid 2 has no row and keeps prev; 0xFFFF is no token
+    codes = np.array([0, 1, 1, 3, 0xFFFF, 0, 3, 1, 0], np.uint16).view(np.int16)
+    return dict(x=_f(r.standard_normal((R_T, R_E))), codes=_f(codes, I16), prev=_f(r.standard_normal((R_K, R_E))), out=_nan(R_K, R_E),
+                counts=_neg(R_K), eps=1e-12)
+
+
+def _ivf_lists():
+    counts, offsets, members = ivf_ref.lists(residual_ref.codes_u16(_tok_codes().numpy()), R_K)
+    return counts, offsets, np.concatenate(members)
+
+
+def _ivf_count():
+    return dict(codes=_tok_codes(), K=R_K, counts=_neg(R_K))
+
+
+def _ivf_offsets():
+    return dict(counts=_f(_ivf_lists()[0], I32), offsets=_neg(R_K + 1))
+
+
+def _ivf_fill():
+    _, offsets, docs = _ivf_lists()
+    return dict(codes=_tok_codes(), offsets=_f(offsets, I32), cursor=_neg(R_K), docs=_neg(len(docs)))
+
+
+def _ivf_mark():
+    _, offsets, docs = _ivf_lists()
+    probes = np.full((R_B, R_LQ, R_P), -1, np.int32)
+    probes[0, 0, 3], probes[0, 2, 0] = 2, 0                          # query 0: centroid 2; token 2 is masked
+    probes[1, 1, :2], probes[1, 5, 1] = (3, 7), 1                    # query 1: centroid 3 and an id past K; token 5 is masked
+    qm = np.ones((R_B, R_LQ), np.int32)
+    qm[0, 2], qm[1, 4:] = 0, 0
+    return dict(probes=_f(probes.reshape(R_B * R_LQ, R_P), I32), qmask=_f(qm, I32), offsets=_f(offsets, I32), docs=_f(docs, I32), N=R_N,
+                bitmap=_neg(R_B, 1), B=R_B, Lq=R_LQ)
+
+
+def _ivf_compact():
+    # row 0: more set bits than cap; row 1: one bit below N and one at N + 1, which does not count
+    return dict(bitmap=_f([[0b111], [0b10010]], I32), N=R_N, count=_neg(R_B), cand=torch.full((R_B, 2), 77, dtype=I32))
+
+
+def _tuples_fwd(layout):
+    def good():
+        p, _ = _ms_in(40, R_B * R_N)
+        p.update(score=_nan(R_B, R_N), argmax=_neg(R_B, R_N, R_LQ), layout=layout)
+        return p
+    return good
+
+
+def _tuples_bwd(layout):
+    def good():
+        p, r = _ms_in(40, R_B * R_N)
+        am = tuple_ref.maxsim_tuples_fwd(p["q"].double().numpy(), p["d"].double().numpy(), p["qmask"].numpy(), p["dmask"].numpy(), layout)[1]
+        return dict(q=p["q"], d=p["d"], dscore=_f(r.standard_normal((R_B, R_N))), argmax=_f(am, I32), dq=_nan(R_B, R_LQ, R_E),
+                    dd=_nan(R_B * R_N, R_LD, R_E), layout=layout)
+    return good
+
+
+def _dot_in():
+    r = _rng(41)
+    return dict(q=_f(r.standard_normal((R_B, R_E))), d=_f(r.standard_normal((R_B * R_N, R_E)))), r
+
+
+def _dot_fwd(layout):
+    def good():
+        p, _ = _dot_in()
+        p.update(score=_nan(R_B, R_N), layout=layout)
+        return p
+    return good
+
+
+def _dot_bwd(layout):
+    def good():
+        p, r = _dot_in()
+        p.update(dscore=_f(r.standard_normal((R_B, R_N))), dq=_nan(R_B, R_E), dd=_nan(R_B * R_N, R_E), layout=layout)
+        return p
+    return good
+
+
+def _distill():
+    r = _rng(42)
+    t = r.standard_normal((R_B, R_K)).astype(np.float32) * 2
+    t[1, 2] = -np.inf                                                # an absent column
+    return dict(student=_f(r.standard_normal((R_B, R_K)) * 2), teacher=_f(t), loss=_nan(1), dstudent=_nan(R_B, R_K))
+
+
 # ------------------------------------------------------------------------------------------------- what the entry points must be handed
 def _p(t):
     return None if t is None else t.data_ptr()
@@ -468,6 +756,147 @@ def _x_dyn(p):
     return {"polus_set_dynamic_params": (_p(p["block"]),)}
 
 
+def _ps(p, *names):
+    return tuple(_p(p[n]) for n in names)
+
+
+def _pld(t):
+    return (_p(t), t.stride(0))
+
+
+_MS_DIMS = (R_LQ, R_LD, R_E, STREAM)
+
+
+def _x_maxsim_fwd(p):
+    return {"polus_maxsim_fwd": (0,) + _ps(p, "q", "d", "qmask", "dmask") + _pld(p["score"]) + (_p(p["argmax"]), R_B, R_N) + _MS_DIMS}
+
+
+def _x_maxsim_scores(p):
+    return {"polus_maxsim_scores": (0,) + _ps(p, "q", "d", "qmask", "dmask") + _pld(p["score"]) + (R_B, R_N) + _MS_DIMS}
+
+
+def _x_maxsim_bwd(p):
+    return {"polus_maxsim_bwd": (0,) + _ps(p, "q", "d") + _pld(p["dscore"]) + _ps(p, "argmax", "dq", "dd") + (R_B, R_N) + _MS_DIMS}
+
+
+def _x_maxsim_rerank(p):
+    return {"polus_maxsim_rerank": (0,) + _ps(p, "q", "d", "qmask", "dmask") + _pld(p["cand"]) + _pld(p["score"]) + (R_B, R_C, R_N) + _MS_DIMS}
+
+
+def _x_l2norm_fwd(p):
+    return {"polus_l2norm_fwd": (0,) + _ps(p, "x", "y", "rnorm") + (R_B * R_LQ, R_E, 1e-12, STREAM)}
+
+
+def _x_l2norm_bwd(p):
+    return {"polus_l2norm_bwd": (0,) + _ps(p, "y", "rnorm", "dy", "dx") + (R_B * R_LQ, R_E, 1e-12, STREAM)}
+
+
+def _x_fp8_quantize(p):
+    return {"polus_fp8_quantize_rows": (0,) + _ps(p, "x", "codes", "scale") + (R_N * R_LD, R_E, STREAM)}
+
+
+def _x_fp8_dequantize(p):
+    return {"polus_fp8_dequantize_rows": (0,) + _ps(p, "codes", "scale", "y") + (R_N * R_LD, R_E, STREAM)}
+
+
+def _x_maxsim_scores_fp8(p):
+    return {"polus_maxsim_scores_fp8": (0,) + _ps(p, "q", "codes", "scale", "qmask", "dmask") + _pld(p["score"]) + (R_B, R_N) + _MS_DIMS}
+
+
+def _x_maxsim_rerank_fp8(p):
+    return {"polus_maxsim_rerank_fp8": (0,) + _ps(p, "q", "codes", "scale", "qmask", "dmask") + _pld(p["cand"]) + _pld(p["score"])
+            + (R_B, R_C, R_N) + _MS_DIMS}
+
+
+def _x_residual_compress(p):
+    return {"polus_residual_compress": (0,) + _ps(p, "x", "codes", "centroids") + (R_K, _p(p["cutoffs"]), R_NBITS, _p(p["packed"]),
+                                                                                 R_N * R_LD, R_E, STREAM)}
+
+
+def _x_residual_decompress(p):
+    return {"polus_residual_decompress": (0,) + _ps(p, "codes", "packed", "centroids") + (R_K, _p(p["weights"]), R_NBITS, _p(p["y"]),
+                                                                                       R_N * R_LD, R_E, STREAM)}
+
+
+def _x_maxsim_rerank_res(p):
+    return {"polus_maxsim_rerank_res": (0,) + _ps(p, "q", "codes", "packed", "centroids") + (R_K, _p(p["weights"]), R_NBITS)
+            + _ps(p, "qmask", "dmask") + _pld(p["cand"]) + _pld(p["score"]) + (R_B, R_C, R_N) + _MS_DIMS}
+
+
+def _x_topk_merge(p):
+    return {"polus_topk_merge": _pld(p["scores"]) + (R_B, R_C, TOPK_ID0) + _ps(p, "top_val", "top_id") + (R_K, 0, STREAM)}
+
+
+def _x_topk_merge_ids(p):
+    return {"polus_topk_merge_ids": _pld(p["scores"]) + _pld(p["ids"]) + (R_B, R_C) + _ps(p, "top_val", "top_id") + (R_K, 1, STREAM)}
+
+
+def _x_centroid_scores(p):
+    return {"polus_centroid_scores": _pld(p["table"]) + _ps(p, "qmask", "codes") + _pld(p["score"]) + (R_B, R_N, R_LQ, R_LD, R_K, STREAM)}
+
+
+def _x_centroid_scores_ids(p):
+    return {"polus_centroid_scores_ids": _pld(p["table"]) + _ps(p, "qmask", "codes") + _pld(p["cand"]) + _pld(p["score"])
+            + (R_B, R_C, R_N, R_LQ, R_LD, R_K, STREAM)}
+
+
+def _x_centroid_codes(p):
+    return {"polus_centroid_codes": _pld(p["sim"]) + _ps(p, "mask", "codes") + (R_T, R_K, STREAM)}
+
+
+def _x_centroid_update(p):
+    return {"polus_centroid_update": (0,) + _ps(p, "x", "codes", "prev", "out", "counts") + (R_T, R_K, R_E, 1e-12, STREAM)}
+
+
+IVF_PAIRS = 6                       # the (centroid, document) pairs of _tok_codes()
+
+
+def _x_ivf_count(p):
+    return {"polus_ivf_count": (_p(p["codes"]), R_N, R_LD, R_K, _p(p["counts"]), STREAM)}
+
+
+def _x_ivf_offsets(p):
+    return {"polus_ivf_offsets": (_p(p["counts"]), R_K, _p(p["offsets"]), STREAM)}
+
+
+def _x_ivf_fill(p):
+    return {"polus_ivf_fill": (_p(p["codes"]), R_N, R_LD, R_K, _p(p["offsets"]), IVF_PAIRS, _p(p["cursor"]), _p(p["docs"]), STREAM)}
+
+
+def _x_ivf_mark(p):
+    return {"polus_ivf_mark": _pld(p["probes"]) + _ps(p, "qmask", "offsets", "docs") + (IVF_PAIRS, R_K, R_N) + _pld(p["bitmap"])
+            + (R_B, R_LQ, R_P, STREAM)}
+
+
+def _x_ivf_compact(p):
+    return {"polus_ivf_compact": _pld(p["bitmap"]) + (R_B, R_N) + _pld(p["cand"]) + (2, _p(p["count"]), STREAM)}
+
+
+def _x_tuples_fwd(p):
+    return {"polus_maxsim_tuples_fwd": (0,) + _ps(p, "q", "d", "qmask", "dmask") + _pld(p["score"]) + (_p(p["argmax"]), R_B, R_N, p["layout"])
+            + _MS_DIMS}
+
+
+def _x_tuples_bwd(p):
+    return {"polus_maxsim_tuples_bwd": (0,) + _ps(p, "q", "d") + _pld(p["dscore"]) + _ps(p, "argmax", "dq", "dd") + (R_B, R_N, p["layout"])
+            + _MS_DIMS}
+
+
+def _x_dot_fwd(p):
+    return {"polus_dot_tuples_fwd": (0,) + _pld(p["q"]) + _pld(p["d"]) + _pld(p["score"]) + (R_B, R_N, p["layout"], R_E, STREAM)}
+
+
+def _x_dot_bwd(p):
+    return {"polus_dot_tuples_bwd": (0,) + _pld(p["q"]) + _pld(p["d"]) + _pld(p["dscore"]) + _pld(p["dq"]) + _pld(p["dd"])
+            + (R_B, R_N, p["layout"], R_E, STREAM)}
+
+
+def _x_distill(fn):
+    def expect(p):
+        return {fn: _pld(p["student"]) + _pld(p["teacher"]) + (_p(p["loss"]),) + _pld(p["dstudent"]) + (R_B, R_K, ANY, ANY, STREAM)}
+    return expect
+
+
 # ------------------------------------------------------------------------------------------------- the table
 _vec32 = lambda **kw: fixed(F32, **kw)
 _one = lambda dtype=F32, **kw: fixed(dtype, layout=None, **kw)          # a single element: no layout to get wrong
@@ -554,6 +983,107 @@ CASES = {
     "set_dynamic_params": Case(_dyn_block, ["polus_set_dynamic_params"], dict(block=T(None)), expect=_x_dyn),
 }
 
+# ---- token retrieval
+_mask = lambda **kw: fixed(I32, **kw)
+_score = lambda **kw: fixed(F32, out=True, ext=("row", "col"), layout="inner", **kw)
+_cand = lambda **kw: fixed(I32, ext=("row", "col"), layout="inner", blame=("score",), **kw)
+_codes2 = lambda **kw: fixed(I16, ext=(), **kw)                       # [N, Ld]: defines N and Ld (EXEMPT)
+_RERANK = dict(qmask=_mask(), dmask=_mask(), cand=_cand(), score=_score())
+_CS = dict(table=fixed(F32, ext=("col",), layout="inner"), qmask=_mask(), codes=_codes2())
+_CS_COUNTS = (("B", R_B + 1, ("table", "qmask", "score")), ("Lq", R_LQ + 1, ("table", "qmask")))
+_RES = dict(codes=fixed(I16), centroids=same(ext=("col",)))
+_TUPLE_KEYS = (("", SLOT_MAJOR), (":query_major", QUERY_MAJOR))
+
+CASES.update({
+    "maxsim_fwd": Case(_maxsim_fwd, ["polus_maxsim_fwd"],
+                       dict(q=same(blame=("d", "qmask", "argmax")), d=same(blame=("dmask", "argmax")), qmask=_mask(), dmask=_mask(),
+                            score=_score(), argmax=fixed(I32, out=True)), expect=_x_maxsim_fwd),
+    "maxsim_scores": Case(_maxsim_scores, ["polus_maxsim_scores"],
+                          dict(q=same(blame=("d", "qmask")), d=same(blame=("dmask",)), qmask=_mask(), dmask=_mask(), score=_score()),
+                          expect=_x_maxsim_scores),
+    "maxsim_bwd": Case(_maxsim_bwd, ["polus_maxsim_bwd"],
+                       dict(q=same(blame=("d", "argmax")), d=same(blame=("argmax",)), dscore=fixed(F32, **_mat), argmax=fixed(I32),
+                            dq=same(out=True), dd=same(out=True)), expect=_x_maxsim_bwd),
+    "maxsim_rerank": Case(_maxsim_rerank, ["polus_maxsim_rerank"], dict(q=same(blame=("d", "cand")), d=same(blame=("dmask",)), **_RERANK),
+                          expect=_x_maxsim_rerank),
+    "l2norm_fwd": Case(_l2norm_fwd, ["polus_l2norm_fwd"], dict(x=same(blame=("y", "rnorm")), y=same(out=True), rnorm=fixed(F32, out=True)),
+                       scalars=("eps",), expect=_x_l2norm_fwd),
+    "l2norm_bwd": Case(_l2norm_bwd, ["polus_l2norm_bwd"], dict(y=same(blame=("rnorm", "dy")), rnorm=fixed(F32), dy=same(), dx=same(out=True)),
+                       scalars=("eps",), expect=_x_l2norm_bwd),
+    "fp8_quantize": Case(_fp8_quantize, ["polus_fp8_quantize_rows"],
+                         dict(x=free(blame=("codes",)), codes=fixed(U8, out=True), scale=fixed(F32, out=True)), expect=_x_fp8_quantize),
+    "fp8_dequantize": Case(_fp8_dequantize, ["polus_fp8_dequantize_rows"],
+                           dict(codes=fixed(U8), scale=fixed(F32), y=free(out=True, blame=("codes",))), expect=_x_fp8_dequantize),
+    "maxsim_scores_fp8": Case(_maxsim_scores_fp8, ["polus_maxsim_scores_fp8"],
+                              dict(q=free(blame=("qmask",)), codes=fixed(U8, blame=("scale",)), scale=fixed(F32), qmask=_mask(), dmask=_mask(),
+                                   score=_score()), expect=_x_maxsim_scores_fp8),
+    "maxsim_rerank_fp8": Case(_maxsim_rerank_fp8, ["polus_maxsim_rerank_fp8"],
+                              dict(q=free(blame=("cand",)), codes=fixed(U8, blame=("scale",)), scale=fixed(F32), **_RERANK),
+                              expect=_x_maxsim_rerank_fp8),
+    "residual_compress": Case(_residual_compress, ["polus_residual_compress"],
+                              dict(x=same(blame=("codes", "centroids")), cutoffs=fixed(F32), packed=fixed(U8, out=True), **_RES),
+                              scalars=("nbits",), expect=_x_residual_compress),
+    "residual_decompress": Case(_residual_decompress, ["polus_residual_decompress"],
+                                dict(packed=fixed(U8), weights=fixed(F32), y=same(out=True, blame=("codes", "centroids")), **_RES),
+                                scalars=("nbits",), expect=_x_residual_decompress),
+    "maxsim_rerank_res": Case(_maxsim_rerank_res, ["polus_maxsim_rerank_res"],
+                              dict(q=same(blame=("centroids", "cand")), codes=fixed(I16, blame=("packed",)), packed=fixed(U8),
+                                   centroids=same(ext=("col",)), weights=fixed(F32), **_RERANK),
+                              scalars=("nbits",), expect=_x_maxsim_rerank_res),
+    "topk_merge": Case(_topk_merge, ["polus_topk_merge"],
+                       dict(scores=fixed(F32, layout="inner", blame=("top_val",)), top_val=fixed(F32, out=True, ext=("row", "col"), blame=("top_id",)),
+                            top_id=fixed(I32, out=True, ext=("row", "col"))), scalars=("id0", "init", "ids"), expect=_x_topk_merge),
+    "topk_merge:ids": Case(_topk_merge_ids, ["polus_topk_merge_ids"],
+                           dict(scores=fixed(F32, layout="inner", blame=("top_val",)), top_val=fixed(F32, out=True, ext=("row", "col"), blame=("top_id",)),
+                                top_id=fixed(I32, out=True, ext=("row", "col")), ids=fixed(I32, ext=("row", "col"), layout="inner")),
+                           scalars=("id0", "init"), expect=_x_topk_merge_ids),
+    "centroid_scores": Case(_centroid_scores, ["polus_centroid_scores"], dict(score=_score(), **_CS), counts=_CS_COUNTS, expect=_x_centroid_scores),
+    "centroid_scores_ids": Case(_centroid_scores_ids, ["polus_centroid_scores_ids"],
+                                dict(cand=fixed(I32, layout="inner"), score=_score(), **_CS), counts=_CS_COUNTS, expect=_x_centroid_scores_ids),
+    "centroid_codes": Case(_centroid_codes, ["polus_centroid_codes"], dict(sim=fixed(F32, ext=(), layout="inner"), mask=_mask(), codes=fixed(I16, out=True)),
+                           counts=(("rows", R_T + 1, ("sim", "mask", "codes")), ("K", R_K + 1, ("sim",))), expect=_x_centroid_codes),
+    "centroid_update": Case(_centroid_update, ["polus_centroid_update"],
+                            dict(x=same(blame=("prev", "codes")), codes=fixed(I16), prev=same(blame=("out",)), out=same(out=True),
+                                 counts=fixed(I32, out=True)), scalars=("eps",), overlaps=(("out", "prev"),), expect=_x_centroid_update),
+    "ivf_count": Case(_ivf_count, ["polus_ivf_count"], dict(codes=_codes2(), counts=fixed(I32, out=True)), counts=(("K", R_K + 1, ("counts",)),),
+                      expect=_x_ivf_count),
+    "ivf_offsets": Case(_ivf_offsets, ["polus_ivf_offsets"], dict(counts=fixed(I32, blame=("offsets",)), offsets=fixed(I32, out=True)),
+                        expect=_x_ivf_offsets),
+    "ivf_fill": Case(_ivf_fill, ["polus_ivf_fill"], dict(codes=_codes2(), offsets=fixed(I32), cursor=fixed(I32, out=True, blame=("offsets",)),
+                                                         docs=fixed(I32, out=True, ext=())), expect=_x_ivf_fill),
+    "ivf_mark": Case(_ivf_mark, ["polus_ivf_mark"], dict(probes=fixed(I32, layout="inner"), qmask=_mask(), offsets=fixed(I32, ext=()),
+                                                         docs=fixed(I32, ext=()), bitmap=fixed(I32, out=True, **_mat)),
+                     counts=(("N", 33, ("bitmap",)), ("B", R_B + 1, ("probes", "qmask", "bitmap")), ("Lq", R_LQ + 1, ("probes", "qmask"))),
+                     expect=_x_ivf_mark),
+    "ivf_compact": Case(_ivf_compact, ["polus_ivf_compact"], dict(bitmap=fixed(I32, **_mat), count=fixed(I32, out=True, ext=()),
+                                                                  cand=fixed(I32, out=True, layout="inner")),
+                        counts=(("N", 33, ("bitmap",)),), expect=_x_ivf_compact),
+    "distill_kl": Case(_distill, ["polus_distill_kl"], dict(student=fixed(F32, blame=("teacher",), **_mat), teacher=fixed(F32, **_mat),
+                                                            loss=_one(out=True), dstudent=fixed(F32, out=True, **_mat)),
+                       expect=_x_distill("polus_distill_kl")),
+    "margin_mse": Case(_distill, ["polus_margin_mse"], dict(student=fixed(F32, blame=("teacher",), **_mat), teacher=fixed(F32, **_mat),
+                                                            loss=_one(out=True), dstudent=fixed(F32, out=True, **_mat)),
+                       expect=_x_distill("polus_margin_mse")),
+})
+for _suffix, _layout in _TUPLE_KEYS:
+    CASES.update({
+        "maxsim_tuples_fwd" + _suffix: Case(_tuples_fwd(_layout), ["polus_maxsim_tuples_fwd"],
+                                            dict(q=same(blame=("d", "score", "argmax")), d=same(blame=("dmask", "argmax")), qmask=_mask(),
+                                                 dmask=_mask(), score=_score(), argmax=fixed(I32, out=True)),
+                                            scalars=("layout",), expect=_x_tuples_fwd),
+        "maxsim_tuples_bwd" + _suffix: Case(_tuples_bwd(_layout), ["polus_maxsim_tuples_bwd"],
+                                            dict(q=same(blame=("d", "dscore", "argmax")), d=same(blame=("argmax",)), dscore=fixed(F32, **_mat),
+                                                 argmax=fixed(I32), dq=same(out=True), dd=same(out=True)),
+                                            scalars=("layout",), expect=_x_tuples_bwd),
+        "dot_tuples_fwd" + _suffix: Case(_dot_fwd(_layout), ["polus_dot_tuples_fwd"],
+                                         dict(q=same(blame=("d", "score"), **_mat), d=same(**_mat), score=_score()),
+                                         scalars=("layout",), expect=_x_dot_fwd),
+        "dot_tuples_bwd" + _suffix: Case(_dot_bwd(_layout), ["polus_dot_tuples_bwd"],
+                                         dict(q=same(blame=("d", "dscore", "dq"), **_mat), d=same(blame=("dd",), **_mat), dscore=fixed(F32, **_mat),
+                                              dq=same(out=True, **_mat), dd=same(out=True, **_mat)),
+                                         scalars=("layout",), expect=_x_dot_bwd),
+    })
+
 # (wrapper, parameter, family) -> why no bad case of that family exists
 EXEMPT = {
     ("embed_ln_fwd", "word", "extent"): "word defines V and H; fewer rows are a smaller vocabulary, which the kernel clamps ids against",
@@ -573,6 +1103,15 @@ EXEMPT = {
     ("scale_", "x", "extent"): "x defines n: a shorter x is a smaller legal call",
     ("transpose_bf16_batched", "src_base", "extent"): "the offsets into the arena live in the device table segs_dev; dst_base is checked against src_base",
     ("set_dynamic_params", "block", "dtype"): "16 raw bytes {u32, f32, f32, u32}: any dtype that holds them is legal",
+    ("centroid_scores", "codes", "extent"): "codes defines N and Ld: fewer rows are a smaller corpus, and score is checked against that N",
+    ("centroid_scores_ids", "codes", "extent"): "codes defines N and Ld: the kernel gives -inf to a candidate outside that N",
+    ("centroid_codes", "sim", "extent"): "sim defines rows and K unless rows= / K= say otherwise: the count cases cover it",
+    ("ivf_count", "codes", "extent"): "codes defines N and Ld: fewer rows are a smaller corpus",
+    ("ivf_fill", "codes", "extent"): "codes defines N and Ld: fewer rows are a smaller corpus",
+    ("ivf_fill", "docs", "extent"): "the extent written is offsets[K], which lives on the device; the kernel never stores past docs' own length",
+    ("ivf_mark", "offsets", "extent"): "offsets defines K: a shorter table is a smaller codebook, and a probe past it is skipped",
+    ("ivf_mark", "docs", "extent"): "the extent read is offsets[K], which lives on the device; the kernel never reads past docs' own length",
+    ("ivf_compact", "count", "extent"): "count defines B: a shorter count is a smaller legal call",
 }
 
 
@@ -666,7 +1205,17 @@ def _set(name, value):
     return mutate
 
 
-def bad_cases(families=("dtype", "extent", "layout", "count", "device")):
+def _overlapping(a, b):
+    """a and b as the two shifted views buf[1:] and buf[:-1] of one allocation; b keeps its values."""
+    def mutate(p):
+        t = p[b]
+        buf = torch.zeros(t.shape[0] + 1, *t.shape[1:], dtype=t.dtype, device=t.device)
+        buf[:-1].copy_(t)
+        p[b], p[a] = buf[:-1], buf[1:]
+    return mutate
+
+
+def bad_cases(families=("dtype", "extent", "layout", "count", "overlap", "device")):
     out = []
     for key, case in CASES.items():
         good = case.good()
@@ -690,6 +1239,28 @@ def bad_cases(families=("dtype", "extent", "layout", "count", "device")):
         if "count" in families:
             for name, value, names in case.counts:
                 out.append(Bad(key, "count", name, str(value), _set(name, value), names))
+        if "overlap" in families:
+            for a, b in case.overlaps:
+                out.append(Bad(key, "overlap", a, b, _overlapping(a, b), (a, b)))
+    return out
+
+
+def shape_and_engine_dtype_cases():
+    """For the retrieval wrappers, the two mistakes that used to surface from elsewhere (a ValueError from unpacking a
+    shape, `unsupported dtype` from the dtype table): every tensor of two or more dimensions given with one dimension
+    fewer (t[0]), and every f32-or-bf16 tensor given as f16 and as f64.  Refused by name like every other bad call."""
+    out = []
+    for key, case in CASES.items():
+        if op_of(key) not in RETRIEVAL_OPS:
+            continue
+        good = case.good()
+        for path, spec in case.tensors.items():
+            names = (param_of(path),) + spec.blame
+            if get(good, path).dim() >= 2:
+                out.append(Bad(key, "dims", path, "one_fewer", _on(path, lambda t: t[0]), names))
+            if spec.bad in (BF16, F64):
+                for d in (torch.float16, F64):
+                    out.append(Bad(key, "dtype", path, str(d).replace("torch.", ""), _on(path, lambda t, d=d: t.to(d)), names))
     return out
 
 

@@ -1,4 +1,5 @@
-"""CPU: the wrappers of the training step (polus_amd/ops.py, CORE_OPS of tests/ops_contract_cases.py) hand the library what
+"""CPU: the wrappers of the training step and of token retrieval (polus_amd/ops.py, CORE_OPS and RETRIEVAL_OPS of
+tests/ops_contract_cases.py) hand the library what
 the table expects for a legal call and refuse every generated illegal one before any entry point is reached, and the C entry
 points behind them refuse by name what they can see from the host.
 
@@ -37,17 +38,18 @@ def no_device_check(monkeypatch):
 def test_every_public_function_of_ops_is_classified():
     from polus_amd import ops
     public = oc.public_functions(ops)
-    assert not set(oc.CORE_OPS) & set(oc.OTHER_OPS)
-    assert sorted(oc.CORE_OPS + oc.OTHER_OPS) == public, (
-        f"unclassified: {sorted(set(public) - set(oc.CORE_OPS) - set(oc.OTHER_OPS))}, "
-        f"gone: {sorted(set(oc.CORE_OPS + oc.OTHER_OPS) - set(public))}")
-    assert sorted({oc.op_of(k) for k in oc.CASES}) == sorted(oc.CORE_OPS)
+    tabled = oc.CORE_OPS + oc.RETRIEVAL_OPS
+    assert not set(tabled) & set(oc.OTHER_OPS) and not set(oc.CORE_OPS) & set(oc.RETRIEVAL_OPS)
+    assert sorted(tabled + oc.OTHER_OPS) == public, (
+        f"unclassified: {sorted(set(public) - set(tabled) - set(oc.OTHER_OPS))}, "
+        f"gone: {sorted(set(tabled + oc.OTHER_OPS) - set(public))}")
+    assert sorted({oc.op_of(k) for k in oc.CASES}) == sorted(tabled)
 
 
 def test_every_tensor_parameter_has_a_dtype_and_an_extent_case(real_lib):
     from polus_amd import ops
     have = {fam: oc.covered(fam) for fam in ("dtype", "extent")}
-    for op in oc.CORE_OPS:
+    for op in oc.CORE_OPS + oc.RETRIEVAL_OPS:
         keys = [k for k in oc.CASES if oc.op_of(k) == op]
         tensors = {oc.param_of(path) for k in keys for path in oc.CASES[k].tensors}
         for k in keys:
@@ -69,7 +71,7 @@ def test_every_tensor_parameter_has_a_dtype_and_an_extent_case(real_lib):
                 else:
                     assert isinstance(reason, str) and len(reason) > 10, f"{op}.{name}: no {fam} case and no reason in EXEMPT"
     for (op, name, fam), reason in oc.EXEMPT.items():
-        assert op in oc.CORE_OPS and fam in ("dtype", "extent") and isinstance(reason, str) and reason, (op, name, fam)
+        assert op in oc.CORE_OPS + oc.RETRIEVAL_OPS and fam in ("dtype", "extent") and isinstance(reason, str) and reason, (op, name, fam)
 
 
 # ------------------------------------------------------------------------------------------------- good calls
@@ -99,13 +101,39 @@ def test_grouped_problem_table_holds_the_expected_pointers(rec, no_device_check)
 
 
 # ------------------------------------------------------------------------------------------------- bad calls
-BAD = oc.bad_cases(("dtype", "extent", "layout", "count"))
+BAD = oc.bad_cases(("dtype", "extent", "layout", "count", "overlap"))
 
 
 @pytest.mark.parametrize("bad", BAD, ids=[b.id for b in BAD])
 def test_bad_call_is_refused_by_name_before_any_entry_point(bad, rec, no_device_check):
     from polus_amd import ops
     oc.check_refused(ops, bad, bad.args(), rec)
+
+
+SHAPE_DTYPE = oc.shape_and_engine_dtype_cases()
+
+
+@pytest.mark.parametrize("bad", SHAPE_DTYPE, ids=[b.id for b in SHAPE_DTYPE])
+def test_retrieval_wrappers_name_a_wrong_dimension_count_and_a_wrong_engine_dtype(bad, rec, no_device_check):
+    from polus_amd import ops
+    oc.check_refused(ops, bad, bad.args(), rec)
+
+
+def test_one_column_scores_are_legal_in_the_maxsim_wrappers(rec, no_device_check):
+    """A [B, 1] column view of a wider matrix has an inner stride that no kernel ever steps by: legal, as in every
+    other wrapper, and its row stride is what the library is handed."""
+    from polus_amd import ops
+    for key, name in (("maxsim_fwd", "score"), ("maxsim_scores", "score"), ("maxsim_bwd", "dscore")):
+        args = oc.CASES[key].good()
+        one = {"d": lambda t: t[:1], "dmask": lambda t: t[:1], "argmax": lambda t: t[:, :1].contiguous(), "dd": lambda t: t[:1]}   # N = 1
+        args.update({k: cut(args[k]) for k, cut in one.items() if k in args})
+        args[name] = torch.zeros(oc.R_B, 6)[:, ::3][:, :1]                      # [B, 1] with strides (6, 3)
+        assert args[name].stride() == (6, 3)
+        rec.calls.clear()
+        getattr(ops, key)(**args)
+        (fn, got), = rec.calls
+        k = got.index(args[name].data_ptr())
+        assert got[k + 1] == 6 and oc.R_B in got and 1 in got, (key, fn, got)
 
 
 @pytest.mark.parametrize("key", list(oc.CASES))
@@ -119,7 +147,7 @@ def test_host_tensors_are_refused_by_the_real_device_check(key, rec):
 
 def test_every_core_wrapper_states_its_contract():
     from polus_amd import ops
-    for op in oc.CORE_OPS:
+    for op in oc.CORE_OPS + oc.RETRIEVAL_OPS:
         doc = inspect.getdoc(getattr(ops, op))
         assert doc and len(doc) > 40, f"{op} has no docstring stating its contract"
 

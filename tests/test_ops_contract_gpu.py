@@ -14,9 +14,18 @@ import torch
 from oracle import bert as ob
 from oracle import losses as ol
 from tests import attention_cases as ac
+from tests import centroid_ref as cr
+from tests import fp8_ref
+from tests import ivf_ref
 from tests import layer_cases as lc
+from tests import maxsim_cases as mc
+from tests import maxsim_ref as mr
 from tests import ops_contract_cases as oc
+from tests import residual_ref as rr
 from tests import rowwise_cases as rc
+from tests import search_ref as sr
+from tests import tuple_cases as tc
+from tests import tuple_ref as tr
 from tests.fakes import RecordingLib
 from tests.util import TOL, dropout_keep_np, host, relerr
 
@@ -314,6 +323,243 @@ def test_set_dynamic_params(ops):
     finally:
         ops.set_dynamic_params(None)
         torch.cuda.synchronize()
+
+
+# ------------------------------------------------------------------------------------------------- token retrieval
+MS = mc.TOL["f32"]
+
+
+def bits(t):
+    """The int32 bit patterns of an f32 device tensor (or host array)."""
+    a = t.detach().cpu().contiguous().numpy() if torch.is_tensor(t) else np.ascontiguousarray(t, np.float32)
+    return a.view(np.int32)
+
+
+def u16(t):
+    return t.cpu().contiguous().numpy().view(np.uint16)
+
+
+def within(got, want, bound, what):
+    """|got - want| <= bound element by element, the form of the derived bounds of tests/test_centroid_gpu.py."""
+    g = host(got) if torch.is_tensor(got) else np.asarray(got, np.float64)
+    assert np.isfinite(g).all(), f"{what}: not fully written (or not finite)"
+    worst = float((np.abs(g - want) / np.maximum(bound, 1e-300)).max())
+    print(f"[contract] {what}: worst |got - ref| / bound {worst:.3f}")
+    assert (np.abs(g - want) <= bound).all(), f"{what}: {worst:.3f} times the bound"
+
+
+def reranked(score, full, cand, n_docs, what):
+    """score[b, c] has the bits of full[b, cand[b, c]] (a device [B, N] score matrix); -inf for a candidate outside [0, N)."""
+    got, cand = score.cpu().numpy(), cand.numpy()
+    ok = (cand >= 0) & (cand < n_docs)
+    assert ok.any() and (~ok).any()
+    want = full.cpu().numpy()[np.arange(cand.shape[0])[:, None], np.where(ok, cand, 0)]
+    assert np.array_equal(bits(got[ok]), bits(want[ok])), f"{what}: not the bits of the all-pairs scorer"
+    assert np.isneginf(got[~ok]).all(), f"{what}: a candidate outside [0, N) must score -inf"
+    return ok
+
+
+def _ms_arrays(cpu):
+    return f64(cpu["q"]), cpu["qmask"].numpy(), cpu["dmask"].numpy()
+
+
+def _argmax_is_decided(q, d, qm, dm):
+    """Every top-two gap of the case exceeds the rounding of one f32 dot product (tests/maxsim_cases.gap_floor), so the
+    device's argmax must be the reference's."""
+    am = mr.maxsim_fwd(q, d, qm, dm)[1]
+    return mr.top2_gap(q, d, qm, dm)[am >= 0].min() > mc.gap_floor(q, d)
+
+
+def test_maxsim_and_normalisation(ops):
+    cpu, dv = run_good(ops, "maxsim_fwd")
+    (q, qm, dm), d = _ms_arrays(cpu), f64(cpu["d"])
+    s_ref, am_ref = mr.maxsim_fwd(q, d, qm, dm)
+    assert _argmax_is_decided(q, d, qm, dm) and (am_ref < 0).any() and np.unique(am_ref).size > 3
+    close(dv["score"], s_ref, MS["score"], "maxsim_fwd score")
+    assert np.array_equal(dv["argmax"].cpu().numpy(), am_ref), "maxsim_fwd argmax"
+    fwd_score = dv["score"]
+
+    cpu, dv = run_good(ops, "maxsim_scores")
+    close(dv["score"], s_ref, MS["score"], "maxsim_scores score")
+    assert np.array_equal(bits(dv["score"]), bits(fwd_score)), "maxsim_scores must give maxsim_fwd's bits"
+    full = dv["score"]
+
+    cpu, dv = run_good(ops, "maxsim_bwd")
+    assert np.array_equal(cpu["argmax"].numpy(), am_ref)
+    dq_ref, dd_ref = mr.maxsim_bwd(q, d, f64(cpu["dscore"]), am_ref)
+    close(dv["dq"], dq_ref, MS["grad"], "maxsim_bwd dq")
+    close(dv["dd"], dd_ref, MS["grad"], "maxsim_bwd dd")
+
+    cpu, dv = run_good(ops, "maxsim_rerank")
+    reranked(dv["score"], full, cpu["cand"], oc.R_N, "maxsim_rerank")
+
+    cpu, fw = run_good(ops, "l2norm_fwd")
+    x = f64(cpu["x"])
+    y_ref, r_ref = mr.l2norm_fwd(x)
+    close(fw["y"], y_ref, MS["norm"], "l2norm_fwd y")
+    close(fw["rnorm"], r_ref, MS["norm"], "l2norm_fwd rnorm")
+
+    def forward_outputs(args):             # the backward's y and rnorm are what the forward wrote
+        args["y"], args["rnorm"] = fw["y"].contiguous(), fw["rnorm"].contiguous()
+    cpu, dv = run_good(ops, "l2norm_bwd", forward_outputs)
+    close(dv["dx"], mr.l2norm_bwd(x, f64(cpu["dy"])), MS["norm"], "l2norm_bwd dx")
+
+
+def test_fp8_index(ops):
+    cpu, dv = run_good(ops, "fp8_quantize")
+    codes_ref, scale_ref, _ = fp8_ref.quantize(cpu["x"].numpy())
+    assert np.array_equal(dv["codes"].cpu().numpy(), codes_ref), "fp8_quantize codes"
+    assert np.array_equal(bits(dv["scale"]), bits(scale_ref)) and np.unique(scale_ref).size > 3, "fp8_quantize scale"
+
+    cpu, dv = run_good(ops, "fp8_dequantize")
+    assert np.array_equal(cpu["codes"].numpy(), codes_ref)
+    corpus = fp8_ref.dequantize(codes_ref, scale_ref)
+    assert np.array_equal(bits(dv["y"]), bits(corpus)), "fp8_dequantize is exact"
+    corpus_dev = dv["y"].contiguous()
+
+    cpu, dv = run_good(ops, "maxsim_scores_fp8")
+    q, qm, dm = _ms_arrays(cpu)
+    plain = torch.full((oc.R_B, oc.R_N), float("nan"), device="cuda")
+    ops.maxsim_scores(dv["q"], corpus_dev, dv["qmask"], dv["dmask"], plain)
+    assert np.array_equal(bits(dv["score"]), bits(plain)), "maxsim_scores_fp8 must give maxsim_scores' bits over the dequantised corpus"
+    close(dv["score"], mr.maxsim_fwd(q, corpus.astype(np.float64), qm, dm)[0], MS["score"], "maxsim_scores_fp8 score")
+    full = dv["score"]
+
+    cpu, dv = run_good(ops, "maxsim_rerank_fp8")
+    reranked(dv["score"], full, cpu["cand"], oc.R_N, "maxsim_rerank_fp8")
+
+
+def test_residual_index(ops):
+    rows, nb = oc.R_N * oc.R_LD, oc.R_NBITS
+    cpu, dv = run_good(ops, "residual_compress")
+    packed_ref = rr.compress(cpu["x"].numpy().reshape(rows, -1), cpu["codes"].numpy().reshape(rows), cpu["centroids"].numpy(),
+                             cpu["cutoffs"].numpy(), nb)
+    assert np.array_equal(dv["packed"].cpu().numpy().reshape(rows, -1), packed_ref) and np.unique(packed_ref).size > 8, "residual_compress"
+
+    cpu, dv = run_good(ops, "residual_decompress")
+    assert np.array_equal(cpu["packed"].numpy().reshape(rows, -1), packed_ref)
+    corpus = rr.decompress(cpu["codes"].numpy().reshape(rows), packed_ref, cpu["centroids"].numpy(), cpu["weights"].numpy(), nb, "f32")
+    assert np.array_equal(bits(dv["y"]).reshape(rows, -1), bits(corpus)), "residual_decompress is exact"
+    assert (corpus == 0).all(1).sum() == 5, "the rows without a token decompress to zeros"
+    corpus_dev = dv["y"].contiguous()
+
+    cpu, dv = run_good(ops, "maxsim_rerank_res")
+    q, qm, dm = _ms_arrays(cpu)
+    plain = torch.full((oc.R_B, oc.R_C), float("nan"), device="cuda")
+    ops.maxsim_rerank(dv["q"], corpus_dev, dv["qmask"], dv["dmask"], dv["cand"], plain)
+    assert np.array_equal(bits(dv["score"]), bits(plain)), "maxsim_rerank_res must give maxsim_rerank's bits over the decompressed corpus"
+    full = mr.maxsim_fwd(q, corpus.reshape(oc.R_N, oc.R_LD, -1).astype(np.float64), qm, dm)[0]
+    cand = cpu["cand"].numpy()
+    ok = (cand >= 0) & (cand < oc.R_N)
+    got = dv["score"].cpu().numpy()
+    assert np.isneginf(got[~ok]).all() and (~ok).sum() == 2
+    close(got[ok], full[np.arange(oc.R_B)[:, None], np.where(ok, cand, 0)][ok], MS["score"], "maxsim_rerank_res score")
+
+
+def test_topk_merge(ops):
+    cpu, dv = run_good(ops, "topk_merge")
+    scores = cpu["scores"].numpy()
+    val, idx = sr.topk_merge(scores, oc.TOPK_ID0 + np.arange(oc.R_C), oc.R_K, state=(cpu["top_val"].numpy(), cpu["top_id"].numpy()))
+    assert (idx < oc.TOPK_ID0).any() and (idx >= oc.TOPK_ID0).any(), "the merge keeps entries of both the state and the new scores"
+    assert np.array_equal(bits(dv["top_val"]), bits(val)) and np.array_equal(dv["top_id"].cpu().numpy(), idx), "topk_merge"
+    cpu, dv = run_good(ops, "topk_merge:ids")
+    ids = cpu["ids"].numpy()
+    val, idx = sr.topk_merge(np.where(ids >= 0, scores, -np.inf).astype(np.float32), ids, oc.R_K)
+    assert np.array_equal(bits(dv["top_val"]), bits(val)) and np.array_equal(dv["top_id"].cpu().numpy(), idx), "topk_merge with ids"
+
+
+def test_centroids(ops):
+    u = 2.0 ** -24
+    cpu, dv = run_good(ops, "centroid_scores")
+    codes = rr.codes_u16(cpu["codes"].numpy())
+    want, mag = cr.centroid_scores(cpu["table"].numpy(), cpu["qmask"].numpy(), codes, oc.R_B, oc.R_LQ)
+    # the bound of tests/test_centroid_gpu.py: the maxima are exact, only the f32 sum of the Lq terms rounds
+    within(dv["score"], want, 1.01 * (oc.R_LQ - 1) * u * mag, "centroid_scores")
+    full = dv["score"]
+
+    cpu, dv = run_good(ops, "centroid_scores_ids")
+    reranked(dv["score"], full, cpu["cand"], oc.R_N, "centroid_scores_ids")
+
+    cpu, dv = run_good(ops, "centroid_codes")
+    want = cr.centroid_codes(cpu["sim"].numpy(), cpu["mask"].numpy())
+    assert want[4] == 0 and want[5] == cr.NONE and np.unique(want).size > 3
+    assert np.array_equal(u16(dv["codes"]), want), "centroid_codes"
+
+    cpu, dv = run_good(ops, "centroid_update")
+    x, prev, E = f64(cpu["x"]), f64(cpu["prev"]), oc.R_E
+    want, counts, sums, mags = cr.centroid_update(x, u16(cpu["codes"]), prev)
+    assert np.array_equal(dv["counts"].cpu().numpy(), counts) and counts[2] == 0 and counts.sum() == oc.R_T - 1
+    got = host(dv["out"])
+    assert np.array_equal(got[2], prev[2]), "a centroid without rows keeps prev"
+    # the bound of tests/test_centroid_gpu.py (test_update_counts_exact_centroids_within_the_derived_bound), f32
+    live = counts > 0
+    nrm = np.sqrt((sums ** 2).sum(1, keepdims=True))[live]
+    es = 1.01 * (counts[live, None] - 1) * u * mags[live]
+    bound = es / nrm + np.abs(want[live]) * (np.linalg.norm(es, axis=1, keepdims=True) / nrm + 1.01 * (E + 4) * u + u)
+    within(got[live], want[live], bound, "centroid_update out")
+
+
+def test_inverted_lists(ops):
+    counts, offsets, members = ivf_ref.lists(rr.codes_u16(oc._tok_codes().numpy()), oc.R_K)
+    assert offsets[-1] == oc.IVF_PAIRS and [len(m) for m in members] == [2, 2, 1, 1]
+    cpu, dv = run_good(ops, "ivf_count")
+    assert np.array_equal(dv["counts"].cpu().numpy(), counts), "ivf_count"
+    cpu, dv = run_good(ops, "ivf_offsets")
+    assert np.array_equal(dv["offsets"].cpu().numpy(), offsets), "ivf_offsets"
+    cpu, dv = run_good(ops, "ivf_fill")
+    assert ivf_ref.split(offsets, dv["docs"].cpu().numpy()) == members, "ivf_fill: the lists as sorted sets"
+
+    cpu, dv = run_good(ops, "ivf_mark")
+    sets = ivf_ref.candidates(cpu["probes"].numpy().reshape(oc.R_B, oc.R_LQ, oc.R_P), cpu["qmask"].numpy(), members, oc.R_N)
+    assert sets == [{1}, {2}], "the masked tokens' probes and the probe past K add nothing"
+    assert np.array_equal(dv["bitmap"].cpu().numpy().view(np.uint32), ivf_ref.bitmap(sets, oc.R_N)), "ivf_mark"
+
+    cpu, dv = run_good(ops, "ivf_compact")
+    count, cand = ivf_ref.compact(cpu["bitmap"].numpy().view(np.uint32), oc.R_N, cpu["cand"].shape[1])
+    assert count.tolist() == [3, 1] and cand.tolist() == [[0, 1], [1, -1]]
+    assert np.array_equal(dv["count"].cpu().numpy(), count) and np.array_equal(dv["cand"].cpu().numpy(), cand), "ivf_compact"
+
+
+TUPLE_KEYS = (("maxsim_tuples_fwd", "maxsim_tuples_bwd", "dot_tuples_fwd", "dot_tuples_bwd", 0),
+              ("maxsim_tuples_fwd:query_major", "maxsim_tuples_bwd:query_major", "dot_tuples_fwd:query_major",
+               "dot_tuples_bwd:query_major", 1))
+
+
+def test_tuples_and_distillation(ops):
+    seen = []
+    for k_fwd, k_bwd, k_dot, k_dot_bwd, layout in TUPLE_KEYS:
+        what = f"layout {layout}"
+        cpu, dv = run_good(ops, k_fwd)
+        assert cpu["layout"] == layout
+        (q, qm, dm), d = _ms_arrays(cpu), f64(cpu["d"])
+        s_ref, am_ref = tr.maxsim_tuples_fwd(q, d, qm, dm, layout)
+        assert _argmax_is_decided(q, d, qm, dm)
+        close(dv["score"], s_ref, MS["score"], f"maxsim_tuples_fwd {what} score")
+        assert np.array_equal(dv["argmax"].cpu().numpy(), am_ref), f"maxsim_tuples_fwd {what} argmax"
+        seen.append(s_ref)
+
+        cpu, dv = run_good(ops, k_bwd)
+        assert np.array_equal(cpu["argmax"].numpy(), am_ref)
+        dq_ref, dd_ref = tr.maxsim_tuples_bwd(q, d, f64(cpu["dscore"]), am_ref, layout)
+        close(dv["dq"], dq_ref, MS["grad"], f"maxsim_tuples_bwd {what} dq")
+        close(dv["dd"], dd_ref, MS["grad"], f"maxsim_tuples_bwd {what} dd")
+
+        tol = tc.TOL["dot_f32"]
+        cpu, dv = run_good(ops, k_dot)
+        q, d = f64(cpu["q"]), f64(cpu["d"])
+        close(dv["score"], tr.dot_tuples_fwd(q, d, layout), tol["score"], f"dot_tuples_fwd {what} score")
+        cpu, dv = run_good(ops, k_dot_bwd)
+        dq_ref, dd_ref = tr.dot_tuples_bwd(q, d, f64(cpu["dscore"]), layout)
+        close(dv["dq"], dq_ref, tol["grad"], f"dot_tuples_bwd {what} dq")
+        close(dv["dd"], dd_ref, tol["grad"], f"dot_tuples_bwd {what} dd")
+    assert not np.allclose(seen[0], seen[1]), "the two layouts pair queries and documents differently"
+
+    for key, kind, ref in (("distill_kl", "kl", tr.distill_kl), ("margin_mse", "mse", tr.margin_mse)):
+        cpu, dv = run_good(ops, key)
+        loss_ref, g_ref = ref(f64(cpu["student"]), f64(cpu["teacher"]))
+        close(dv["loss"], [loss_ref], tc.TOL[kind]["loss"], f"{key} loss")
+        close(dv["dstudent"], g_ref, tc.TOL[kind]["grad"], f"{key} dstudent")
+        assert (dv["dstudent"].cpu().numpy()[np.isneginf(cpu["teacher"].numpy())] == 0).all(), f"{key}: an absent column gets zero gradient"
 
 
 def test_every_good_case_runs_on_the_device():
