@@ -1090,6 +1090,55 @@ int polus_ivfpq_residual(int dtype, const void* x, long ldx, const void* cent, c
 int polus_ivfpq_coarse_update(int dtype, const void* x, long ldx, const uint16_t* coarse, const void* prev, void* out,
                               int32_t* counts, int T, int K, int E, void* stream);
 
+/* ---- refine: exact re-scoring of per-query candidate ids against stored single ([CLS]) vectors (refine.hip; the second
+ * stage of FAISS' IndexRefine and of ScaNN's reordering, and the bi-encoder rerank behind a lexical first stage; no
+ * counterpart in the reference).  A compressed index proposes R > k candidates, this kernel scores those R against better
+ * vectors, polus_topk_merge_ids keeps the best k.
+ *
+ * polus_cls_rerank:  Q [B, E] in `dtype` (f32 or bf16), row stride ldq >= E;  D [N, E] in `dtype`, row stride ldd >= E;
+ *   cand int32 [B, C], row stride ldcand >= C;  score f32 [B, C], row stride lds >= C
+ *   n           = cand[b, c]
+ *   score[b, c] = <Q[b], D[n]> by the rule below          for n in [0, N)
+ *               = -inf, and nothing is read for it          for n outside [0, N)   (-inf is what polus_topk_merge_ids drops;
+ *                                                           the contract of polus_maxsim_rerank and polus_ivfpq_scores_ids)
+ *   Columns past C are not written.  A repeated id is scored once per copy.  Document addresses are 64-bit.  Q and D may
+ *   hold NaN and +-inf; they propagate by IEEE rules.  No atomics, no workspace, no LDS; bitwise reproducible.
+ * Arithmetic.  bf16 is widened to f32 (exact).  Every f32 operation is one IEEE rounding, never an fma, so NumPy float32
+ *   reproduces every bit (tests/refine_ref.py).  The order is a function of E alone: the features are taken in groups of 8
+ *   consecutive ones; partial l = 0 .. 63 adds, from +0.0 and in ascending e, fl(q_e * d_e) for every e with
+ *   (e div 8) mod 64 == l; then six rounds p_l = fl(p_l + p_(l xor o)) for o = 32, 16, 8, 4, 2, 1 (the xor order of
+ *   polus_pq_update); the score is p_0.  The bits of a score depend on its (query, document) pair only: not on B, C, the
+ *   column it stands in, ldcand, the chunking of a search, or how many candidates a wave or a workgroup handles.
+ * polus_cls_rerank_fp8:  the same call with codes uint8 [N, E] (OCP e4m3fn, row stride ldd >= E) and scale f32 [N] in place
+ *   of D; Q stays in `dtype`.  The sum runs over fl(f32(q_e) * f32(code_e)) in the same order, then
+ *   score = fl(scale[n] * sum), one more rounding.  A power-of-two scale commutes with every rounding, so
+ *     polus_cls_rerank_fp8(Q, codes, scale) is bit for bit polus_cls_rerank(Q, D) with D = T(codes) * scale,
+ *   provided no product or partial sum under- or overflows f32 (scales of a unit-norm or N(0,1) corpus are ~2^-8).  All
+ *   quantisation error therefore sits in polus_cls_fp8_quantize.
+ * Kernel.  One workgroup of 4 waves per (query, contiguous range of candidate columns); a wave owns a candidate, so its id
+ *   is wave-uniform.  Lane l holds the query's groups l, l + 64, ... in registers for the whole launch and reads the same
+ *   groups of a row, 16 bytes (bf16), 32 (f32) or 8 (codes) at a time; the rows of a wave's next candidates are requested
+ *   before the current ones are reduced (8 rows in flight per wave at E <= 1024, 4 up to 2048, 2 above).  The cross-lane
+ *   rounds use DPP, swizzles and one bpermute.  The column range of a workgroup follows B * C and the CU count of the
+ *   current device (about 16 waves per CU over the launch, 1 .. 64 columns a wave), so one query with 1000 candidates
+ *   still occupies 250 workgroups.  A gather of whole rows: bound by memory latency, not by arithmetic.
+ * Limits (refused before any launch): dtype f32 or bf16; E a multiple of 16 in [16, 5120]; 1 <= B, C <= 65535;
+ *   1 <= N <= 2^31 - 1; ldq, ldd >= E; ldcand, lds >= C; non-null pointers; Q and D / codes 16-byte aligned, and row strides
+ *   that keep every row 16-byte aligned (ldq and ldd multiples of 4 in f32, of 8 in bf16; ldd a multiple of 16 for codes).
+ *
+ * polus_cls_fp8_quantize / polus_cls_fp8_dequantize:  the quantiser of polus_fp8_quantize_rows, word for word (the integer
+ *   rule for the exponent, one power-of-two scale per row, nothing saturates, a NaN element ignored by amax and kept as a
+ *   NaN code, a zero row with e = 0; the same device code, csrc/fp8_common.h), over whole rows:  x, y [rows, E] in
+ *   `dtype`, contiguous;  codes uint8 [rows, E], contiguous;  scale f32 [rows].  One wave per row, two passes over it.
+ *   Limits (refused before any launch): dtype f32 or bf16; rows >= 1; E a multiple of 16 in [16, 5120]; non-null
+ *   pointers; x / y and codes 16-byte aligned. */
+int polus_cls_rerank(int dtype, const void* Q, long ldq, const void* D, long ldd, const int32_t* cand, long ldcand,
+                     float* score, long lds, int B, int C, int N, int E, void* stream);
+int polus_cls_rerank_fp8(int dtype, const void* Q, long ldq, const uint8_t* codes, long ldd, const float* scale,
+                         const int32_t* cand, long ldcand, float* score, long lds, int B, int C, int N, int E, void* stream);
+int polus_cls_fp8_quantize(int dtype, const void* x, uint8_t* codes, float* scale, int rows, int E, void* stream);
+int polus_cls_fp8_dequantize(int dtype, const uint8_t* codes, const float* scale, void* y, int rows, int E, void* stream);
+
 /* ---- argmax over the last axis (PolusClassifier.inference, polus/models.py:148-150) */
 int polus_argmax(const float* x, long ldx, int32_t* out, int rows, int C, void* stream);
 

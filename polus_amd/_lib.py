@@ -132,6 +132,10 @@ SIGNATURES = {
     "polus_ivfpq_scores_ids_route": (_i, [_i, _i, _i, _i, _c.POINTER(_i)]),
     "polus_ivfpq_residual": (_i, [_i, _vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _vp]),
     "polus_ivfpq_coarse_update": (_i, [_i, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "polus_cls_rerank": (_i, [_i, _vp, _l, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i, _vp]),
+    "polus_cls_rerank_fp8": (_i, [_i, _vp, _l, _vp, _l, _vp, _vp, _l, _vp, _l, _i, _i, _i, _i, _vp]),
+    "polus_cls_fp8_quantize": (_i, [_i, _vp, _vp, _vp, _i, _i, _vp]),
+    "polus_cls_fp8_dequantize": (_i, [_i, _vp, _vp, _vp, _i, _i, _vp]),
     "polus_argmax": (_i, [_vp, _l, _vp, _i, _i, _vp]),
     "polus_adam_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i64,
                              _f, _f, _f, _f, _f, _f, _f, _vp, _vp]),

@@ -13,11 +13,9 @@
 //   polus_maxsim_rerank_fp8(...)             == polus_maxsim_scores_fp8 of each pair        in bits
 // and the quantiser below holds all of the error.
 #include "maxsim_common.h"
+#include "fp8_common.h"
 
 namespace {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-constexpr int F8_EMIN = -100;           // lowest scale exponent
 
 // 8 e4m3fn bytes (k ascending from the low byte of raw.x) -> one MFMA fragment of T; exact
 __device__ __forceinline__ void f8_to_f32(float (&v)[8], uint2 raw) {
@@ -49,18 +47,10 @@ __global__ __launch_bounds__(256) void fp8_quantize_kernel(const T* __restrict__
     float v[4] = {0.f, 0.f, 0.f, 0.f};
     if (on) load4<T>(x + (size_t)row * E + e0, v);
     const float amax = wave_max(fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
-    // amax = m 2^k, m in [0.5, 1): k = (exponent field) - 126, m > 0.875 where the fraction passes 1.75.  A subnormal
-    // amax (field 0) lands below the clamp like every amax < 2^-91.
-    const unsigned bits = __float_as_uint(amax);
-    int e = (int)(bits >> 23) - 126 - 9 + ((bits & 0x7fffffu) > 0x600000u ? 1 : 0);
-    e = max(e, F8_EMIN);
-    if (amax == 0.f) e = 0;
-    const float inv = __uint_as_float((unsigned)(127 - e) << 23);       // 2^-e: the products are exact
-    int w = 0;
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(v[0] * inv, v[1] * inv, w, false);
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(v[2] * inv, v[3] * inv, w, true);
+    const int e = f8_row_exponent(amax);
+    const int w = f8_pack4(v, f8_pow2(-e));
     if (on) *reinterpret_cast<int*>(codes + (size_t)row * E + e0) = w;
-    if (lane == 0) scale[row] = __uint_as_float((unsigned)(e + 127) << 23);
+    if (lane == 0) scale[row] = f8_pow2(e);
 }
 
 template <typename T>
@@ -73,9 +63,8 @@ __global__ __launch_bounds__(256) void fp8_dequantize_kernel(const unsigned char
     const int e0 = 4 * lane;
     if (e0 >= E) return;
     const int w = *reinterpret_cast<const int*>(codes + (size_t)row * E + e0);
-    const float s = scale[row];
-    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8(w, false), b = __builtin_amdgcn_cvt_pk_f32_fp8(w, true);
-    const float v[4] = {a[0] * s, a[1] * s, b[0] * s, b[1] * s};
+    float v[4];
+    f8_unpack4(w, scale[row], v);
     store4<T>(y + (size_t)row * E + e0, v);
 }
 

@@ -12,6 +12,7 @@ Bit-for-bit the same training run as the eager path (tests/test_boundary_gpu.py:
 Limits: one process (no data parallelism inside the capture), static batch shape, a model whose dropout
 seeds come from `site_seed` (BertModel / TFBertSplited), a fused polus_amd optimizer, no gradient accumulation,
 no post_process_grads that runs host code per step."""
+import gc
 import math
 import struct
 
@@ -131,11 +132,20 @@ class GraphedStep:
         it, ds, mc = opt.iterations, model.dropout_step, getattr(tr, "step_counter_micro", 0)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
+        # No garbage collection inside the capture: a dead cycle of an earlier trainer may own device memory, events or a
+        # captured graph, and freeing those makes runtime calls that a capturing stream forbids (the process aborts in the
+        # destructor).  torch.cuda.graph collected on entry once and no longer does, so collect here, then keep the collector
+        # off until the capture has ended.
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
         try:
             with torch.cuda.graph(g):
                 with _lib.pinned_stream():
                     loss = tr._train_step(*self.static_in)
         finally:
+            if gc_was_on:
+                gc.enable()
             ops.WORKSPACE_OVERRIDE = None
             ops.set_dynamic_params(None)
             model.graph_seeds = False

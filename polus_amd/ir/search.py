@@ -87,6 +87,24 @@ with nprobe = K the result is the exhaustive one, bit for bit.  What is approxim
 scored.  Because `search(queries, k)` falls back to the index's own `nprobe`, TwoStageSearch, HybridSearch and
 mine_negatives get a probed first stage unchanged.  Recall on a real collection has not been measured.
 
+A [CLS] index can keep a refine store, the vectors an exact second look scores (FAISS' IndexRefine, ScaNN's reordering):
+
+    plain = CorpusIndex(model, compute_scores, post_process_logits, refine="full")     # its own vectors, nothing copied
+    scores, ids = plain.rerank(queries, candidates, k=100)                             # e.g. TwoStageSearch(bm25, plain, 1000)
+    small = CorpusIndex(model, compute_scores, post_process_logits, storage="ivfpq", codec=codec, nprobe=16, refine="fp8")
+    scores, ids = small.search(queries, k=100, candidates=400)                         # first stage for 400, re-scored, best 100
+
+`rerank` scores each query against its own candidate ids with ops.cls_rerank (refine="full": the projected, post-processed
+vectors in the model's dtype, beside PQ or IVF-PQ codes a second field of 2 E bytes in bf16) or ops.cls_rerank_fp8 ("fp8":
+e4m3fn codes and one power-of-two scale per document, E + 4 bytes, quantised in `add` by ops.cls_fp8_quantize).  The sum's
+order is a function of E alone (include/polus_hip.h "refine"), so a score's bits depend on its (query, document) pair only,
+and the fp8 score is bit for bit the full score over the dequantised vectors.  The contract of `search` on a PQ or IVF-PQ
+index with a refine store: every returned score is the refine rule's score of its document, with the bits `rerank` gives
+that pair, in `rerank`'s order (score descending, ties to the lower id); WHICH documents are considered is approximate, the
+first stage's best R = `candidates` under its look-up scores; under "fp8" all remaining score error is the quantiser's.
+`search(..., candidates=...)` on an index without a refine store is an error, and an index built without `refine` behaves
+bit for bit as before.  Recall against the exact search has not been measured on any real collection.
+
 A learned sparse (SPLADE) first stage is a SparseCorpusIndex: per document its best (term id, weight) pairs, dense
 queries, every document scored for every query (ops.sparse_scores).  With `postings=True` it searches block-inverted
 postings instead (polus_amd/ir/postings.py has the format and the score rule): the dense queries become lists of their
@@ -100,7 +118,8 @@ As in ir/training.py, arithmetic is hand-written HIP (ops.gemm / ops.maxsim_scor
 ops.l2norm_fwd, ops.topk_merge, ops.centroid_scores / centroid_scores_ids / centroid_codes / centroid_update,
 ops.ivf_count / ivf_offsets / ivf_fill / ivf_mark / ivf_compact, ops.residual_compress /
 residual_decompress / maxsim_rerank_res, ops.pq_encode / pq_update / pq_decode / pq_lut / pq_scores,
-ops.ivfpq_residual / ivfpq_coarse_update / ivfpq_scores_ids); torch allocates, views and copies.  Data parallelism: every rank holds the whole
+ops.ivfpq_residual / ivfpq_coarse_update / ivfpq_scores_ids, ops.cls_rerank / cls_rerank_fp8 / cls_fp8_quantize /
+cls_fp8_dequantize); torch allocates, views and copies.  Data parallelism: every rank holds the whole
 index and searches its own shard of the queries; ValidationDataCallback gathers the predictions."""
 import numpy as np
 import torch
@@ -207,6 +226,8 @@ class _ClsVectors:
         st = self.store
         if not st.fields:
             st.declare(**self.fields(v))       # fill 0: the padding of documents shorter than the index's length is never written
+            if self.ix._refine is not None:
+                st.declare(**self.ix._refine.fields(v))
         st.reserve(st.n + v.shape[0], v.device)
         self.dtype = v.dtype
         return st.n, st.n + v.shape[0]
@@ -303,6 +324,66 @@ class _IvfPqVectors(_PqVectors):
             return res.to(self.dtype)
         ops.pq_decode(codes, self.cb, res)
         return (self.ix._centroids[coarse.to(torch.int64) & 0xFFFF].float() + res).to(self.dtype)
+
+
+class _FullRefine:
+    """The refine store of a [CLS] index in the model's dtype: the vectors `add` projected and post-processed, [N, E], which
+    `rerank` scores with ops.cls_rerank.  On a plain index they ARE the stored vectors (field "reps": no second copy); beside
+    PQ or IVF-PQ codes they are a field of their own, "rvec"."""
+
+    def __init__(self, ix):
+        self.ix, self.store, self.field = ix, ix._store, "reps" if ix.storage is None else "rvec"
+
+    @staticmethod
+    def check_width(E):
+        if E % 16 or not 16 <= E <= 5120:
+            raise ValueError(f"a refine store holds vectors of a multiple of 16 features in [16, 5120], the rows ops.cls_rerank "
+                             f"reads in 16-byte pieces (got E = {E})")
+
+    def fields(self, v):
+        self.check_width(v.shape[1])
+        return {} if self.field == "reps" else dict(rvec=((v.shape[1],), v.dtype, 0))
+
+    def write(self, a, b, v):
+        if self.field != "reps":
+            self.store.bufs["rvec"][a:b].copy_(v)
+
+    def reranker(self, q, cand):
+        d = self.store.view(self.field)
+        return lambda a, b, s: ops.cls_rerank(q, d, cand[:, a:b], s)
+
+    def vectors(self, dtype):
+        return self.store.view(self.field)
+
+    codes = scales = property(lambda self: None)
+
+
+class _Fp8Refine(_FullRefine):
+    """The refine store as e4m3fn codes uint8 [N, E] ("rcodes") and one power-of-two scale f32 [N] ("rscale") per document,
+    quantised by ops.cls_fp8_quantize in `add` and scored as they are by ops.cls_rerank_fp8."""
+
+    def fields(self, v):
+        self.check_width(v.shape[1])
+        return dict(rcodes=((v.shape[1],), torch.uint8, 0), rscale=((), torch.float32, 0))
+
+    def write(self, a, b, v):
+        ops.cls_fp8_quantize(v.contiguous(), self.store.bufs["rcodes"][a:b], self.store.bufs["rscale"][a:b])
+
+    def reranker(self, q, cand):
+        codes, scale = self.store.view("rcodes"), self.store.view("rscale")
+        return lambda a, b, s: ops.cls_rerank_fp8(q, codes, scale, cand[:, a:b], s)
+
+    def vectors(self, dtype):
+        codes = self.store.view("rcodes")
+        if codes is None:
+            return None
+        y = torch.empty(codes.shape, dtype=dtype, device=codes.device)
+        if codes.shape[0]:
+            ops.cls_fp8_dequantize(codes, self.store.view("rscale"), y)
+        return y
+
+    codes = property(lambda self: self.store.view("rcodes"))
+    scales = property(lambda self: self.store.view("rscale"))
 
 
 class _Tokens(_ClsVectors):
@@ -462,10 +543,17 @@ class CorpusIndex:
     `codec`, a PQCodec, polus_pq_encode; `search` scores them by table look-ups, at most 65535 queries a call) or "ivfpq"
     ([CLS] representations only: per document the coarse code int16 and the m bytes of its residual under `codec`, an
     IVFPQCodec; `nprobe`, which only this storage takes, is the number of lists `search` probes when the call names
-    none: None scores every document)."""
+    none: None scores every document).
+
+    `refine` gives a [CLS] index a refine store, the vectors `rerank` scores exactly (ops.cls_rerank): "full" keeps the
+    projected, post-processed vectors in the model's dtype (on storage=None they are the stored vectors themselves, nothing
+    is copied; beside PQ or IVF-PQ codes 2 E or 4 E more bytes per document), "fp8" keeps them as e4m3fn codes with one
+    power-of-two scale per document (E + 4 bytes; PQ and IVF-PQ only: a plain index searches exactly already).  On a PQ or
+    IVF-PQ index `search` then asks its first stage for `candidates` documents per query (1 .. 1024; None: min(4 k, 1024)),
+    re-scores them and returns the best k.  E must be a multiple of 16."""
 
     def __init__(self, model, compute_scores, post_process_logits=None, scratch_bytes=256 << 20, storage=None, codec=None,
-                 nprobe=None):
+                 nprobe=None, refine=None, candidates=None):
         if storage not in (None, "fp8", "residual", "pq", "ivfpq"):
             raise ValueError(f"storage must be None or 'fp8' or 'residual' or 'pq' or 'ivfpq' (got {storage!r})")
         want = {"residual": ResidualCodec, "pq": PQCodec, "ivfpq": IVFPQCodec}.get(storage)
@@ -481,7 +569,24 @@ class CorpusIndex:
         if nprobe is not None and storage != "ivfpq":
             raise ValueError(f"nprobe belongs to storage='ivfpq', whose search probes lists (got storage={storage!r}); a "
                              "token index takes it per call, search_pruned(..., nprobe)")
-        self.storage, self.codec = storage, codec
+        if refine not in (None, "full", "fp8"):
+            raise ValueError(f"refine must be None or 'full' or 'fp8' (got {refine!r})")
+        if refine is not None and storage in ("fp8", "residual"):
+            raise ValueError(f"refine belongs to a [CLS] index (storage=None, 'pq' or 'ivfpq'); storage={storage!r} holds token "
+                             "representations, which rerank scores by MaxSim as they are")
+        if refine == "fp8" and storage is None:
+            raise ValueError("refine='fp8' belongs to storage='pq' or 'ivfpq': a plain [CLS] index searches its own vectors "
+                             "exactly, and refine='full' lets it rerank them without a second copy")
+        if refine is not None and codec is not None:
+            _FullRefine.check_width(codec.E)
+        if candidates is not None:
+            if refine is None or storage is None:
+                raise ValueError("candidates belongs to a storage='pq' or 'ivfpq' index with a refine store (refine='full' or "
+                                 f"'fp8'), whose search re-scores that many first-stage results (got refine={refine!r}, "
+                                 f"storage={storage!r})")
+            self._check_candidates(candidates)
+        self.storage, self.codec, self.refine = storage, codec, refine
+        self.candidates = None if candidates is None else int(candidates)
         self.nprobe = None if nprobe is None else self._check_nprobe(nprobe, codec.K)
         self.model, self.compute_scores = model, compute_scores
         self.post_process_logits = post_process_logits
@@ -494,6 +599,7 @@ class CorpusIndex:
         """Empty the index (the storage is released; the next `add` fixes the document length again).  A residual
         index keeps its codec."""
         self._store = RowStore()
+        self._refine = {"full": _FullRefine, "fp8": _Fp8Refine}[self.refine](self) if self.refine else None
         self._kind = {"fp8": _Fp8Tokens, "residual": _ResidualTokens, "pq": _PqVectors, "ivfpq": _IvfPqVectors}[self.storage](self) if self.storage else None
         self._centroids = None                        # [K, E]; the codes are the store's int16 [cap, Ld] field
         self._cutoffs = self._weights = None          # a residual index: the codec's tables on the device
@@ -527,6 +633,23 @@ class CorpusIndex:
         return self._store.view("coarse")
 
     @property
+    def refine_vectors(self):
+        """[N, E] in the index's dtype: the vectors `rerank` scores (an index with a refine store; None otherwise, and before
+        the first add).  Under refine="full" a view (on a plain index the stored vectors themselves); under "fp8" a COPY,
+        the codes dequantised (exactly codes * scales), as `representations` is on an FP8 token index."""
+        return None if self._refine is None or self._reps is None else self._refine.vectors(self._kind.dtype)
+
+    @property
+    def refine_codes(self):
+        """uint8 [N, E]: a view of the refine store's e4m3fn codes (refine="fp8"; None otherwise)."""
+        return None if self._refine is None else self._refine.codes
+
+    @property
+    def refine_scales(self):
+        """f32 [N]: a view of the refine store's per-document scales, exact powers of two (refine="fp8"; None otherwise)."""
+        return None if self._refine is None else self._refine.scales
+
+    @property
     def residuals(self):
         """uint8 [N, Ld, E * nbits / 8]: a view of the stored residual bits (a residual index; None otherwise)."""
         return None if self.storage != "residual" else self._store.view("reps")
@@ -558,7 +681,8 @@ class CorpusIndex:
     @property
     def nbytes(self):
         """Bytes of the stored representations, scales, mask and centroid codes of the len(index) documents, and of
-        the inverted lists once a probed search has built them (4 (K + 1) + 4 P; an IVF-PQ index: N (m + 2), and P = N)."""
+        the inverted lists once a probed search has built them (4 (K + 1) + 4 P; an IVF-PQ index: N (m + 2), and P = N).  A
+        refine store beside PQ or IVF-PQ codes counts: N E element sizes under "full", N (E + 4) under "fp8"."""
         return sum(t[:self._n].numel() * t.element_size() for t in self._store.bufs.values()) + sum(
             t.numel() * t.element_size() for t in self._lists or ())
 
@@ -579,6 +703,9 @@ class CorpusIndex:
                              "to the scorer (MaxSimScores(normalize=True))")
         if self.tokens is not None and tokens != self.tokens:
             raise ValueError("the index holds " + ("token" if self.tokens else "[CLS]") + " representations")
+        if tokens and self.refine is not None:
+            raise ValueError("refine belongs to a [CLS] index: token representations are what rerank scores by MaxSim, they "
+                             "need no refine store")
         if self.storage in ("pq", "ivfpq"):
             if tokens:
                 raise ValueError(f"storage={self.storage!r} holds single ([CLS]) vectors only: product quantisation is for "
@@ -595,7 +722,8 @@ class CorpusIndex:
         residual index gives them their nearest centroid of the codec and compresses them; a PQ index stores the codes
         of the projected (and post-processed) vectors; an IVF-PQ index gives them their L2-nearest coarse centroid
         (ops.gemm with the bias -|c|^2 / 2, then ops.centroid_codes), takes the residual (ops.ivfpq_residual) and stores
-        its codes (ops.pq_encode)."""
+        its codes (ops.pq_encode).  A PQ or IVF-PQ index with a refine store also keeps the projected (and post-processed)
+        vector itself, as it is ("full") or quantised by ops.cls_fp8_quantize ("fp8")."""
         model = self.model
         rep = model.document_projection(model.encode_document(documents, training=False), training=False)
         if self._check_kind(rep):
@@ -614,6 +742,8 @@ class CorpusIndex:
         if self._kind is None:
             self._kind = (_Tokens if self.tokens else _ClsVectors)(self)
         self._kind.write(v, m)
+        if self._refine is not None:
+            self._refine.write(self._n, self._n + v.shape[0], v)
         ids = torch.arange(self._n, self._n + v.shape[0], dtype=torch.int32, device=v.device)
         self._n += v.shape[0]
         self._lists_stale = True
@@ -635,25 +765,49 @@ class CorpusIndex:
             return TokenReps(self._l2norm(v) if self.normalize else v, q.mask.contiguous())
         return (q if self.post_process_logits is None else self.post_process_logits(q)).contiguous()
 
-    def search(self, queries, k, nprobe=None):
+    def _check_candidates(self, candidates, k=1):
+        if not int(k) <= int(candidates) <= MAX_K:
+            raise ValueError(f"need {'1' if k == 1 else f'k = {k}'} <= candidates <= {MAX_K}, the limit of ops.topk_merge, which keeps "
+                             f"the first stage's results (got {candidates})")
+        return int(candidates)
+
+    def search(self, queries, k, nprobe=None, candidates=None):
         """(scores f32 [Q, k], ids int32 [Q, k]) on the device: per query the k best documents, score descending, ties
         to the lower id; when the corpus holds fewer than k, the tail is (-inf, -1).
 
         `nprobe` (an IVF-PQ index only; None: the index's own `nprobe`): 1 <= nprobe <= min(K, 1024) scores only the
         documents in the lists of each query's nprobe best centroids by dot product (ties to the lower centroid), with the
         bits the exhaustive scan gives them; with fewer than k such documents the tail is (-inf, -1).  Both unset: every
-        document is scored."""
+        document is scored.
+
+        A PQ or IVF-PQ index with a refine store runs that search, exhaustive or probed, for R = `candidates` (None: the
+        index's own `candidates`, else min(4 k, 1024); k <= R <= 1024) results per query, re-scores those R documents
+        against the refine store (`rerank`'s path, the queries encoded once) and returns the best k: every score is the
+        refine rule's, with the bits `rerank` gives that pair; which documents were considered is the first stage's choice.
+        `candidates` on any other index raises."""
         if nprobe is not None and self.storage != "ivfpq":
             raise ValueError(f"nprobe belongs to storage='ivfpq' (got storage={self.storage!r}); a token index takes it "
                              "in search_pruned(..., nprobe)")
+        refined = self._refine is not None and self.storage is not None
+        if candidates is not None and not refined:
+            raise ValueError("candidates belongs to the search of a storage='pq' or 'ivfpq' index with a refine store "
+                             f"(got refine={self.refine!r}, storage={self.storage!r}); a token index takes it in search_pruned")
         if self._n == 0:
             raise ValueError("the index is empty: add documents before searching")
+        first = k
+        if refined:
+            R = candidates if candidates is not None else self.candidates
+            first = self._check_candidates(min(4 * int(k), MAX_K) if R is None else R, int(k))
         nprobe = self.nprobe if nprobe is None else nprobe
         if nprobe is not None:
-            return self._search_probed(queries, k, self._check_nprobe(nprobe))
+            nprobe = self._check_nprobe(nprobe)
         q = self.encode_queries(queries)
-        qv = q.values if self.tokens else q
-        return topk_scan(qv.shape[0], k, self.chunks(qv.shape[0], decode=True), qv.device, self._kind.scorer(q))
+        if nprobe is not None:
+            top = self._search_probed(q, first, nprobe)
+        else:
+            qv = q.values if self.tokens else q
+            top = topk_scan(qv.shape[0], first, self.chunks(qv.shape[0], decode=True), qv.device, self._kind.scorer(q))
+        return self._rerank_encoded(q, top[1], k) if refined else top
 
     def rerank_chunks(self, Q, C):
         """[(start, stop), ...]: the candidate columns one rerank launch scores: at most 65535, and at most as many as
@@ -661,7 +815,8 @@ class CorpusIndex:
         return score_chunks(C, Q, self.scratch_bytes, "candidate")
 
     def rerank(self, queries, candidates, k):
-        """Score every query against its own candidates only (a token index): (scores f32 [Q, k], ids int32 [Q, k]) on
+        """Score every query against its own candidates only (a token index: MaxSim; a [CLS] index with a refine store:
+        the dot product with the refine vectors, ops.cls_rerank / cls_rerank_fp8): (scores f32 [Q, k], ids int32 [Q, k]) on
         the device, the contract of `search` over the documents named in the query's row of `candidates`.
 
         `candidates` is an integer [Q, C] array of document ids, padded with -1 anywhere in a row.  A host array is
@@ -672,16 +827,19 @@ class CorpusIndex:
         copies return is not defined (ops.topk_merge).  A row without a candidate returns (-inf, -1)."""
         if self._n == 0:
             raise ValueError("the index is empty: add documents before re-ranking")
-        if not self.tokens:
-            raise ValueError("rerank scores token representations (MaxSim); the index holds [CLS] representations, "
-                             "whose search is already one GEMM")
+        if not self.tokens and self._refine is None:
+            raise ValueError("rerank scores token representations (MaxSim) or the refine store of a [CLS] index; the index "
+                             "holds [CLS] representations without one, whose search is already one GEMM: build it with "
+                             "refine='full' (or, on storage='pq' / 'ivfpq', refine='fp8') to rerank candidates")
         return self._rerank_encoded(self.encode_queries(queries), candidates, k)
 
     def _rerank_encoded(self, q, candidates, k):
-        """`rerank` behind the query encoder: q is encode_queries' TokenReps."""
-        Q, dev = q.values.shape[0], q.values.device
+        """`rerank` behind the query encoder: q is what encode_queries returns, TokenReps or [CLS] vectors [Q, E]."""
+        qv = q.values if self.tokens else q
+        Q, dev = qv.shape[0], qv.device
         cand = check_candidates(candidates, Q, self._n, dev)
-        return topk_scan(Q, k, self.rerank_chunks(Q, cand.shape[1]), dev, self._kind.reranker(q, cand), ids=cand)
+        rr = (self._kind if self.tokens else self._refine).reranker(q, cand)
+        return topk_scan(Q, k, self.rerank_chunks(Q, cand.shape[1]), dev, rr, ids=cand)
 
     # ------------------------------------------------------------ centroid-pruned search
     def _check_centroid_support(self):
@@ -1079,15 +1237,14 @@ class CorpusIndex:
                       top=(top[0][a:b], top[1][a:b]))
             a = b
 
-    def _search_probed(self, queries, k, nprobe):
-        """`search` of an IVF-PQ index under `nprobe`: one GEMM gives every query's dot products with the centroids, which
+    def _search_probed(self, q, k, nprobe):
+        """`search` of an IVF-PQ index under `nprobe` for encoded queries q [Q, E]: one GEMM gives every query's dot products with the centroids, which
         are both the probe ranking (ops.topk_merge: descending, ties to the lower centroid) and the centroid term of the
         scores; the probed lists become a bitmap and ascending candidate ids (_mark, _scan_probed), scored by
         ops.ivfpq_scores_ids."""
         if not 1 <= int(k) <= MAX_K:
             raise ValueError(f"need 1 <= k <= {MAX_K}, the limit of ops.topk_merge (got {k})")
         self._fresh_lists()
-        q = self.encode_queries(queries)
         Q, dev = q.shape[0], q.device
         lut, cdot = self._kind.tables(q)
         probes = torch.empty((Q, nprobe), dtype=torch.int32, device=dev)
@@ -1248,10 +1405,11 @@ class SparseCorpusIndex:
 
 
 class TwoStageSearch:
-    """Retrieve with a cheap index, re-rank with the token index: `first` is anything with search(queries, k) ->
-    (scores, ids) and add(documents), in practice a [CLS] CorpusIndex over a DualEncoder; `second` is a token
-    CorpusIndex holding the same documents under the same ids; `candidates` is how many documents the first stage
-    proposes per query.  A CorpusIndex returns at most 1024 results per query (the limit of ops.topk_merge), so with
+    """Retrieve with a cheap index, re-rank with a better one: `first` is anything with search(queries, k) ->
+    (scores, ids) and add(documents), in practice a [CLS] CorpusIndex over a DualEncoder, a BM25Index, a SparseCorpusIndex
+    or a HybridSearch; `second` is anything with rerank(queries, candidates, k) holding the same documents under the same
+    ids: a token CorpusIndex (MaxSim), or a [CLS] CorpusIndex with a refine store (refine="full" on a plain index: the
+    lexical -> bi-encoder pipeline); `candidates` is how many documents the first stage proposes per query.  A CorpusIndex returns at most 1024 results per query (the limit of ops.topk_merge), so with
     one as the first stage `candidates` is at most 1024; another first stage sets its own limit."""
 
     def __init__(self, first, second, candidates):

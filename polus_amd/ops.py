@@ -14,6 +14,8 @@ from ._lib import (F32, BF16, K_CONTIG, K_STRIDED, ACT_NONE, ACT_GELU, ACT_SWISH
 # the product-quantisation wrappers (csrc/pq.hip) live in a module of their own and are part of this namespace
 from .pq_ops import (IvfPqRoute, PqRoute, ivfpq_coarse_update, ivfpq_residual, ivfpq_scores_ids, ivfpq_scores_ids_route,
                      pq_decode, pq_encode, pq_lut, pq_scores, pq_scores_route, pq_update)
+# so do the refine wrappers (csrc/refine.hip)
+from .refine_ops import cls_fp8_dequantize, cls_fp8_quantize, cls_rerank, cls_rerank_fp8
 
 # bench.py instrumentation: when a list, every gemm launch appends (kind, flops, ev0, ev1)
 GEMM_PROFILE = None
